@@ -1,6 +1,15 @@
 """Benchmark: dense revised-simplex iterations/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C4|C5 | --m M --n N]
+                    [--dump-outputs DIR] [--full]
+
+A plain run builds the context, warms up, times the K steps and prints the
+result line (`value`, `ms_per_step`, `config`, `ranks`, `timed_region`).
+`--dump-outputs DIR` also writes the solver state the timed steps left
+(x_b, b_ixs, y, z) as DIR/<name>.npy.  Everything else described below -- the
+windows timed after the region, the event-timed kernel split and roofline,
+`explicit`, `pricing_c4`, `solve_to_optimum`, `steepest`, `tableau` and
+`cpu_baseline` -- takes runs of its own and is measured only with `--full`.
 
 A *step* is one simplex iteration (pricing over the non-basic columns, entering
 MINLOC, FTRAN, ratio test, B^-1 update, x_b / y update) on the seeded dense
@@ -150,6 +159,14 @@ def parse():
     ap.add_argument("--m", type=int, default=None)
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the next three windows, the event-timed kernel "
+                         "split and roofline, explicit B^-1, C4 sharded pricing, the whole solve, steepest edge, "
+                         "the window tableau and the CPU baseline (each can be skipped with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (rank 0: x_b, b_ixs, y of the basis "
+                         "rows and the objective z, float64) as DIR/<name>.npy; reading it back folds the eta "
+                         "window, so with --full the windows timed after the region start from a fresh window")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_r06.json"),
@@ -212,6 +229,7 @@ def describe_dispatch(d):
 
 def main():
     args = parse()
+    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -275,7 +293,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         return t.tolist()
 
-    def timed_window(window, events, spread=False):
+    def timed_window(window, events, spread=False, dump=False):
         """W warm-up pivots, untimed pivots to the next window boundary, one
         more untimed whole window (so the timed passes are not the batch
         graph's first replay), then K (rounded up to whole windows) timed
@@ -324,6 +342,14 @@ def main():
         cols = ctx.ftran_cols()
         delta = {k: d1[k] - d0[k] for k in ("eager_passes", "graph_launches", "graph_passes",
                                             "persistent_launches", "persistent_passes", "folds", "graph_builds")}
+        outputs = None
+        if dump:
+            # what a caller of the timed path receives after its last step
+            # (all ranks read back: a row-sharded x_b is gathered collectively)
+            wd.arm("output readback", ctx)
+            s = ctx.state()
+            outputs = {"x_b": s["x_b"], "b_ixs": s["b_ixs"].astype(np.float64), "y": s["y"],
+                       "z": np.array([ctx.objective()], dtype=np.float64)}
         windows = None
         if spread and st == 0:
             ts, pv = [], piv1
@@ -354,7 +380,7 @@ def main():
         ctx.close()
         wd.disarm()
         return {"cfg": cfg, "dt": dt, "pivots": piv1 - piv0, "steps": steps, "lead": lead + warm, "dispatch": delta,
-                "windows_s_per_pivot": windows,
+                "windows_s_per_pivot": windows, "outputs": outputs,
                 "pt": pt, "lt": lt, "nb": 0.5 * (info0["local_nonbasic"] + info1["local_nonbasic"]),
                 "price_bytes": 0.5 * (info0["bytes_price"] + info1["bytes_price"]), "ftran_cols": cols,
                 "status": int(st), "comm": comm}
@@ -382,7 +408,7 @@ def main():
     win = args.window
     # (1) the measured run: undisturbed (no events), graph replay where the
     #     library captures, timed over whole windows
-    main_run = timed_window(win, False, spread=True)
+    main_run = timed_window(win, False, spread=args.full, dump=args.dump_outputs is not None)
     cfg = main_run["cfg"]
     win = cfg["window"]
     value = main_run["pivots"] / main_run["dt"] if main_run["dt"] > 0 else 0.0
@@ -400,63 +426,131 @@ def main():
         if multi:
             dist.destroy_process_group()
         raise SystemExit(f"bench.py: rank evidence check failed: {e}")
-    # (2) the same window with per-dispatch hipEvents (eager): kernel split
-    ev_run = timed_window(args.window, True)
-    ks = kernel_split(ev_run, win)
-    price_ms_max, minloc_ms_max, update_ms_max = reduce_max([ks["price_ms"], ks["minloc_ms"], ks["update_ms"]])
-    price_bytes_all = reduce_sum([ks["price_bytes"]])[0]
-    price_gbs = ks["price_bytes"] / (ks["price_ms"] * 1e-3) / 1e9 if ks["price_ms"] > 0 else 0.0
-    update_gbs = ks["update_bytes"] / (ks["update_ms"] * 1e-3) / 1e9 if ks["update_ms"] > 0 else 0.0
-    # fold: dense -- B_w read + written, U / Qrows read once
-    # per window; compact (k_cfold) -- the operand's S columns read, written
-    # and scattered into the dense B_w, U read once
-    S_end = ev_run["ftran_cols"]
-    if win and cfg.get("compact_fold"):
-        fold_bytes = 8.0 * m * (3.0 * S_end + win)
-    else:
-        fold_bytes = 16.0 * m * m + 8.0 * win * 2 * m if win else 0.0
-    b_upd = 8.0 * m * S_end + fold_bytes / (win - 1) if win else 16.0 * m * m
-    b_moved = price_bytes_all + b_upd                       # this representation, per pivot
-    b_alg = 8.0 * (m + 1) * (n - m) + 16.0 * m * m         # SURVEY.md §8(d) B_alg, per pivot
+    if args.dump_outputs is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in main_run["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
-    traffic = None
-    if os.path.exists(args.traffic_json):
-        try:
-            with open(args.traffic_json) as f:
-                tj = json.load(f)
-            if tj.get("m") == m and tj.get("n") == n and world == 1:
-                traffic = tj.get("price_hbm_bytes_per_launch")
-        except (OSError, ValueError):
-            traffic = None
+    def full_blocks():
+        """What --full adds to the result line; each block takes runs of its own."""
+        # (2) the same window with per-dispatch hipEvents (eager): kernel split
+        ev_run = timed_window(args.window, True)
+        ks = kernel_split(ev_run, win)
+        price_ms_max, minloc_ms_max, update_ms_max = reduce_max([ks["price_ms"], ks["minloc_ms"], ks["update_ms"]])
+        price_bytes_all = reduce_sum([ks["price_bytes"]])[0]
+        price_gbs = ks["price_bytes"] / (ks["price_ms"] * 1e-3) / 1e9 if ks["price_ms"] > 0 else 0.0
+        update_gbs = ks["update_bytes"] / (ks["update_ms"] * 1e-3) / 1e9 if ks["update_ms"] > 0 else 0.0
+        # fold (DESIGN.md §4a): dense -- B_w read + written, U / Qrows read once
+        # per window; compact (k_cfold) -- the operand's S columns read, written
+        # and scattered into the dense B_w, U read once
+        S_end = ev_run["ftran_cols"]
+        if win and cfg.get("compact_fold"):
+            fold_bytes = 8.0 * m * (3.0 * S_end + win)
+        else:
+            fold_bytes = 16.0 * m * m + 8.0 * win * 2 * m if win else 0.0
+        b_upd = 8.0 * m * S_end + fold_bytes / (win - 1) if win else 16.0 * m * m
+        b_moved = price_bytes_all + b_upd                       # this representation, per pivot
+        b_alg = 8.0 * (m + 1) * (n - m) + 16.0 * m * m         # SURVEY.md §8(d) B_alg, per pivot
 
-    explicit = None
-    if not args.no_explicit and win > 0 and not row_shard:
-        explicit = explicit_block(timed_window, kernel_split, reduce_max, m, n)
+        traffic = None
+        if os.path.exists(args.traffic_json):
+            try:
+                with open(args.traffic_json) as f:
+                    tj = json.load(f)
+                if tj.get("m") == m and tj.get("n") == n and world == 1:
+                    traffic = tj.get("price_hbm_bytes_per_launch")
+            except (OSError, ValueError):
+                traffic = None
 
-    sharded = None
-    if not args.no_sharded_pricing and (m, n) != CONFIGS["C4"]:
-        with wd.phase("pricing_c4 (C4 sharded pricing window)"):
-            sharded = sharded_pricing_block(make, reduce_max, reduce_sum, world, args)
+        explicit = None
+        if not args.no_explicit and win > 0 and not row_shard:
+            explicit = explicit_block(timed_window, kernel_split, reduce_max, m, n)
 
-    to_opt = None
-    if not args.no_solve_to_optimum:
-        to_opt = solve_to_optimum_block(make, barrier, reduce_max, torch, args.window, main_run, value, wd)
+        sharded = None
+        if not args.no_sharded_pricing and (m, n) != CONFIGS["C4"]:
+            with wd.phase("pricing_c4 (C4 sharded pricing window)"):
+                sharded = sharded_pricing_block(make, reduce_max, reduce_sum, world, args)
 
-    steep = None
-    if world == 1 and not multi and not args.no_steepest and win > 0:
-        steep = steepest_block(spx, torch, m, n, args, local)
+        to_opt = None
+        if not args.no_solve_to_optimum:
+            to_opt = solve_to_optimum_block(make, barrier, reduce_max, torch, args.window, main_run, value, wd)
 
-    tab = None
-    if world == 1 and not multi and not args.no_tableau:
-        tab = tableau_block(spx, torch, m, n, args, local)
+        steep = None
+        if world == 1 and not multi and not args.no_steepest and win > 0:
+            steep = steepest_block(spx, torch, m, n, args, local)
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(m, n, args.seed, args.cpu_seconds)
-        cpu["glpk"] = glpk_status()
+        tab = None
+        if world == 1 and not multi and not args.no_tableau:
+            tab = tableau_block(spx, torch, m, n, args, local)
+
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(m, n, args.seed, args.cpu_seconds)
+            cpu["glpk"] = glpk_status()
+        return {
+            "roofline": {
+                "bound": "hbm",
+                "kernel": ("k_loop pricing phase (in-kernel clock, workgroup 0), rank 0" if cfg.get("persistent")
+                           else "k_price (pricing GEMV + entering argmin"
+                           + (", prologue: the previous pivot's deferred ratio-test reduction" if cfg.get("defer_tail")
+                              else "") + "), rank 0"),
+                "achieved": price_gbs,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": price_gbs / HBM_PEAK_GBS,
+                "traffic": traffic,
+                "algorithmic_bytes_per_launch": ks["price_bytes"],
+                "avg_launch_ms": ks["price_ms"],
+            },
+            "kernels": {
+                "k_update": {"what": ("rank-1 update (RMW) + FTRAN" if not win else
+                                      "FTRAN (B_w read-only) + ratio-test partials; the leaving argmin and the "
+                                      "bookkeeping run in the next k_price (deferred tail)" if cfg.get("defer_tail")
+                                      else "FTRAN (B_w read-only) + ratio test"),
+                             "avg_launch_ms": ks["update_ms"], "algorithmic_bytes_per_launch": ks["update_bytes"],
+                             "achieved_GBps": update_gbs, "frac": update_gbs / HBM_PEAK_GBS},
+                "k_fold": ({"kernels": ("k_bc_list + k_cfold (the listed columns of B_w only)"
+                                        if cfg.get("compact_fold") else "k_fold + k_bc_list + k_bc_gather"),
+                            "avg_launch_ms": ks["fold_ms"], "launches_timed": ks["folds"],
+                            "per_pivot_ms": ks["fold_ms"] / (win - 1),
+                            "algorithmic_bytes_per_launch": fold_bytes,
+                            "achieved_GBps": fold_bytes / (ks["fold_ms"] * 1e-3) / 1e9 if ks["fold_ms"] > 0 else 0.0}
+                           if win else None),
+                # whole-iteration roofline of this representation: the bytes
+                # it moves per pivot (pricing stream, FTRAN operand, fold / 63)
+                # over the pivot time.  SURVEY.md §8(d)'s B_alg counts the
+                # explicit representation's per-pivot B^-1 rewrite, which the
+                # window never does, so B_alg / time is only an equivalent
+                # rate, not a fraction of peak (the explicit block's
+                # iteration.frac is that representation's own roofline)
+                "iteration": {"algorithmic_bytes": b_moved,
+                              "achieved_GBps": b_moved * value / 1e9,
+                              "frac": b_moved * value / 1e9 / HBM_PEAK_GBS,
+                              "bytes_survey_B_alg": b_alg,
+                              "equivalent_GBps_survey": b_alg * value / 1e9,
+                              "explicit_iteration_frac": explicit["iteration"]["frac"] if explicit else None,
+                              "event_timed_ms_per_step": 1e3 * ev_run["dt"] / max(ev_run["pivots"], 1),
+                              "event_timed_dispatch": describe_dispatch(ev_run["dispatch"])},
+            },
+            "pricing": {
+                "bytes_all_ranks": price_bytes_all,
+                "max_rank_price_ms": price_ms_max,
+                "max_rank_price_plus_minloc_ms": minloc_ms_max,
+                "throughput_GBps": price_bytes_all / (minloc_ms_max * 1e-3) / 1e9 if minloc_ms_max > 0 else 0.0,
+                "max_rank_update_ms": update_ms_max,
+            },
+            "solve_to_optimum": to_opt,
+            "steepest": steep,
+            "explicit": explicit,
+            "pricing_c4": sharded,
+            "tableau": tab,
+            "cpu_baseline": cpu,
+        }
+
+    extra = full_blocks() if args.full else {}
 
     if rank == 0:
-        fc = ev_run["ftran_cols"]
+        fc = main_run["ftran_cols"]  # (the event-timed copy of the window ends on the same count)
         rep = (("eta window %d: B_w + U R, FTRAN stream read-only, rank-%d fold every %d pivots" % (win, win - 1, win - 1)
                 + ("; B_w's non-unit columns only (compact FTRAN operand, %d of %d columns at the window's end)"
                    % (fc, m) if fc < m else ""))
@@ -523,64 +617,11 @@ def main():
                 "next_windows_spread": ((max(main_run["windows_s_per_pivot"]) / min(main_run["windows_s_per_pivot"])
                                          - 1.0) if main_run["windows_s_per_pivot"] else None),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": ("k_loop pricing phase (in-kernel clock, workgroup 0), rank 0" if cfg.get("persistent")
-                           else "k_price (pricing GEMV + entering argmin"
-                           + (", prologue: the previous pivot's deferred ratio-test reduction" if cfg.get("defer_tail")
-                              else "") + "), rank 0"),
-                "achieved": price_gbs,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": price_gbs / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "algorithmic_bytes_per_launch": ks["price_bytes"],
-                "avg_launch_ms": ks["price_ms"],
-            },
-            "kernels": {
-                "k_update": {"what": ("rank-1 update (RMW) + FTRAN" if not win else
-                                      "FTRAN (B_w read-only) + ratio-test partials; the leaving argmin and the "
-                                      "bookkeeping run in the next k_price (deferred tail)" if cfg.get("defer_tail")
-                                      else "FTRAN (B_w read-only) + ratio test"),
-                             "avg_launch_ms": ks["update_ms"], "algorithmic_bytes_per_launch": ks["update_bytes"],
-                             "achieved_GBps": update_gbs, "frac": update_gbs / HBM_PEAK_GBS},
-                "k_fold": ({"kernels": ("k_bc_list + k_cfold (the listed columns of B_w only)"
-                                        if cfg.get("compact_fold") else "k_fold + k_bc_list + k_bc_gather"),
-                            "avg_launch_ms": ks["fold_ms"], "launches_timed": ks["folds"],
-                            "per_pivot_ms": ks["fold_ms"] / (win - 1),
-                            "algorithmic_bytes_per_launch": fold_bytes,
-                            "achieved_GBps": fold_bytes / (ks["fold_ms"] * 1e-3) / 1e9 if ks["fold_ms"] > 0 else 0.0}
-                           if win else None),
-                # whole-iteration roofline of this representation: the bytes
-                # it moves per pivot (pricing stream, FTRAN operand, fold / 63)
-                # over the pivot time.  SURVEY.md §8(d)'s B_alg counts the
-                # explicit representation's per-pivot B^-1 rewrite, which the
-                # window never does, so B_alg / time is only an equivalent
-                # rate, not a fraction of peak (the explicit block's
-                # iteration.frac is that representation's own roofline)
-                "iteration": {"algorithmic_bytes": b_moved,
-                              "achieved_GBps": b_moved * value / 1e9,
-                              "frac": b_moved * value / 1e9 / HBM_PEAK_GBS,
-                              "bytes_survey_B_alg": b_alg,
-                              "equivalent_GBps_survey": b_alg * value / 1e9,
-                              "explicit_iteration_frac": explicit["iteration"]["frac"] if explicit else None,
-                              "event_timed_ms_per_step": 1e3 * ev_run["dt"] / max(ev_run["pivots"], 1),
-                              "event_timed_dispatch": describe_dispatch(ev_run["dispatch"])},
-            },
-            "pricing": {
-                "bytes_all_ranks": price_bytes_all,
-                "max_rank_price_ms": price_ms_max,
-                "max_rank_price_plus_minloc_ms": minloc_ms_max,
-                "throughput_GBps": price_bytes_all / (minloc_ms_max * 1e-3) / 1e9 if minloc_ms_max > 0 else 0.0,
-                "max_rank_update_ms": update_ms_max,
-            },
-            "solve_to_optimum": to_opt,
-            "steepest": steep,
-            "explicit": explicit,
-            "pricing_c4": sharded,
-            "tableau": tab,
-            "cpu_baseline": cpu,
         }
+        out.update(extra)
+        if args.dump_outputs is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": sorted(main_run["outputs"]),
+                              "what": "state after the last timed pivot (spx_get_state, spx_objective), float64"}
         if args.share_gpu:
             out["rehearsal"] = (f"{world} ranks share one GPU (--share-gpu: gloo process group, mailbox MINLOC); "
                                 "checks the multi-rank path, not a scaling number")

@@ -43,6 +43,18 @@ def test_run_to_exit_chunks(total):
     assert sum(ks) == bench.calls_passes(calls)
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """A plain run measures the headline only: the blocks that take runs of
+    their own are behind --full, and nothing is written without --dump-outputs."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None
+    assert (a.steps, a.warmup, a.m, a.n) == (20, 5, 4096, 16384)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
 def test_schedule_matches_spx_solve():
     src = open(os.path.join(ROOT, "simplex_method_gpu_amd", "csrc", "spx_api.cpp")).read()
     body = src[src.index("int spx_solve("):]

@@ -14,7 +14,7 @@ mkdir -p $OUT
 export MASTER_ADDR=127.0.0.1 GPU_MAX_HW_QUEUES=1
 run8() {  # tag, port, extra bench args
   timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-      --master-port $2 bench.py --gpus 8 --share-gpu --steps 20 --warmup 5 $3 > $OUT/$1.log 2>&1 \
+      --master-port $2 bench.py --full --gpus 8 --share-gpu --steps 20 --warmup 5 $3 > $OUT/$1.log 2>&1 \
       || { tail -40 $OUT/$1.log; return 1; }
   grep '^{' $OUT/$1.log | tail -1 > $OUT/$1.json
   python3 -c "import json; d=json.load(open('$OUT/$1.json')); r=d['ranks']; t=d.get('solve_to_optimum') or {}; p=d.get('pricing_c4') or {}; print('$1', 'world', r['world_size'], 'exchange', r['exchange'], 'ranks', [x['rank'] for x in r['per_rank']], 'value', round(d['value'], 1), 'to_opt', t.get('status'), t.get('pivots'), 'pricing_c4 GB/s', round(p.get('throughput_GBps', 0)))"
