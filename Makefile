@@ -32,11 +32,15 @@ $(BUILD)/spx_loop.o: $(SRC)/spx_loop.hip $(SRC)/spx_loop.h $(SRC)/spx_grid.h $(S
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/spx_api.o: $(SRC)/spx_api.cpp $(SRC)/spx_loop.h $(SRC)/spx_kernels.h $(SRC)/spx_reinv.h $(SRC)/spx_tableau.h $(SRC)/spx_device.h include/simplex.h
+$(BUILD)/spx_dual.o: $(SRC)/spx_dual.hip $(SRC)/spx_dual.h $(SRC)/spx_device.h $(SRC)/spx_common.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(BUILD)/spx_loop.o $(BUILD)/spx_api.o
+$(BUILD)/spx_api.o: $(SRC)/spx_api.cpp $(SRC)/spx_loop.h $(SRC)/spx_dual.h $(SRC)/spx_kernels.h $(SRC)/spx_reinv.h $(SRC)/spx_tableau.h $(SRC)/spx_device.h include/simplex.h
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIB): $(BUILD)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(BUILD)/spx_loop.o $(BUILD)/spx_dual.o $(BUILD)/spx_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ $(LDFLAGS)
 
 $(CLI): $(SRC)/solver_main.cpp $(SRC)/lp_io.cpp $(SRC)/lp_io.h $(SRC)/mps_io.cpp $(SRC)/mps_io.h include/simplex.h $(LIB)
@@ -64,13 +68,13 @@ AB        := $(PKG)/_ab
 xlib:
 	@mkdir -p $(AB)/x$(X)
 	$(HIPCC) $(HIPFLAGS) $(XFLAGS) -c $(SRC)/spx_kernels.hip -o $(AB)/x$(X)/spx_kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/x$(X)/libsimplex.so $(AB)/x$(X)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(BUILD)/spx_loop.o $(BUILD)/spx_api.o $(LDFLAGS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/x$(X)/libsimplex.so $(AB)/x$(X)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(BUILD)/spx_loop.o $(BUILD)/spx_dual.o $(BUILD)/spx_api.o $(LDFLAGS)
 
 # persistent-loop experiment build: make xloop X=name XFLAGS="-DSPX_LOOP_FU=4"
 xloop:
 	@mkdir -p $(AB)/l$(X)
 	$(HIPCC) $(HIPFLAGS) $(XFLAGS) -c $(SRC)/spx_loop.hip -o $(AB)/l$(X)/spx_loop.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/l$(X)/libsimplex.so $(BUILD)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(AB)/l$(X)/spx_loop.o $(BUILD)/spx_api.o $(LDFLAGS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/l$(X)/libsimplex.so $(BUILD)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(AB)/l$(X)/spx_loop.o $(BUILD)/spx_dual.o $(BUILD)/spx_api.o $(LDFLAGS)
 
 abclean:
 	rm -rf $(AB)

@@ -19,7 +19,8 @@
  * Conventions
  *   - A is m x n COLUMN-major (column j at A + j*m), as the reference's R2C
  *     (src/v4_cub_reduction.cu:59-60); the last m columns must be the slack
- *     identity and b >= 0 (the reference's unchecked assumption, v4:272-277).
+ *     identity and, for the primal loop, b >= 0 (the reference's unchecked
+ *     assumption, v4:272-277); b of any sign with SPX_ALGO_DUAL.
  *   - Everything is fp64.  Indices are 0-based int64.
  *   - Every function returns SPX_OK (0) or a negative SPX_ERR_* code; nothing
  *     exits or throws across the ABI.  spx_last_error() gives a message.
@@ -47,6 +48,9 @@ extern "C" {
 #define SPX_STATUS_OPTIMUM_FOUND  1
 #define SPX_STATUS_UNBOUNDED      2
 #define SPX_STATUS_THETA_OVERFLOW 3 /* kept for ABI parity; unreachable since v2 */
+#define SPX_STATUS_INFEASIBLE     4 /* dual loop only: a basic variable is negative
+                                       and its row has no dual ratio-test candidate,
+                                       so no x >= 0 satisfies the constraints       */
 
 #define SPX_OK             0
 #define SPX_ERR_ARG       -1  /* bad argument (m > n, m <= 0, NULL, ...)     */
@@ -87,9 +91,11 @@ typedef struct spx_opts {
                              basis columns (spx_reinvert) every K pivots;
                              0 = never (the reference never does)            */
     double  piv_tol;      /* SPX_RATIO_GUARDED / HARRIS: rows need alpha_i >
-                             piv_tol (default 1e-9)                           */
+                             piv_tol (default 1e-9); SPX_ALGO_DUAL: ratio-test
+                             candidates need rho.A_j < -piv_tol               */
     double  feas_tol;     /* SPX_RATIO_HARRIS: primal feasibility tolerance
-                             delta of the first pass (default 1e-9)          */
+                             delta of the first pass (default 1e-9);
+                             SPX_ALGO_DUAL: rows leave while x_b < -feas_tol  */
     int32_t pricing;      /* entering-column rule, SPX_PRICING_* (default DANTZIG) */
     int32_t loop_block;   /* tuning: threads per workgroup of the persistent loop
                              kernel (512 / 1024), 0 = auto                     */
@@ -99,8 +105,29 @@ typedef struct spx_opts {
                              0 = off.  The reference prints nothing of the
                              kind; the parity tests compare it with the
                              oracle's pivot sequence.                        */
-    int32_t reserved;
+    int32_t algorithm;    /* SPX_ALGO_PRIMAL (default) or SPX_ALGO_DUAL; the field
+                             was `reserved` (0) before, the layout is unchanged */
 } spx_opts;
+
+/* Simplex algorithm of spx_iterate / spx_solve.
+ * PRIMAL: the loop above; needs a primal feasible basis (b >= 0 at the slack
+ *         basis).
+ * DUAL:   the dual simplex method, for a basis that is dual
+ *         feasible (every non-basic e_j >= -eps; checked before the first dual
+ *         pass: SPX_ERR_STATE "basis is not dual feasible") but may have
+ *         negative x_b: a covering LP max -c.x, -G x + s = -h with c >= 0 at
+ *         its slack basis, or an optimal basis after spx_set_rhs.  Leaving row
+ *         q = argmin x_b[i] over x_b[i] < -feas_tol (none: OPTIMUM_FOUND);
+ *         with rho = row q of B^-1, a_j = rho.A_j and d_j = y.A_j - c_j the
+ *         entering column is the argmin of max(d_j, 0) / -a_j over non-basic
+ *         a_j < -piv_tol (none: SPX_STATUS_INFEASIBLE); first index on ties.
+ *         One rank, explicit B^-1 (window 0 resolves to -1), Dantzig pricing;
+ *         spx_create rejects nranks > 1, an eta window, the tableau, the
+ *         Harris ratio test and Devex / steepest-edge pricing with
+ *         SPX_ERR_ARG.  spx_price / spx_pivot and spx_group_iterate return
+ *         SPX_ERR_STATE under it.  refactor_every works as in the primal loop. */
+#define SPX_ALGO_PRIMAL 0
+#define SPX_ALGO_DUAL   1
 
 /* Entering-column rules (README.md:16-17 "steepest edge").
  * DANTZIG: most negative e_j (v4:288-302).
@@ -276,6 +303,21 @@ int spx_reinvert(spx_ctx* ctx);
  * On SPX_ERR_SINGULAR the context has no valid basis until spx_reset. */
 int spx_set_basis(spx_ctx* ctx, const int64_t* basis);
 
+/* Switch the context between the primal and the dual loop (SPX_ALGO_*); the
+ * basis, B^-1, x_b, y and the pivot count are kept and the status goes back to
+ * running, so the new loop re-tests its own stopping rule.  SPX_ERR_STATE when
+ * the context cannot run the dual loop: an eta window or tableau context,
+ * nranks > 1, Harris ratio test, Devex / steepest-edge pricing (the message
+ * names the combination). */
+int spx_set_algorithm(spx_ctx* ctx, int32_t algorithm);
+
+/* New right-hand side b[0..m), any signs: uploaded, then x_b = B^-1 b for the
+ * current basis (through spx_reinvert), status back to running, pivot count
+ * kept.  The basis stays dual feasible, so after an optimal solve
+ * spx_set_algorithm(SPX_ALGO_DUAL) + spx_solve re-optimises from it.  One rank,
+ * replicated B^-1 (SPX_ERR_STATE otherwise). */
+int spx_set_rhs(spx_ctx* ctx, const double* b);
+
 /* Whole solve, device-resident: at most max_iter loop passes (reference
  * MAX_ITER, v4:19, do/while at v4:286-359).  Writes z, x_b[m], b_ixs[m] (basis
  * order) for every status (the reference writes them only on optimum);
@@ -323,7 +365,8 @@ int spx_get_trace(spx_ctx* ctx, int64_t* p, int64_t* q, int64_t cap, int64_t* co
 int spx_get_weights(spx_ctx* ctx, double* w);
 
 /* With SPX_FLAG_TIMING: total device milliseconds and launch counts of the
- * pricing kernel and of the fused update kernel since the last call (resets). */
+ * pricing kernel and of the fused update kernel since the last call (resets).
+ * Dual loop: the dual ratio-test kernel and the FTRAN + update kernel. */
 int spx_kernel_times(spx_ctx* ctx, double* price_ms, int64_t* price_launches,
                      double* update_ms, int64_t* update_launches);
 

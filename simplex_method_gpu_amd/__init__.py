@@ -25,7 +25,7 @@ from ._lib import SimplexError, SpxOpts, check, load
 __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_unique_id",
            "shard_range", "minloc_merge", "group_iterate", "group_sync", "check_ranks",
            "SimplexError", "FLAG_TIMING", "RATIO_REFERENCE", "RATIO_GUARDED", "RATIO_HARRIS",
-           "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST"]
+           "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -44,6 +44,9 @@ FLAG_PRICE_TAIL = 1024  # k_price's last workgroup merges the entering candidate
 RATIO_REFERENCE, RATIO_GUARDED, RATIO_HARRIS = 0, 1, 2
 # entering-column rules (include/simplex.h SPX_PRICING_*)
 PRICING_DANTZIG, PRICING_DEVEX, PRICING_STEEPEST = 0, 1, 2
+# simplex algorithm of iterate / solve (include/simplex.h SPX_ALGO_*): the dual
+# loop starts from a dual feasible basis whose x_b may be negative (b of any sign)
+ALGO_PRIMAL, ALGO_DUAL = 0, 1
 
 
 class SolveStatus(IntEnum):
@@ -51,6 +54,7 @@ class SolveStatus(IntEnum):
     OptimumFound = 1
     Unbounded = 2
     ThetaOverflow = 3
+    Infeasible = 4  # dual loop: a negative basic variable whose row has no ratio-test candidate
 
 
 @dataclass
@@ -155,7 +159,7 @@ class Context:
                  ratio_test: int = 0, piv_tol: float = 1e-9, feas_tol: float = 1e-9, refactor_every: int = 0,
                  pricing: int = 0, persist: bool | None = None, loop_block: int = 0, comm1: bool = False,
                  tableau: bool = False, trace: int = 0, counted_tail: bool = False,
-                 price_tail: bool = False):
+                 price_tail: bool = False, algorithm: int = ALGO_PRIMAL):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -168,6 +172,7 @@ class Context:
         o.pricing = pricing  # PRICING_DANTZIG / PRICING_DEVEX / PRICING_STEEPEST
         o.loop_block = loop_block
         o.trace_cap = trace  # record the first `trace` pivots' (p, q) on the device
+        o.algorithm = algorithm  # ALGO_PRIMAL / ALGO_DUAL
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
@@ -260,6 +265,20 @@ class Context:
         if bs.shape != (self.m,):
             raise ValueError(f"basis must have {self.m} entries")
         check(self._L.spx_set_basis(self._h, _ptr(bs)))
+
+    def set_algorithm(self, algo: int):
+        """Switch between the primal and the dual loop (spx_set_algorithm):
+        basis, B^-1, x_b, y and the pivot count are kept, the status goes back
+        to running."""
+        check(self._L.spx_set_algorithm(self._h, algo))
+
+    def set_rhs(self, b):
+        """New right-hand side of any sign (spx_set_rhs): x_b = B^-1 b for the
+        current basis, which stays dual feasible; status back to running."""
+        bv = np.ascontiguousarray(b, dtype=np.float64)
+        if bv.shape != (self.m,):
+            raise ValueError(f"b must have {self.m} entries")
+        check(self._L.spx_set_rhs(self._h, _ptr(bv)))
 
     # -- loop
     def iterate(self, k: int):
@@ -430,8 +449,11 @@ class Context:
         return dict(zip(keys, list(out)))
 
 
-def solve(A_cols, b, c, max_iter: int = (1 << 62), eps: float = 1e-7, device: int = -1) -> SolveResult:
+def solve(A_cols, b, c, max_iter: int = (1 << 62), eps: float = 1e-7, device: int = -1,
+          algorithm: int = ALGO_PRIMAL) -> SolveResult:
     """Mirror of the reference's ``solve()`` (v4:219-380): A column-major as
-    (n, m), returns z, status, x_b and b_ixs in basis order, pivots made."""
-    with Context(A_cols, b, c, eps=eps, device=device) as ctx:
+    (n, m), returns z, status, x_b and b_ixs in basis order, pivots made.
+    ``algorithm=ALGO_DUAL`` runs the dual simplex loop from the slack basis
+    (c_j <= 0 for every column; b of any sign)."""
+    with Context(A_cols, b, c, eps=eps, device=device, algorithm=algorithm) as ctx:
         return ctx.solve(max_iter)

@@ -38,7 +38,7 @@ class SpxOpts(ctypes.Structure):
         ("pricing", ctypes.c_int32),
         ("loop_block", ctypes.c_int32),
         ("trace_cap", ctypes.c_int32),
-        ("reserved", ctypes.c_int32),
+        ("algorithm", ctypes.c_int32),
     ]
 
 
@@ -56,6 +56,8 @@ SIGNATURES = {
     "spx_reset": (ctypes.c_int, [_p]),
     "spx_reinvert": (ctypes.c_int, [_p]),
     "spx_set_basis": (ctypes.c_int, [_p, _p]),
+    "spx_set_algorithm": (ctypes.c_int, [_p, _i32]),
+    "spx_set_rhs": (ctypes.c_int, [_p, _p]),
     "spx_group_iterate": (ctypes.c_int, [_p, _i32, _i64, _p, _p]),
     "spx_group_sync": (ctypes.c_int, [_p, _i32]),
     "spx_solve": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _p]),

@@ -24,6 +24,10 @@
 //   --refactor K   rebuild B^-1 from the basis every K pivots (spx_reinvert)
 //   --window W     B^-1 representation (0 auto, -1 explicit, 8..64 eta window)
 //   --pricing P    entering-column rule: dantzig (v4:288-302, default) | devex | steepest
+//   --dual         solve with the dual simplex loop (SPX_ALGO_DUAL, simplex.h): from
+//                  the slack basis, which must be dual feasible (every c_j <= 0;
+//                  b of any sign); "Problem infeasible." when no x >= 0 exists;
+//                  a slack basis that is not dual feasible is an error (exit 1)
 //   --tableau      window tableau (SPX_FLAG_TABLEAU): T_w = B_w A
 //                  kept in HBM, no per-pivot A / B^-1 stream
 //   --mps          the input is an MPS file (mps_io.h): converted to the
@@ -68,7 +72,7 @@ static void print_elapsed_time(const char* msg, double dur) {
 static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
-                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau]"
+                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -87,7 +91,7 @@ int main(int argc, char* argv[]) {
     int ratio = -1, window = 0, pricing = SPX_PRICING_DANTZIG;
     double piv_tol = 1e-9, feas_tol = 1e-9, big_m = 0.0;
     int64_t refactor = 0;
-    bool mps_in = false, tableau = false;
+    bool mps_in = false, tableau = false, dual = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -121,6 +125,7 @@ int main(int argc, char* argv[]) {
         else if (s == "--window") { need(1); window = std::atoi(argv[++a]); }
         else if (s == "--mps") mps_in = true;
         else if (s == "--tableau") tableau = true;
+        else if (s == "--dual") dual = true;
         else if (s == "--pricing") {
             need(1);
             const std::string r = argv[++a];
@@ -194,6 +199,7 @@ int main(int argc, char* argv[]) {
     o.window = window;
     o.pricing = pricing;
     if (tableau) o.flags |= SPX_FLAG_TABLEAU;
+    if (dual) o.algorithm = SPX_ALGO_DUAL;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)
@@ -261,6 +267,7 @@ int main(int argc, char* argv[]) {
             break;
         case SPX_STATUS_UNBOUNDED: std::cout << "Problem unbounded.\n"; break;
         case SPX_STATUS_THETA_OVERFLOW: std::cout << "Theta overflow.\n"; break;
+        case SPX_STATUS_INFEASIBLE: std::cout << "Problem infeasible.\n"; break;
         default: std::cout << "MAX_ITER exceeded.\n"; break;
     }
     std::cout << '\n';

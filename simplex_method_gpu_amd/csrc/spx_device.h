@@ -58,7 +58,14 @@
 
 namespace spx {
 
-enum : int32_t { ST_RUNNING = 0, ST_OPTIMAL = 1, ST_UNBOUNDED = 2, ST_WINDOW_FULL = 16, ST_HANDOFF_TIMEOUT = 17 };
+enum : int32_t {
+    ST_RUNNING = 0,
+    ST_OPTIMAL = 1,
+    ST_UNBOUNDED = 2,
+    ST_INFEASIBLE = 4,  // dual loop (spx_dual.h): a row with x_b < 0 and no ratio-test candidate
+    ST_WINDOW_FULL = 16,
+    ST_HANDOFF_TIMEOUT = 17
+};
 
 // (value, global index) candidate; the order is value, then smallest index —
 // cub::DeviceReduce::ArgMin's first-index semantics (v4:294,324) for every

@@ -1,0 +1,76 @@
+// spx_dual.h — the dual simplex loop's kernels (spx_dual.hip): one rank,
+// explicit B^-1 (Params::win == 0, in-place storage).  DESIGN.md §7d.
+//
+// A dual pass at iteration it is three launches on the context's stream; the
+// kernel boundaries are the only ordering between them:
+//   k_dual_step    one workgroup.  Finishes the pivot the previous pass left
+//                  in DualRec (x_b -= theta alpha, x_b[q] = theta, y -= (d_p /
+//                  alpha_q) rho, basis bookkeeping, iter + 1), then picks the
+//                  leaving row q = argmin x_b[i] over x_b[i] < -feas_tol (none:
+//                  ST_OPTIMAL), forms the pivot row rho = row q of the true
+//                  B^-1 and stages the pending pivot's row into Params::rbuf.
+//   k_dual_price   the dual ratio test: for every non-basic column j on
+//                  nb_list a_j = rho.A_j and d_j = y.A_j - c_j (rho and y in
+//                  LDS), candidates a_j < -piv_tol, key max(d_j, 0) / -a_j,
+//                  argmin (smallest column on ties) per workgroup.
+//   k_dual_update  every workgroup reduces k_dual_price's partials (no
+//                  candidate: ST_INFEASIBLE), then FTRAN fused with the pending
+//                  rank-1 update exactly as k_update's explicit pass: row i of
+//                  B^-1 is read once, the pending pivot applied, written once
+//                  and dotted with A_p.
+// The B^-1 state keeps the primal loop's convention (spx_device.h): P.B0 = S =
+// B^-1 before the last pivot, whose (st->q, st->aq, alpha[iter & 1]) are
+// pending; x_b and y are always current after k_dual_step (y_applied =
+// xb_applied = iter), so k_flush has nothing to do, k_materialize applies the
+// pending pivot, and a primal pass can follow a dual one and vice versa.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "spx_device.h"
+
+namespace spx {
+
+struct alignas(16) DualPartial {  // a k_dual_price workgroup's candidate
+    double key;
+    int64_t idx;  // entering column, INT64_MAX when none
+    double a;     // rho . A_idx
+    double d;     // y . A_idx - c_idx
+};
+
+struct alignas(16) DualRec {  // the pass in flight
+    int64_t q;      // leaving row (k_dual_step)
+    int64_t p;      // entering column (k_dual_update)
+    double d_p;     // its reduced cost
+    int32_t fresh;  // 1: k_dual_update ran the FTRAN, the pivot awaits k_dual_step
+    int32_t pad;
+};
+
+struct DualArgs {
+    double* rho;         // L: the pivot row
+    DualPartial* parts;  // price_grid
+    DualRec* rec;
+    int32_t price_grid;
+    int32_t pad;
+    double feas_tol;
+    double piv_tol;
+};
+
+struct DualCfg {
+    int price_grid = 0;
+    bool price_lds = false;  // rho and y staged in LDS (2 * 8 * L bytes) or read from global
+    int update_grid = 0;
+    bool update_lds = false;  // the pending row and A_p staged in LDS
+};
+
+constexpr int DUAL_BLOCK = 512;  // threads per workgroup of k_dual_price / k_dual_update
+constexpr int DUAL_WAVES = DUAL_BLOCK / 64;
+
+// geometry: price_grid_opt > 0 fixes the pricing grid, global_y keeps rho and y in global memory
+hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, DualCfg* cfg);
+hipError_t launch_dual_step(const Params& P, const DualArgs& D, bool finish_only, hipStream_t s);
+hipError_t launch_dual_price(const Params& P, const DualArgs& D, const DualCfg& c, hipStream_t s, hipEvent_t e0,
+                             hipEvent_t e1);
+hipError_t launch_dual_update(const Params& P, const DualArgs& D, const DualCfg& c, hipStream_t s, hipEvent_t e0,
+                              hipEvent_t e1);
+
+}  // namespace spx
