@@ -32,7 +32,7 @@ $(BUILD)/spx_loop.o: $(SRC)/spx_loop.hip $(SRC)/spx_loop.h $(SRC)/spx_grid.h $(S
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/spx_dual.o: $(SRC)/spx_dual.hip $(SRC)/spx_dual.h $(SRC)/spx_device.h $(SRC)/spx_common.h
+$(BUILD)/spx_dual.o: $(SRC)/spx_dual.hip $(SRC)/spx_dual_step.inc $(SRC)/spx_dual.h $(SRC)/spx_device.h $(SRC)/spx_common.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -121,13 +121,34 @@ typedef struct spx_opts {
  *         with rho = row q of B^-1, a_j = rho.A_j and d_j = y.A_j - c_j the
  *         entering column is the argmin of max(d_j, 0) / -a_j over non-basic
  *         a_j < -piv_tol (none: SPX_STATUS_INFEASIBLE); first index on ties.
- *         One rank, explicit B^-1 (window 0 resolves to -1), Dantzig pricing;
- *         spx_create rejects nranks > 1, an eta window, the tableau, the
- *         Harris ratio test and Devex / steepest-edge pricing with
- *         SPX_ERR_ARG.  spx_price / spx_pivot and spx_group_iterate return
- *         SPX_ERR_STATE under it.  refactor_every works as in the primal loop. */
+ *         One rank, explicit B^-1 (window 0 resolves to -1), opts.pricing (the
+ *         primal entering rule) Dantzig; spx_create rejects nranks > 1, an eta
+ *         window, the tableau, the Harris ratio test and Devex / steepest-edge
+ *         opts.pricing with SPX_ERR_ARG.  spx_price / spx_pivot and
+ *         spx_group_iterate return SPX_ERR_STATE under it.  refactor_every works
+ *         as in the primal loop.  The leaving-row rule is SPX_DUAL_PRICING_*. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
+
+/* Leaving-row rules of the dual loop (SPX_FLAG_DUAL_STEEPEST at spx_create,
+ * spx_set_dual_pricing later; opts.pricing is the primal entering rule and
+ * stays Dantzig under SPX_ALGO_DUAL).
+ * DANTZIG:  q = argmin x_b[i] over x_b[i] < -feas_tol (above).
+ * STEEPEST: dual steepest edge with exact weights w_i = ||row i of B^-1||^2:
+ *           q = argmin of -x_b[i]^2 / w_i over x_b[i] < -feas_tol (first index
+ *           on ties; none: OPTIMUM_FOUND); the ratio test is unchanged.  The
+ *           pass that pivots on row q with alpha = B^-1 A_p reads every row of
+ *           the explicit B^-1 anyway and takes w_i = row_i.row_i and tau_i =
+ *           row_i.rho (rho = row q) from the same read; with r_i = alpha_i /
+ *           alpha_q and w_q = rho.rho the weights after the pivot are
+ *           w'_i = max(w_i - 2 r_i tau_i + r_i^2 w_q, 1e-300) for i != q and
+ *           w'_q = w_q / alpha_q^2.  w_i is recomputed every pass, so nothing
+ *           drifts and there is no reset rule.  Where no pass has kept them
+ *           (spx_create, spx_reset, spx_set_basis, spx_reinvert, refactor_every,
+ *           spx_set_rhs, spx_set_algorithm, a change of rule) the weights are
+ *           recomputed from B^-1 before the next pass. */
+#define SPX_DUAL_PRICING_DANTZIG  0
+#define SPX_DUAL_PRICING_STEEPEST 1
 
 /* Entering-column rules (README.md:16-17 "steepest edge").
  * DANTZIG: most negative e_j (v4:288-302).
@@ -179,7 +200,10 @@ typedef struct spx_opts {
 #define SPX_FLAG_TIMING 1 /* record per-kernel hipEvents (spx_kernel_times)  */
 #define SPX_FLAG_STAMPS 2 /* in-kernel phase stamps (spx_phase_times); diagnostic */
 #define SPX_FLAG_GLOBAL_Y 4 /* pricing reads y from global memory instead of LDS
-                               (automatic when L*8 bytes do not fit in LDS)   */
+                               (automatic when L*8 bytes do not fit in LDS); the
+                               dual loop's ratio test then reads rho and y, and its
+                               steepest-edge FTRAN + update kernel its three
+                               operands, from global memory                   */
 #define SPX_FLAG_SPLIT_TAIL 16 /* tuning: run the pivot tail as its own launch
                                   instead of the update kernel's last workgroup */
 #define SPX_FLAG_NO_PERSIST 32 /* tuning: never use the persistent loop kernel */
@@ -218,6 +242,11 @@ typedef struct spx_opts {
                                 carries the pivot row.  Readback functions
                                 then gather x_b over the communicator
                                 (collective: every rank must call them).     */
+
+#define SPX_FLAG_DUAL_STEEPEST 2048 /* the dual loop starts with the leaving-row rule
+                                       SPX_DUAL_PRICING_STEEPEST (default DANTZIG);
+                                       accepted and inert while the context runs the
+                                       primal loop                                */
 
 void spx_default_opts(spx_opts* opts);
 
@@ -310,6 +339,18 @@ int spx_set_basis(spx_ctx* ctx, const int64_t* basis);
  * nranks > 1, Harris ratio test, Devex / steepest-edge pricing (the message
  * names the combination). */
 int spx_set_algorithm(spx_ctx* ctx, int32_t algorithm);
+
+/* Leaving-row rule of the dual loop (SPX_DUAL_PRICING_*), between any two
+ * calls; takes effect with the next dual pass.  Valid while the context runs
+ * the primal loop too (e.g. before spx_set_algorithm(SPX_ALGO_DUAL) repairs a
+ * primal solve after spx_set_rhs).  SPX_ERR_ARG for NULL or an unknown rule. */
+int spx_set_dual_pricing(spx_ctx* ctx, int32_t rule);
+
+/* Dual steepest-edge weights w[0..m) of the current basis (squared row norms
+ * of B^-1, basis order), recomputed first where no pass has kept them.
+ * SPX_ERR_STATE when the rule is SPX_DUAL_PRICING_DANTZIG or the context runs
+ * the primal loop. */
+int spx_get_dual_weights(spx_ctx* ctx, double* w /* m */);
 
 /* New right-hand side b[0..m), any signs: uploaded, then x_b = B^-1 b for the
  * current basis (through spx_reinvert), status back to running, pivot count

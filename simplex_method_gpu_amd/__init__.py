@@ -25,7 +25,8 @@ from ._lib import SimplexError, SpxOpts, check, load
 __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_unique_id",
            "shard_range", "minloc_merge", "group_iterate", "group_sync", "check_ranks",
            "SimplexError", "FLAG_TIMING", "RATIO_REFERENCE", "RATIO_GUARDED", "RATIO_HARRIS",
-           "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL"]
+           "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL",
+           "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -39,6 +40,7 @@ MBOX_HANDLE_BYTES = 64  # SPX_MBOX_HANDLE_BYTES
 FLAG_TABLEAU = 256  # window tableau: T_w = B_w A and dw kept beside the eta window
 FLAG_COUNTED_TAIL = 512  # ratio-test hand-off by drained stores + last-arrival count (default: tagged poll)
 FLAG_PRICE_TAIL = 1024  # k_price's last workgroup merges the entering candidates (default: deferred into k_update)
+FLAG_DUAL_STEEPEST = 2048  # the dual loop starts with dual steepest-edge pricing (default: Dantzig)
 
 # leaving-row rules (include/simplex.h SPX_RATIO_*)
 RATIO_REFERENCE, RATIO_GUARDED, RATIO_HARRIS = 0, 1, 2
@@ -47,6 +49,8 @@ PRICING_DANTZIG, PRICING_DEVEX, PRICING_STEEPEST = 0, 1, 2
 # simplex algorithm of iterate / solve (include/simplex.h SPX_ALGO_*): the dual
 # loop starts from a dual feasible basis whose x_b may be negative (b of any sign)
 ALGO_PRIMAL, ALGO_DUAL = 0, 1
+# leaving-row rules of the dual loop (include/simplex.h SPX_DUAL_PRICING_*)
+DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST = 0, 1
 
 
 class SolveStatus(IntEnum):
@@ -159,7 +163,8 @@ class Context:
                  ratio_test: int = 0, piv_tol: float = 1e-9, feas_tol: float = 1e-9, refactor_every: int = 0,
                  pricing: int = 0, persist: bool | None = None, loop_block: int = 0, comm1: bool = False,
                  tableau: bool = False, trace: int = 0, counted_tail: bool = False,
-                 price_tail: bool = False, algorithm: int = ALGO_PRIMAL):
+                 price_tail: bool = False, algorithm: int = ALGO_PRIMAL,
+                 dual_pricing: int = DUAL_PRICING_DANTZIG):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -173,12 +178,16 @@ class Context:
         o.loop_block = loop_block
         o.trace_cap = trace  # record the first `trace` pivots' (p, q) on the device
         o.algorithm = algorithm  # ALGO_PRIMAL / ALGO_DUAL
+        if dual_pricing not in (DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST):
+            raise ValueError("dual_pricing must be DUAL_PRICING_DANTZIG or DUAL_PRICING_STEEPEST")
+        self._dual_pricing = dual_pricing
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
                    | ({None: 0, True: FLAG_PERSIST, False: FLAG_NO_PERSIST}[persist])
                    | (FLAG_COMM1 if comm1 else 0) | (FLAG_TABLEAU if tableau else 0)
-                   | (FLAG_COUNTED_TAIL if counted_tail else 0) | (FLAG_PRICE_TAIL if price_tail else 0))
+                   | (FLAG_COUNTED_TAIL if counted_tail else 0) | (FLAG_PRICE_TAIL if price_tail else 0)
+                   | (FLAG_DUAL_STEEPEST if dual_pricing == DUAL_PRICING_STEEPEST else 0))
         h = ctypes.c_void_p()
         if A_cols is not None:
             A_cols = np.ascontiguousarray(A_cols, dtype=np.float64)
@@ -271,6 +280,19 @@ class Context:
         basis, B^-1, x_b, y and the pivot count are kept, the status goes back
         to running."""
         check(self._L.spx_set_algorithm(self._h, algo))
+
+    def set_dual_pricing(self, rule: int):
+        """Leaving-row rule of the dual loop from the next dual pass on
+        (spx_set_dual_pricing): DUAL_PRICING_DANTZIG / DUAL_PRICING_STEEPEST."""
+        check(self._L.spx_set_dual_pricing(self._h, rule))
+        self._dual_pricing = rule
+
+    def dual_weights(self):
+        """Dual steepest-edge weights of the current basis, the squared row
+        norms of B^-1 in basis order (spx_get_dual_weights)."""
+        w = np.empty(self.m, dtype=np.float64)
+        check(self._L.spx_get_dual_weights(self._h, _ptr(w)))
+        return w
 
     def set_rhs(self, b):
         """New right-hand side of any sign (spx_set_rhs): x_b = B^-1 b for the
@@ -446,7 +468,9 @@ class Context:
         keys = ("window", "price_block", "price_grid", "price_lds", "update_block", "update_rows", "update_grid",
                 "graph_batch", "persistent", "loop_block", "tableau", "loop_grid", "defer_tail", "compact_fold",
                 "ftran_rows_per_wave", "mbox_fused")
-        return dict(zip(keys, list(out)))
+        cfg = dict(zip(keys, list(out)))
+        cfg["dual_pricing"] = self._dual_pricing  # (the library keeps it outside spx_config)
+        return cfg
 
 
 def solve(A_cols, b, c, max_iter: int = (1 << 62), eps: float = 1e-7, device: int = -1,

@@ -28,6 +28,8 @@
 //                  the slack basis, which must be dual feasible (every c_j <= 0;
 //                  b of any sign); "Problem infeasible." when no x >= 0 exists;
 //                  a slack basis that is not dual feasible is an error (exit 1)
+//   --dual-pricing R  leaving-row rule of --dual: dantzig (most negative x_b, default)
+//                  | steepest (dual steepest edge, SPX_DUAL_PRICING_STEEPEST)
 //   --tableau      window tableau (SPX_FLAG_TABLEAU): T_w = B_w A
 //                  kept in HBM, no per-pivot A / B^-1 stream
 //   --mps          the input is an MPS file (mps_io.h): converted to the
@@ -73,6 +75,7 @@ static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
                  " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual]"
+                 " [--dual-pricing dantzig|steepest]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -91,7 +94,7 @@ int main(int argc, char* argv[]) {
     int ratio = -1, window = 0, pricing = SPX_PRICING_DANTZIG;
     double piv_tol = 1e-9, feas_tol = 1e-9, big_m = 0.0;
     int64_t refactor = 0;
-    bool mps_in = false, tableau = false, dual = false;
+    bool mps_in = false, tableau = false, dual = false, dual_steepest = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -126,6 +129,12 @@ int main(int argc, char* argv[]) {
         else if (s == "--mps") mps_in = true;
         else if (s == "--tableau") tableau = true;
         else if (s == "--dual") dual = true;
+        else if (s == "--dual-pricing") {
+            need(1);
+            const std::string r = argv[++a];
+            if (r != "dantzig" && r != "steepest") { usage(); return 1; }
+            dual_steepest = r == "steepest";
+        }
         else if (s == "--pricing") {
             need(1);
             const std::string r = argv[++a];
@@ -200,6 +209,7 @@ int main(int argc, char* argv[]) {
     o.pricing = pricing;
     if (tableau) o.flags |= SPX_FLAG_TABLEAU;
     if (dual) o.algorithm = SPX_ALGO_DUAL;
+    if (dual_steepest) o.flags |= SPX_FLAG_DUAL_STEEPEST;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)

@@ -178,10 +178,12 @@ struct spx_ctx {
 
     // dual simplex loop (spx_dual.h): buffers allocated when the context first runs it
     int32_t algo = SPX_ALGO_PRIMAL;
-    DualArgs dual{};
+    DualSeArgs dual{};
     DualCfg dcfg{};
     bool dual_checked = false;  // dual feasibility of the basis verified since it was last set
     double* dual_e = nullptr;   // n reduced costs (the check)
+    int32_t dual_rule = SPX_DUAL_PRICING_DANTZIG;  // leaving-row rule (spx_set_dual_pricing)
+    bool dual_w_stale = true;   // steepest edge: dual.w is not the current basis's (k_dual_norms before the next pass)
 
     template <typename T>
     int alloc(T** p, size_t count, unsigned ext_flags = ~0u) {
@@ -325,6 +327,7 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
             return fail(SPX_ERR_ARG, "piv_tol and feas_tol must be >= 0");
     }
     x->algo = x->opts.algorithm;
+    x->dual_rule = (x->opts.flags & SPX_FLAG_DUAL_STEEPEST) ? SPX_DUAL_PRICING_STEEPEST : SPX_DUAL_PRICING_DANTZIG;
     P.ratio = rule;
     P.piv_tol = rule == SPX_RATIO_REFERENCE ? 0.0 : x->opts.piv_tol;
     P.feas_tol = rule == SPX_RATIO_HARRIS ? x->opts.feas_tol : 0.0;
@@ -678,6 +681,7 @@ int do_reset(spx_ctx* x) {
     SPX_TRY(tab_rebuild(x, true));
     if (x->dual.rec) HIP_TRY(hipMemsetAsync(x->dual.rec, 0, sizeof(DualRec), x->stream));
     x->dual_checked = false;
+    x->dual_w_stale = true;
     HIP_TRY(hipStreamSynchronize(x->stream));
     x->pivots = 0;
     x->status = SPX_STATUS_MAX_ITER;
@@ -1002,7 +1006,13 @@ int iterate_persist(spx_ctx* x, int64_t k) {
 int dual_setup(spx_ctx* x) {
     if (x->dual.rho) return SPX_OK;
     if (!kernels_inplace()) return fail(SPX_ERR_STATE, "the dual simplex loop needs the in-place B^-1 build");
-    HIP_TRY(dual_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0, &x->dcfg));
+    // steepest edge, k_dual_update's third operand rho: staged in LDS, or (SPX_DUAL_RHO_LDS=0) read from global memory
+    HIP_TRY(dual_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
+                         !env_off("SPX_DUAL_RHO_LDS"), &x->dcfg));
+    SPX_TRY(x->alloc(&x->dual.tau, (size_t)x->L));
+    SPX_TRY(x->alloc(&x->dual.wex, (size_t)x->L));
+    SPX_TRY(x->alloc(&x->dual.w, (size_t)x->L));
+    x->dual_w_stale = true;
     SPX_TRY(x->alloc(&x->dual.rho, (size_t)x->L));
     SPX_TRY(x->alloc(&x->dual.parts, (size_t)x->dcfg.price_grid));
     SPX_TRY(x->alloc(&x->dual.rec, 1));
@@ -1036,12 +1046,22 @@ int dual_check_feasible(spx_ctx* x) {
     return SPX_OK;
 }
 
+// Steepest edge: the weights of the current basis from scratch where no pass
+// has kept them (k_dual_norms; between passes, nothing of the dual loop's in flight)
+int dual_refresh_weights(spx_ctx* x) {
+    if (!x->dual_w_stale) return SPX_OK;
+    HIP_TRY(launch_dual_norms(x->P, x->dual, x->dcfg, x->stream));
+    x->dual_w_stale = false;
+    return SPX_OK;
+}
+
 // One dual pass: leaving row + pivot row, ratio test, FTRAN + update.
 int enqueue_dual_pass(spx_ctx* x, hipEvent_t p0, hipEvent_t p1, hipEvent_t u0, hipEvent_t u1) {
-    HIP_TRY(launch_dual_step(x->P, x->dual, false, x->stream));
+    const bool se = x->dual_rule == SPX_DUAL_PRICING_STEEPEST;
+    HIP_TRY(launch_dual_step(x->P, x->dual, se, false, x->stream));
     HIP_TRY(launch_dual_price(x->P, x->dual, x->dcfg, x->stream, p0, p1));
     if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
-    HIP_TRY(launch_dual_update(x->P, x->dual, x->dcfg, x->stream, u0, u1));
+    HIP_TRY(launch_dual_update(x->P, x->dual, x->dcfg, se, x->stream, u0, u1));
     return SPX_OK;
 }
 
@@ -1053,6 +1073,9 @@ int enqueue_dual_pass(spx_ctx* x, hipEvent_t p0, hipEvent_t p1, hipEvent_t u0, h
 int iterate_dual(spx_ctx* x, int64_t k) {
     SPX_TRY(dual_setup(x));
     if (!x->dual_checked) SPX_TRY(dual_check_feasible(x));
+    const bool se = x->dual_rule == SPX_DUAL_PRICING_STEEPEST;
+    if (se) SPX_TRY(dual_refresh_weights(x));
+    else x->dual_w_stale = true;  // Dantzig passes keep no weights
     SPX_TRY(set_limit(x, x->pivots + k));
     for (int64_t i = 0; i < k; ++i) {
         hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
@@ -1075,7 +1098,7 @@ int iterate_dual(spx_ctx* x, int64_t k) {
         SPX_TRY(enqueue_dual_pass(x, p0, p1, u0, u1));
         ++x->n_eager;
     }
-    HIP_TRY(launch_dual_step(x->P, x->dual, true, x->stream));
+    HIP_TRY(launch_dual_step(x->P, x->dual, se, true, x->stream));  // (steepest edge: the last pivot's weights too)
     return read_state(x);
 }
 
@@ -1203,6 +1226,7 @@ int reinvert_basis(spx_ctx* x, const int64_t* basis) {
     }
     SPX_TRY(tab_rebuild(x, false));
     x->nw = 0;
+    x->dual_w_stale = true;
     return read_state(x);
 }
 
@@ -1603,7 +1627,31 @@ int spx_set_algorithm(spx_ctx* x, int32_t algo) {
     x->algo = algo;
     x->opts.algorithm = algo;
     x->dual_checked = false;
+    x->dual_w_stale = true;  // (primal passes keep no dual weights)
     return set_running(x);
+}
+
+int spx_set_dual_pricing(spx_ctx* x, int32_t rule) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (rule != SPX_DUAL_PRICING_DANTZIG && rule != SPX_DUAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_ARG, "bad dual pricing rule %d", rule);
+    if (rule != x->dual_rule) x->dual_w_stale = true;
+    x->dual_rule = rule;
+    return SPX_OK;
+}
+
+int spx_get_dual_weights(spx_ctx* x, double* w) {
+    if (!x || !w) return fail(SPX_ERR_ARG, "NULL argument");
+    if (x->dual_rule != SPX_DUAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "no dual pricing weights: the dual leaving-row rule is Dantzig");
+    if (x->algo != SPX_ALGO_DUAL)
+        return fail(SPX_ERR_STATE, "no dual pricing weights: the context runs the primal loop");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    SPX_TRY(dual_setup(x));
+    SPX_TRY(dual_refresh_weights(x));
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(w, x->dual.w, sizeof(double) * (size_t)x->m, hipMemcpyDeviceToHost));
+    return SPX_OK;
 }
 
 int spx_set_rhs(spx_ctx* x, const double* b) {

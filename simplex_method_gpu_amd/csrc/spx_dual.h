@@ -23,6 +23,13 @@
 // pending; x_b and y are always current after k_dual_step (y_applied =
 // xb_applied = iter), so k_flush has nothing to do, k_materialize applies the
 // pending pivot, and a primal pass can follow a dual one and vice versa.
+//
+// Dual steepest-edge pricing (SPX_DUAL_PRICING_STEEPEST) runs the same three
+// launches in their steepest-edge instantiations: k_dual_update<., SE> also
+// dots every updated row with rho (tau) and with itself (wex, the exact weight
+// before the pivot), k_dual_step_se's commit turns them into the weights after
+// the pivot (DualSeArgs::w) and its selection takes argmin -x_b^2 / w.
+// k_dual_norms recomputes w from B^-1 where no pass has kept it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,22 +62,37 @@ struct DualArgs {
     double piv_tol;
 };
 
+// the steepest-edge instantiations' arguments (the Dantzig ones take DualArgs
+// alone: their kernel arguments are what they were before the rule existed)
+struct DualSeArgs : DualArgs {
+    double* tau;  // L: row_i . rho of the pass in flight (k_dual_update<., SE>)
+    double* wex;  // L: row_i . row_i of the pass in flight, B^-1 before its pivot
+    double* w;    // L: the weights of the current basis (k_dual_step_se, k_dual_norms)
+};
+
 struct DualCfg {
     int price_grid = 0;
     bool price_lds = false;  // rho and y staged in LDS (2 * 8 * L bytes) or read from global
     int update_grid = 0;
     bool update_lds = false;  // the pending row and A_p staged in LDS
+    bool se_update_lds = false;  // k_dual_update<., SE>: its operands staged in LDS (24 L bytes must fit)
+    bool se_rho_lds = false;     // ... rho among them (24 L bytes of LDS), or read from global memory (16 L)
 };
 
 constexpr int DUAL_BLOCK = 512;  // threads per workgroup of k_dual_price / k_dual_update
 constexpr int DUAL_WAVES = DUAL_BLOCK / 64;
+constexpr double DUAL_W_FLOOR = 1e-300;  // steepest-edge weights stay positive: the key -x_b^2 / w stays finite
 
-// geometry: price_grid_opt > 0 fixes the pricing grid, global_y keeps rho and y in global memory
-hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, DualCfg* cfg);
-hipError_t launch_dual_step(const Params& P, const DualArgs& D, bool finish_only, hipStream_t s);
+// geometry: price_grid_opt > 0 fixes the pricing grid, global_y keeps rho and y
+// (and the steepest-edge update's operands) in global memory
+hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, bool se_rho_lds, DualCfg* cfg);
+// se: the steepest-edge instantiations (leaving row by -x_b^2 / w, weights kept in D.w)
+hipError_t launch_dual_step(const Params& P, const DualSeArgs& D, bool se, bool finish_only, hipStream_t s);
 hipError_t launch_dual_price(const Params& P, const DualArgs& D, const DualCfg& c, hipStream_t s, hipEvent_t e0,
                              hipEvent_t e1);
-hipError_t launch_dual_update(const Params& P, const DualArgs& D, const DualCfg& c, hipStream_t s, hipEvent_t e0,
-                              hipEvent_t e1);
+hipError_t launch_dual_update(const Params& P, const DualSeArgs& D, const DualCfg& c, bool se, hipStream_t s,
+                              hipEvent_t e0, hipEvent_t e1);
+// D.w = squared row norms of the true B^-1 (pending pivot applied in registers)
+hipError_t launch_dual_norms(const Params& P, const DualSeArgs& D, const DualCfg& c, hipStream_t s);
 
 }  // namespace spx

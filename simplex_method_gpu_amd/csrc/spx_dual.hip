@@ -3,6 +3,8 @@
 
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "spx_common.h"
 
 namespace spx {
@@ -53,166 +55,37 @@ struct StepState {  // k_dual_step: the loop state, read once by thread 0
     double d_p;
 };
 
+template <bool SE>
+using DualArgsOf = std::conditional_t<SE, DualSeArgs, DualArgs>;
+
+// what only k_dual_update's steepest-edge instantiations carry (nothing in the Dantzig ones)
+template <int SE>
+struct SeDots {  // k_dual_update: rho's operand and the two extra dots' accumulators
+    const dbl2* xh;
+    double t0 = 0.0, t1 = 0.0, w0 = 0.0, w1 = 0.0;
+};
+template <>
+struct SeDots<0> {};
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
 // Finish of the previous pass's pivot, leaving row, pivot row (one workgroup)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_dual_step(Params P, DualArgs D, int finish_only) {
-    constexpr int BLOCK = 1024, WAVES = BLOCK / 64;
-    DevState* st = P.st;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t m = P.m, L = P.L;
-    __shared__ StepState S;
-    __shared__ ArgMinEntry s_red[WAVES];
-    // The kernel is a chain of dependent memory round trips on one CU, so each
-    // phase requests everything it needs before its first store: the state and
-    // the pass record in one snapshot, the vectors in chunks of CH per thread
-    // (loads of a chunk ahead of its stores), the bookkeeping's four loads
-    // together on a wave of their own beside the vector updates.
-    constexpr int CH = 4;
-    if (tid == 0) {
-        S.it = st->iter;
-        S.limit = st->limit;
-        S.qprev = st->q;
-        S.aqprev = st->aq;
-        S.status = st->status;
-        S.y_buf = st->y_buf;
-        S.cnt = st->nb_count;
-        S.fresh = D.rec->fresh;
-        S.q = D.rec->q;
-        S.p = D.rec->p;
-        S.d_p = D.rec->d_p;
-    }
-    __syncthreads();
-    double* y = S.y_buf ? P.y1 : P.y0;
-    int64_t it = S.it, qprev = S.qprev;
-    double aqprev = S.aqprev;
-    if (S.fresh) {
-        // pivot it: alpha = B^-1 A_p is in alpha[(it + 1) & 1] (k_dual_update)
-        const int64_t q = S.q, p = S.p;
-        const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
-        const double aq = al[q], xq = P.x_b[q];  // (every thread: the same two words)
-        const bool book = tid == BLOCK - 64;      // the last wave's lane 0
-        int64_t leave = -1;
-        double c_p = 0.0;
-        int kp = -1, last = -1;
-        if (book) {
-            leave = P.b_ixs[q];
-            c_p = P.c[p];
-            kp = P.nb_pos[p];
-            last = P.nb_list[S.cnt - 1];
-        }
-        const double theta = xq / aq, sy = -(S.d_p / aq);
-        __syncthreads();  // x_b[q] is read by every thread before its owner overwrites it
-        for (int64_t i0 = tid; i0 < L; i0 += (int64_t)CH * BLOCK) {
-            double xv[CH], av[CH], yv[CH], rv[CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int64_t i = i0 + (int64_t)u * BLOCK;
-                xv[u] = i < m ? P.x_b[i] : 0.0;
-                av[u] = i < m ? al[i] : 0.0;
-                yv[u] = i < L ? y[i] : 0.0;
-                rv[u] = i < L ? D.rho[i] : 0.0;  // (rho's padding is 0: so is y's)
-            }
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int64_t i = i0 + (int64_t)u * BLOCK;
-                if (i < m) P.x_b[i] = (i == q) ? theta : fma(-theta, av[u], xv[u]);
-                if (i < L) y[i] = fma(sy, rv[u], yv[u]);
-            }
-        }
-        if (book) {
-            P.c_B[q] = c_p;
-            P.b_ixs[q] = p;
-            // nb_list / nb_pos as pivot_bookkeeping keeps them: swap-remove p, append the leaving column
-            int cnt = S.cnt;
-            P.nb_list[kp] = last;
-            P.nb_pos[last] = kp;
-            P.nb_pos[p] = -1;
-            --cnt;
-            P.nb_list[cnt] = (int32_t)leave;
-            P.nb_pos[leave] = cnt;
-            ++cnt;
-            st->nb_count = cnt;
-            st->aq = aq;
-            st->s_y = sy;
-            st->y_applied = it + 1;  // y and x_b are current: only B^-1 stays pending
-            st->xb_applied = it + 1;
-            st->p = p;
-            st->q = q;
-            st->min_e = S.d_p;
-            st->iter = it + 1;
-            record_pivot(P, it, p, q);
-            D.rec->fresh = 0;
-        }
-        it += 1;
-        qprev = q;
-        aqprev = aq;
-        __syncthreads();  // x_b as this workgroup's threads left it
-    }
-    if (finish_only || S.status != ST_RUNNING || it >= S.limit) return;
-
-    // leaving row: the most negative x_b below -feas_tol, first index on ties
-    double bv = INFINITY;
-    int64_t bi = INT64_MAX;
-    for (int64_t i = tid; i < m; i += BLOCK) {
-        const double v = P.x_b[i];
-        if (v < -D.feas_tol && argmin_better(v, i, bv, bi)) {
-            bv = v;
-            bi = i;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double v2 = __shfl_xor(bv, off, 64);
-        const int64_t j2 = __shfl_xor(bi, off, 64);
-        if (argmin_better(v2, j2, bv, bi)) {
-            bv = v2;
-            bi = j2;
-        }
-    }
-    if (lane == 0) s_red[wave] = ArgMinEntry{bv, bi};
-    __syncthreads();
-    if (tid == 0) {
-        ArgMinEntry t = s_red[0];
-        for (int w = 1; w < WAVES; ++w)
-            if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
-        S.q = t.idx;
-        if (t.idx == INT64_MAX) st->status = ST_OPTIMAL;  // primal feasible: optimum
-        else D.rec->q = t.idx;
-    }
-    __syncthreads();
-    const int64_t q = S.q;
-    if (q == INT64_MAX) return;
-
-    // rho = row q of the true B^-1 = S[q] + E_q r', r' = S[q'] the pending pivot's
-    // row (staged into rbuf: k_dual_update overwrites row q' while other waves
-    // still read it)
-    const bool pend = it > 0 && qprev >= 0;
-    const double* Sq = P.B0 + q * L;
-    const double* Sp = P.B0 + (pend ? qprev : q) * L;
-    const double* a_prev = (it & 1) ? P.alpha1 : P.alpha0;
-    const double aq_prev = pend ? a_prev[q] : 0.0;
-    for (int64_t k0 = tid; k0 < L; k0 += (int64_t)CH * BLOCK) {
-        double sp[CH], sq[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int64_t k = k0 + (int64_t)u * BLOCK;
-            sq[u] = k < L ? Sq[k] : 0.0;
-            sp[u] = (pend && k < L) ? Sp[k] : 0.0;
-        }
-        const double eq = pend ? eta_entry(aq_prev, q, qprev, aqprev) : 0.0;
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int64_t k = k0 + (int64_t)u * BLOCK;
-            if (k < L) {
-                if (pend) P.rbuf[k] = sp[u];
-                D.rho[k] = pend ? fma(eq, sp[u], sq[u]) : sq[u];
-            }
-        }
-    }
-}
+#define SPX_STEP_KERNEL k_dual_step
+#define SPX_STEP_ARGS DualArgs
+#define SPX_STEP_SE 0
+#include "spx_dual_step.inc"
+#undef SPX_STEP_KERNEL
+#undef SPX_STEP_ARGS
+#undef SPX_STEP_SE
+#define SPX_STEP_KERNEL k_dual_step_se
+#define SPX_STEP_ARGS DualSeArgs
+#define SPX_STEP_SE 1
+#include "spx_dual_step.inc"
+#undef SPX_STEP_KERNEL
+#undef SPX_STEP_ARGS
+#undef SPX_STEP_SE
 
 // ---------------------------------------------------------------------------
 // Dual ratio test (the hot kernel): two dots per streamed non-basic column
@@ -315,8 +188,12 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, DualArgs D)
 // A_p: alpha_i into alpha[(it + 1) & 1].  After the launch S is B^-1 before
 // pivot it, and (q, alpha_q, alpha) is the new pending pivot once k_dual_step
 // commits it.
-template <bool XL>
-__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgs D) {
+// SE (dual steepest edge): the updated row is also dotted with the pivot row
+// rho (tau_i) and with itself (the exact weight wex_i), in acc0 / acc1's fixed
+// order, so neither depends on the grid.  SE 1 stages rho in LDS beside the
+// pending row and A_p (24 L bytes), SE 2 reads it from global memory (L2 hits).
+template <bool XL, int SE>
+__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgsOf<SE != 0> D) {
     constexpr int WAVES = DUAL_WAVES, U = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
     __shared__ DualPartial s_red[WAVES];
@@ -369,11 +246,15 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgs D
         for (int64_t k = tid; k < L2; k += DUAL_BLOCK) {
             d[k] = rp[k];
             d[L2 + k] = ap[k];
+            if constexpr (SE == 1) d[2 * L2 + k] = reinterpret_cast<const dbl2*>(D.rho)[k];
         }
         __syncthreads();
     }
     const dbl2* xr = XL ? reinterpret_cast<const dbl2*>(dsm) : rp;
     const dbl2* xa = XL ? reinterpret_cast<const dbl2*>(dsm) + L2 : ap;
+    [[maybe_unused]] SeDots<SE> se;
+    if constexpr (SE != 0)
+        se.xh = (XL && SE == 1) ? reinterpret_cast<const dbl2*>(dsm) + 2 * L2 : reinterpret_cast<const dbl2*>(D.rho);
 
     const int64_t i = (int64_t)blockIdx.x * WAVES + wave;
     if (i >= m) return;  // (no barrier below)
@@ -400,6 +281,13 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgs D
                 st2<SPX_NT_BSTORE>(nv, row + 64 * (c0 + u));
                 acc0 = fma(nv.x, a.x, acc0);
                 acc1 = fma(nv.y, a.y, acc1);
+                if constexpr (SE != 0) {
+                    const dbl2 h = se.xh[k];
+                    se.t0 = fma(nv.x, h.x, se.t0);
+                    se.t1 = fma(nv.y, h.y, se.t1);
+                    se.w0 = fma(nv.x, nv.x, se.w0);
+                    se.w1 = fma(nv.y, nv.y, se.w1);
+                }
             }
         }
 #pragma unroll
@@ -407,6 +295,47 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgs D
     }
     const double alpha = wave_sum(acc0 + acc1);
     if (lane == 0) a_new[i] = alpha;
+    if constexpr (SE != 0) {
+        double t = se.t0 + se.t1, w = se.w0 + se.w1;
+        wave_sum2(t, w);
+        if (lane == 0) {
+            D.tau[i] = t;
+            D.wex[i] = w;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Dual steepest-edge weights of the current basis, from scratch
+// ---------------------------------------------------------------------------
+// One row per wave: w_i = ||S[i] + E_i r'||^2, the pending pivot (r' = S[q'],
+// read in place: nothing is written to B^-1) applied in registers, summed in
+// k_dual_update's order.  Runs between passes only (DualRec::fresh == 0).
+__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_norms(Params P, DualSeArgs D) {
+    constexpr int WAVES = DUAL_WAVES;
+    const DevState* st = P.st;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t it = st->iter, qp = st->q;
+    const double aqp = st->aq;
+    const int64_t m = P.m, L = P.L;
+    const int nch = (int)(L >> 7);
+    const int64_t i = (int64_t)blockIdx.x * WAVES + wave;
+    if (i >= m) return;
+    const bool pend = it > 0 && qp >= 0 && qp < m;
+    const double* a_prev = (it & 1) ? P.alpha1 : P.alpha0;
+    const double ei = pend ? eta_entry(a_prev[i], i, qp, aqp) : 0.0;
+    const dbl2* row = reinterpret_cast<const dbl2*>(P.B0 + i * L) + lane;
+    const dbl2* rp = reinterpret_cast<const dbl2*>(pend ? P.B0 + qp * L : P.zeros) + lane;
+    double w0 = 0.0, w1 = 0.0;
+    for (int c = 0; c < nch; ++c) {
+        const dbl2 s = row[64 * c], r = rp[64 * c];
+        const double vx = fma(ei, r.x, s.x), vy = fma(ei, r.y, s.y);
+        w0 = fma(vx, vx, w0);
+        w1 = fma(vy, vy, w1);
+    }
+    const double w = wave_sum(w0 + w1);
+    if (lane == 0) D.w[i] = fmax(w, DUAL_W_FLOOR);
 }
 
 // ---------------------------------------------------------------------------
@@ -423,9 +352,9 @@ hipError_t set_lds(K kernel, size_t lds) {
                                (int)lds);
 }
 
-template <typename K>
+template <typename K, typename DA>
 hipError_t launch_timed(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const Params& P,
-                        const DualArgs& D) {
+                        const DA& D) {
     if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(DUAL_BLOCK), (uint32_t)lds, s, e0, e1, 0, P, D);
     else hipLaunchKernelGGL(kernel, dim3(grid), dim3(DUAL_BLOCK), lds, s, P, D);
     return hipGetLastError();
@@ -433,10 +362,13 @@ hipError_t launch_timed(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_
 
 }  // namespace
 
-hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, DualCfg* cfg) {
+hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, bool se_rho_lds, DualCfg* cfg) {
     const size_t vec2 = (size_t)P.L * 16;  // two staged vectors
+    const size_t vec3 = (size_t)P.L * 24;  // with rho
     cfg->price_lds = !global_y && vec2 <= DUAL_LDS_CAP;
     cfg->update_lds = vec2 <= DUAL_LDS_CAP;
+    cfg->se_update_lds = !global_y && vec3 <= DUAL_LDS_CAP;
+    cfg->se_rho_lds = se_rho_lds;
     hipError_t e = hipSuccess;
     int per_cu = 0;
     if (cfg->price_lds) {
@@ -448,7 +380,11 @@ hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool globa
     }
     if (e != hipSuccess) return e;
     if (cfg->update_lds) {
-        e = set_lds(k_dual_update<true>, vec2);
+        e = set_lds(k_dual_update<true, 0>, vec2);
+        if (e != hipSuccess) return e;
+    }
+    if (cfg->se_update_lds) {
+        e = se_rho_lds ? set_lds(k_dual_update<true, 1>, vec3) : set_lds(k_dual_update<true, 2>, vec2);
         if (e != hipSuccess) return e;
     }
     if (per_cu < 1) per_cu = 1;
@@ -462,8 +398,10 @@ hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool globa
     return hipSuccess;
 }
 
-hipError_t launch_dual_step(const Params& P, const DualArgs& D, bool finish_only, hipStream_t s) {
-    hipLaunchKernelGGL(k_dual_step, dim3(1), dim3(1024), 0, s, P, D, finish_only ? 1 : 0);
+hipError_t launch_dual_step(const Params& P, const DualSeArgs& D, bool se, bool finish_only, hipStream_t s) {
+    const DualArgs& D0 = D;
+    if (se) hipLaunchKernelGGL(k_dual_step_se, dim3(1), dim3(1024), 0, s, P, D, finish_only ? 1 : 0);
+    else hipLaunchKernelGGL(k_dual_step, dim3(1), dim3(1024), 0, s, P, D0, finish_only ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -473,10 +411,21 @@ hipError_t launch_dual_price(const Params& P, const DualArgs& D, const DualCfg& 
     return launch_timed(k_dual_price<false>, c.price_grid, 0, s, e0, e1, P, D);
 }
 
-hipError_t launch_dual_update(const Params& P, const DualArgs& D, const DualCfg& c, hipStream_t s, hipEvent_t e0,
-                              hipEvent_t e1) {
-    if (c.update_lds) return launch_timed(k_dual_update<true>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D);
-    return launch_timed(k_dual_update<false>, c.update_grid, 0, s, e0, e1, P, D);
+hipError_t launch_dual_update(const Params& P, const DualSeArgs& D, const DualCfg& c, bool se, hipStream_t s,
+                              hipEvent_t e0, hipEvent_t e1) {
+    if (se) {
+        if (!c.se_update_lds) return launch_timed(k_dual_update<false, 2>, c.update_grid, 0, s, e0, e1, P, D);
+        if (c.se_rho_lds) return launch_timed(k_dual_update<true, 1>, c.update_grid, (size_t)P.L * 24, s, e0, e1, P, D);
+        return launch_timed(k_dual_update<true, 2>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D);
+    }
+    const DualArgs& D0 = D;
+    if (c.update_lds) return launch_timed(k_dual_update<true, 0>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D0);
+    return launch_timed(k_dual_update<false, 0>, c.update_grid, 0, s, e0, e1, P, D0);
+}
+
+hipError_t launch_dual_norms(const Params& P, const DualSeArgs& D, const DualCfg& c, hipStream_t s) {
+    hipLaunchKernelGGL(k_dual_norms, dim3(c.update_grid), dim3(DUAL_BLOCK), 0, s, P, D);
+    return hipGetLastError();
 }
 
 }  // namespace spx
