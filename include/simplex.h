@@ -126,7 +126,24 @@ typedef struct spx_opts {
  *         window, the tableau, the Harris ratio test and Devex / steepest-edge
  *         opts.pricing with SPX_ERR_ARG.  spx_price / spx_pivot and
  *         spx_group_iterate return SPX_ERR_STATE under it.  refactor_every works
- *         as in the primal loop.  The leaving-row rule is SPX_DUAL_PRICING_*. */
+ *         as in the primal loop.  The leaving-row rule is SPX_DUAL_PRICING_*.
+ *         Boxed variables 0 <= x_j <= u_j (spx_set_bounds; all n columns, a
+ *         bounded slack is a ranged row) exist under DUAL only.  A non-basic
+ *         column sits at 0 (sigma_j = +1) or at u_j (sigma_j = -1) and is dual
+ *         feasible with e_j >= -eps at lower, e_j <= eps at upper; before the
+ *         first pass every non-basic column is put on its feasible side (e_j <
+ *         -eps with no upper bound: SPX_ERR_STATE "basis is not dual feasible",
+ *         naming the column).  x_b = B^-1 (b - sum_{j at upper} u_j A_j) and z =
+ *         c_B.x_b + sum_{j at upper} c_j u_j.  Row i (basic column k) violates
+ *         by delta_i = x_b[i] below -feas_tol, x_b[i] - u_k above u_k +
+ *         feas_tol; Dantzig takes argmin -|delta_i|, steepest edge argmin
+ *         -delta_i^2 / w_i; s = +1 when the row leaves to its lower bound, -1 to
+ *         its upper.  Ratio test over non-basic s sigma_j a_j < -piv_tol with key
+ *         max(sigma_j d_j, 0) / -(s sigma_j a_j); theta = delta_q / alpha_q and
+ *         the entering column starts from the bound it sat at.  Without a
+ *         finite bound the loop and its kernels are the unbounded ones.  Finite
+ *         bounds with SPX_ALGO_PRIMAL are SPX_ERR_STATE; no bound-flipping ratio
+ *         test, no non-zero or free lower bounds. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
 
@@ -358,6 +375,22 @@ int spx_get_dual_weights(spx_ctx* ctx, double* w /* m */);
  * spx_set_algorithm(SPX_ALGO_DUAL) + spx_solve re-optimises from it.  One rank,
  * replicated B^-1 (SPX_ERR_STATE otherwise). */
 int spx_set_rhs(spx_ctx* ctx, const double* b);
+
+/* Upper bounds ub[0..n) of all columns, slacks included (+inf = none, NULL =
+ * none at all); lower bounds are 0.  The basis and the pivot count are kept and
+ * the status is back to running: a non-basic column at an upper bound that
+ * became infinite goes to lower, every non-basic column is put on its dual
+ * feasible side and x_b is recomputed, so spx_solve re-optimises from the old
+ * basis.  B^-1 is untouched: steepest-edge weights stay valid.  SPX_ERR_ARG for
+ * a NaN or negative bound (the message names the column); SPX_ERR_STATE unless
+ * one rank, replicated B^-1, SPX_ALGO_DUAL and not between spx_price and
+ * spx_pivot, and when a column with e_j < -eps has no upper bound. */
+int spx_set_bounds(spx_ctx* ctx, const double* ub /* n, +inf = none */);
+int spx_get_bounds(spx_ctx* ctx, double* ub /* n */);
+
+/* The full primal vector x[0..n): basic values, u_j for a non-basic column at
+ * its upper bound (at_upper[j] = 1), 0 otherwise. */
+int spx_get_primal(spx_ctx* ctx, double* x /* n */, int8_t* at_upper /* n, may be NULL */);
 
 /* Whole solve, device-resident: at most max_iter loop passes (reference
  * MAX_ITER, v4:19, do/while at v4:286-359).  Writes z, x_b[m], b_ixs[m] (basis

@@ -164,7 +164,7 @@ class Context:
                  pricing: int = 0, persist: bool | None = None, loop_block: int = 0, comm1: bool = False,
                  tableau: bool = False, trace: int = 0, counted_tail: bool = False,
                  price_tail: bool = False, algorithm: int = ALGO_PRIMAL,
-                 dual_pricing: int = DUAL_PRICING_DANTZIG):
+                 dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -205,6 +205,12 @@ class Context:
             self.m, self.n = m, n
         self._h = h
         self._L = L
+        if upper is not None:  # 0 <= x <= upper: the dual loop only (the library refuses it otherwise)
+            try:
+                self.set_bounds(upper)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifecycle
     def close(self):
@@ -301,6 +307,34 @@ class Context:
         if bv.shape != (self.m,):
             raise ValueError(f"b must have {self.m} entries")
         check(self._L.spx_set_rhs(self._h, _ptr(bv)))
+
+    def set_bounds(self, upper):
+        """Upper bounds of all n columns, slacks included (spx_set_bounds):
+        ``inf`` = none, ``None`` = no bounds at all.  The basis is kept, the
+        placements are made dual feasible and x_b recomputed, so ``solve()``
+        re-optimises from the old basis.  ALGO_DUAL only."""
+        if upper is None:
+            check(self._L.spx_set_bounds(self._h, None))
+            return
+        ub = np.ascontiguousarray(upper, dtype=np.float64)
+        if ub.shape != (self.n,):
+            raise ValueError(f"upper must have {self.n} entries")
+        check(self._L.spx_set_bounds(self._h, _ptr(ub)))
+
+    def bounds(self) -> np.ndarray:
+        """The upper bounds in force (spx_get_bounds), ``inf`` where none."""
+        ub = np.empty(self.n, dtype=np.float64)
+        check(self._L.spx_get_bounds(self._h, _ptr(ub)))
+        return ub
+
+    def primal(self):
+        """(x, at_upper): the full primal vector of n entries -- basic values,
+        u_j for a non-basic column at its upper bound, 0 otherwise -- and the
+        at-upper flags (spx_get_primal)."""
+        x = np.empty(self.n, dtype=np.float64)
+        up = np.zeros(self.n, dtype=np.int8)
+        check(self._L.spx_get_primal(self._h, _ptr(x), _ptr(up)))
+        return x, up.astype(bool)
 
     # -- loop
     def iterate(self, k: int):

@@ -58,6 +58,9 @@ SIGNATURES = {
     "spx_set_basis": (ctypes.c_int, [_p, _p]),
     "spx_set_algorithm": (ctypes.c_int, [_p, _i32]),
     "spx_set_rhs": (ctypes.c_int, [_p, _p]),
+    "spx_set_bounds": (ctypes.c_int, [_p, _p]),
+    "spx_get_bounds": (ctypes.c_int, [_p, _p]),
+    "spx_get_primal": (ctypes.c_int, [_p, _p, _p]),
     "spx_set_dual_pricing": (ctypes.c_int, [_p, _i32]),
     "spx_get_dual_weights": (ctypes.c_int, [_p, _p]),
     "spx_group_iterate": (ctypes.c_int, [_p, _i32, _i64, _p, _p]),

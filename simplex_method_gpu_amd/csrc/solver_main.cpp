@@ -30,6 +30,10 @@
 //                  a slack basis that is not dual feasible is an error (exit 1)
 //   --dual-pricing R  leaving-row rule of --dual: dantzig (most negative x_b, default)
 //                  | steepest (dual steepest edge, SPX_DUAL_PRICING_STEEPEST)
+//   --bounds F     upper bounds 0 <= x_j <= u_j of all n columns for --dual
+//                  (spx_set_bounds): F holds n whitespace-separated values, "inf"
+//                  = none; without --dual the library's refusal is printed (exit
+//                  1); not with --mps (its reader turns bounds into rows)
 //   --tableau      window tableau (SPX_FLAG_TABLEAU): T_w = B_w A
 //                  kept in HBM, no per-pivot A / B^-1 stream
 //   --mps          the input is an MPS file (mps_io.h): converted to the
@@ -75,7 +79,7 @@ static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
                  " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual]"
-                 " [--dual-pricing dantzig|steepest]"
+                 " [--dual-pricing dantzig|steepest] [--bounds F]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -87,7 +91,7 @@ int main(int argc, char* argv[]) {
     int device = -1;
     bool iter_lines = true, json = false, gen = false, solve = true;
     int threads = 0;
-    std::string write_bin, write_text;
+    std::string write_bin, write_text, bounds_path;
     int64_t gm = 0, gn = 0;
     uint64_t gseed = 0;
     const char* path = nullptr;
@@ -129,6 +133,7 @@ int main(int argc, char* argv[]) {
         else if (s == "--mps") mps_in = true;
         else if (s == "--tableau") tableau = true;
         else if (s == "--dual") dual = true;
+        else if (s == "--bounds") { need(1); bounds_path = argv[++a]; }
         else if (s == "--dual-pricing") {
             need(1);
             const std::string r = argv[++a];
@@ -217,6 +222,34 @@ int main(int argc, char* argv[]) {
     if (rc != SPX_OK) {
         std::cerr << "spx_create failed (" << rc << "): " << spx_last_error() << "\n";
         return EXIT_FAILURE;
+    }
+    if (!bounds_path.empty()) {
+        if (mps_in) {
+            std::cerr << "--bounds does not combine with --mps: the MPS reader turns bounds into rows\n";
+            spx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+        std::ifstream bf(bounds_path);
+        std::vector<double> ub;
+        std::string tok;
+        bool bad = !bf;
+        while (!bad && bf >> tok) {
+            char* end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);  // ("inf" / "+inf" / "infinity" parse as infinity)
+            if (end == tok.c_str() || *end != '\0') bad = true;
+            ub.push_back(v);
+        }
+        if (bad || (int64_t)ub.size() != n) {
+            std::cerr << "--bounds " << bounds_path << ": expected " << n << " values (one per column, inf = none)\n";
+            spx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+        rc = spx_set_bounds(ctx, ub.data());
+        if (rc != SPX_OK) {
+            std::cerr << "spx_set_bounds failed (" << rc << "): " << spx_last_error() << "\n";
+            spx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
     }
     const TimePoint t_init_end = Clock::now();
     double z = 0.0;

@@ -11,6 +11,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -178,12 +179,17 @@ struct spx_ctx {
 
     // dual simplex loop (spx_dual.h): buffers allocated when the context first runs it
     int32_t algo = SPX_ALGO_PRIMAL;
-    DualSeArgs dual{};
+    DualBoxArgs dual{};
     DualCfg dcfg{};
     bool dual_checked = false;  // dual feasibility of the basis verified since it was last set
     double* dual_e = nullptr;   // n reduced costs (the check)
     int32_t dual_rule = SPX_DUAL_PRICING_DANTZIG;  // leaving-row rule (spx_set_dual_pricing)
     bool dual_w_stale = true;   // steepest edge: dual.w is not the current basis's (k_dual_norms before the next pass)
+    // boxed variables 0 <= x <= u (spx_set_bounds; the dual loop only).  While boxed,
+    // P.b (= b) is the effective right-hand side b_user - sum_{j at upper} u_j A_j
+    bool boxed = false;          // some bound is finite: the passes run the boxed kernels
+    std::vector<double> ub;      // n host copy (empty: never set)
+    double* b_user = nullptr;    // L: the caller's b
 
     template <typename T>
     int alloc(T** p, size_t count, unsigned ext_flags = ~0u) {
@@ -236,6 +242,7 @@ const char* spx_status_string(int32_t s) {
 namespace {
 
 int reset_stamps(spx_ctx* x);
+int box_sync(spx_ctx* x);
 
 bool env_on(const char* name);
 bool env_off(const char* name);
@@ -671,7 +678,12 @@ int do_reset(spx_ctx* x) {
     for (double* v : {x->P.alpha0, x->P.alpha1, x->P.y0, x->P.y1, x->P.x_b, x->P.c_B})
         HIP_TRY(hipMemsetAsync(v, 0, (size_t)x->L * sizeof(double), x->stream));
     SPX_TRY(clear_tickets(x));
+    if (x->boxed) {  // every column back at its lower bound: b_eff = b
+        HIP_TRY(hipMemsetAsync(x->dual.at_upper, 0, (size_t)x->n, x->stream));
+        HIP_TRY(hipMemcpyAsync(x->b, x->b_user, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
+    }
     HIP_TRY(launch_reset(x->P, x->stream));
+    SPX_TRY(box_sync(x));
     HIP_TRY(launch_se_init(x->P, x->stream));  // steepest edge: gamma_j = 1 + ||A_j||^2
     if (x->P.bc) {  // B_w = I: no column list
         HIP_TRY(hipMemsetAsync(x->P.rleft, 0, (size_t)x->L * sizeof(int32_t), x->stream));
@@ -1023,9 +1035,63 @@ int dual_setup(spx_ctx* x) {
     return SPX_OK;
 }
 
+// Boxed contexts: the effective right-hand side for the current placements
+// (k_box_rhs), before anything that recomputes x_b from P.b
+int box_sync(spx_ctx* x) {
+    if (!x->boxed) return SPX_OK;
+    HIP_TRY(launch_box_rhs(x->P, x->dual, x->b_user, x->b, x->stream));
+    return SPX_OK;
+}
+
+// ... and x_b = B^-1 b_eff from it (B^-1 untouched)
+int box_recompute_xb(spx_ctx* x) {
+    SPX_TRY(box_sync(x));
+    HIP_TRY(launch_box_xb(x->P, x->dcfg, x->stream));
+    return SPX_OK;
+}
+
+// Boxed entry normalisation: every non-basic column on the side where its
+// reduced cost is dual feasible (e_j >= -eps at lower, e_j <= eps at upper;
+// |e_j| <= eps keeps its side); x_b recomputed when a placement changed (or
+// `force`).  A column with e_j < -eps and no upper bound has no such side.
+int box_normalise(spx_ctx* x, bool force) {
+    HIP_TRY(launch_reduced_costs(x->P, x->dual_e, x->stream));
+    const size_t n = (size_t)x->n;
+    std::vector<double> e(n);
+    std::vector<int32_t> pos(n);
+    std::vector<int8_t> up(n);
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(e.data(), x->dual_e, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
+    const double eps = x->opts.eps;
+    bool changed = false;
+    for (size_t j = 0; j < n; ++j) {
+        if (pos[j] < 0) {  // basic: no placement
+            if (up[j]) { up[j] = 0; changed = true; }
+            continue;
+        }
+        if (e[j] < -eps) {
+            if (!std::isfinite(x->ub[j]))
+                return fail(SPX_ERR_STATE, "basis is not dual feasible (reduced cost %g at column %lld, eps %g): the "
+                            "column has no upper bound to sit at, and the dual simplex loop needs e_j >= -eps at a "
+                            "lower bound", e[j], (long long)j, eps);
+            if (!up[j]) { up[j] = 1; changed = true; }
+        } else if (e[j] > eps && up[j]) {
+            up[j] = 0;
+            changed = true;
+        }
+    }
+    if (changed) HIP_TRY(hipMemcpy(x->dual.at_upper, up.data(), n, hipMemcpyHostToDevice));
+    if (changed || force) SPX_TRY(box_recompute_xb(x));
+    x->dual_checked = true;
+    return SPX_OK;
+}
+
 // min over the non-basic columns of e_j = y.A_j - c_j must be >= -eps (x_b and
 // y are current: nothing of theirs is pending when the dual loop starts)
 int dual_check_feasible(spx_ctx* x) {
+    if (x->boxed) return box_normalise(x, false);
     HIP_TRY(launch_reduced_costs(x->P, x->dual_e, x->stream));
     std::vector<double> e((size_t)x->n);
     std::vector<int32_t> pos((size_t)x->n);
@@ -1058,8 +1124,8 @@ int dual_refresh_weights(spx_ctx* x) {
 // One dual pass: leaving row + pivot row, ratio test, FTRAN + update.
 int enqueue_dual_pass(spx_ctx* x, hipEvent_t p0, hipEvent_t p1, hipEvent_t u0, hipEvent_t u1) {
     const bool se = x->dual_rule == SPX_DUAL_PRICING_STEEPEST;
-    HIP_TRY(launch_dual_step(x->P, x->dual, se, false, x->stream));
-    HIP_TRY(launch_dual_price(x->P, x->dual, x->dcfg, x->stream, p0, p1));
+    HIP_TRY(launch_dual_step(x->P, x->dual, se, x->boxed, false, x->stream));
+    HIP_TRY(launch_dual_price(x->P, x->dual, x->dcfg, x->boxed, x->stream, p0, p1));
     if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
     HIP_TRY(launch_dual_update(x->P, x->dual, x->dcfg, se, x->stream, u0, u1));
     return SPX_OK;
@@ -1098,7 +1164,7 @@ int iterate_dual(spx_ctx* x, int64_t k) {
         SPX_TRY(enqueue_dual_pass(x, p0, p1, u0, u1));
         ++x->n_eager;
     }
-    HIP_TRY(launch_dual_step(x->P, x->dual, se, true, x->stream));  // (steepest edge: the last pivot's weights too)
+    HIP_TRY(launch_dual_step(x->P, x->dual, se, x->boxed, true, x->stream));  // (steepest edge: the last pivot's weights too)
     return read_state(x);
 }
 
@@ -1189,6 +1255,7 @@ int reinvert_basis(spx_ctx* x, const int64_t* basis) {
         HIP_TRY(hipMemcpy(x->rv_pos, pos.data(), pos.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(x->P.b_ixs, basis, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice));
+    SPX_TRY(box_sync(x));  // boxed: x_b below is B^-1 b_eff of the current placements
     HIP_TRY(hipMemsetAsync(R.rs, 0, sizeof(RvState), x->stream));
     HIP_TRY(hipMemsetAsync(R.X, 0, (size_t)(m * L) * sizeof(double), x->stream));
     HIP_TRY(rv_launch_identity(R, x->stream));
@@ -1612,6 +1679,9 @@ int spx_set_algorithm(spx_ctx* x, int32_t algo) {
     if (algo != SPX_ALGO_PRIMAL && algo != SPX_ALGO_DUAL) return fail(SPX_ERR_ARG, "bad algorithm %d", algo);
     if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_algorithm between spx_price and spx_pivot");
+    if (algo == SPX_ALGO_PRIMAL && x->boxed)
+        return fail(SPX_ERR_STATE, "the primal loop does not run with finite upper bounds (spx_set_bounds): bounded "
+                    "variables are the dual simplex loop's; remove the bounds first");
     if (algo == SPX_ALGO_DUAL) {
         if (const char* why = dual_conflict(x->opts, x->P.win))
             return fail(SPX_ERR_STATE, "the dual simplex loop does not run %s", why);
@@ -1663,9 +1733,106 @@ int spx_set_rhs(spx_ctx* x, const double* b) {
     if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_rhs between spx_price and spx_pivot");
     HIP_TRY(hipStreamSynchronize(x->stream));
-    HIP_TRY(hipMemcpy(x->b, b, (size_t)x->m * sizeof(double), hipMemcpyHostToDevice));  // (rows m..L-1 stay 0)
+    // (rows m..L-1 stay 0; boxed: the caller's b, reinvert_basis forms b_eff from it)
+    HIP_TRY(hipMemcpy(x->boxed ? x->b_user : x->b, b, (size_t)x->m * sizeof(double), hipMemcpyHostToDevice));
     SPX_TRY(reinvert_current(x));  // x_b = B^-1 b (and the window / tableau rebuilds)
     return set_running(x);
+}
+
+int spx_set_bounds(spx_ctx* x, const double* ub) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    const size_t n = (size_t)x->n;
+    bool finite = false;
+    for (size_t j = 0; ub && j < n; ++j) {
+        if (std::isnan(ub[j])) return fail(SPX_ERR_ARG, "upper bound of column %lld is NaN", (long long)j);
+        if (ub[j] < 0.0)
+            return fail(SPX_ERR_ARG, "upper bound %g of column %lld is negative (lower bounds are 0)", ub[j], (long long)j);
+        finite = finite || std::isfinite(ub[j]);
+    }
+    if (x->opts.nranks > 1 || x->P.row_shard)
+        return fail(SPX_ERR_STATE, "spx_set_bounds needs one rank and replicated B^-1 (nranks %d%s)", x->opts.nranks,
+                    x->P.row_shard ? ", row-sharded" : "");
+    if (x->algo != SPX_ALGO_DUAL)
+        return fail(SPX_ERR_STATE, "upper bounds need the dual simplex loop (SPX_ALGO_DUAL): the primal loop does not "
+                    "run bounded variables");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_bounds between spx_price and spx_pivot");
+    SPX_TRY(dual_setup(x));
+    {  // refused before anything changes: a column that would have no dual feasible side
+        HIP_TRY(launch_reduced_costs(x->P, x->dual_e, x->stream));
+        std::vector<double> e(n);
+        std::vector<int32_t> pos(n);
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        HIP_TRY(hipMemcpy(e.data(), x->dual_e, n * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < n; ++j)
+            if (pos[j] >= 0 && e[j] < -x->opts.eps && !(ub && std::isfinite(ub[j])))
+                return fail(SPX_ERR_STATE, "basis is not dual feasible (reduced cost %g at column %lld, eps %g): the "
+                            "column has no upper bound to sit at, and the dual simplex loop needs e_j >= -eps at a "
+                            "lower bound", e[j], (long long)j, x->opts.eps);
+    }
+    if (!finite && !x->boxed) {  // nothing to keep: today's kernels, today's state
+        x->ub.assign(n, INFINITY);
+        return set_running(x);
+    }
+    if (!x->dual.ub) {
+        double* d_ub = nullptr;
+        SPX_TRY(x->alloc(&d_ub, n));
+        x->dual.ub = d_ub;
+        SPX_TRY(x->alloc(&x->dual.ub_B, (size_t)x->L));
+        SPX_TRY(x->alloc(&x->dual.at_upper, n));
+        SPX_TRY(x->alloc(&x->b_user, (size_t)x->L));
+    }
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    if (!x->boxed) {  // P.b is still the caller's b, every column at lower
+        HIP_TRY(hipMemcpy(x->b_user, x->b, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemset(x->dual.at_upper, 0, n));
+    }
+    x->ub.assign(n, INFINITY);
+    if (ub) x->ub.assign(ub, ub + n);
+    HIP_TRY(hipMemcpy(const_cast<double*>(x->dual.ub), x->ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    // a column at an upper bound that no longer exists goes to lower
+    std::vector<int8_t> up(n);
+    HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < n; ++j)
+        if (up[j] && !std::isfinite(x->ub[j])) up[j] = 0;
+    HIP_TRY(hipMemcpy(x->dual.at_upper, up.data(), n, hipMemcpyHostToDevice));
+    x->boxed = true;  // (the normalisation and b_eff below run on the boxed state either way)
+    x->dual_checked = false;
+    SPX_TRY(set_running(x));
+    const int rc = box_normalise(x, true);
+    if (!finite && rc == SPX_OK) {  // no bound left: P.b is b again (no column at upper), the plain kernels run
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        x->boxed = false;
+    }
+    return rc;
+}
+
+int spx_get_bounds(spx_ctx* x, double* ub) {
+    if (!x || !ub) return fail(SPX_ERR_ARG, "NULL argument");
+    for (size_t j = 0; j < (size_t)x->n; ++j) ub[j] = x->ub.empty() ? INFINITY : x->ub[j];
+    return SPX_OK;
+}
+
+int spx_get_primal(spx_ctx* x, double* xv, int8_t* at_upper) {
+    if (!x || !xv) return fail(SPX_ERR_ARG, "NULL argument");
+    const size_t n = (size_t)x->n, m = (size_t)x->m;
+    std::vector<double> xb(m);
+    std::vector<int64_t> bix(m);
+    SPX_TRY(spx_get_state(x, xb.data(), bix.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+    std::vector<int8_t> up(n, 0);
+    std::vector<int32_t> pos(n, 0);
+    if (x->boxed) {
+        HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    for (size_t j = 0; j < n; ++j) {
+        up[j] = (x->boxed && up[j] && pos[j] >= 0) ? 1 : 0;
+        xv[j] = up[j] ? x->ub[j] : 0.0;
+    }
+    for (size_t i = 0; i < m; ++i) xv[(size_t)bix[i]] = xb[i];
+    if (at_upper) std::memcpy(at_upper, up.data(), n);
+    return SPX_OK;
 }
 
 int spx_iterate(spx_ctx* x, int64_t k, int32_t* status, int64_t* pivots) {
@@ -1808,7 +1975,21 @@ int spx_objective(spx_ctx* x, double* z) {
     SPX_TRY(gather_xb(x));
     HIP_TRY(launch_objective(x->P, x->stream));
     SPX_TRY(read_state(x));
-    if (z) *z = x->st_host->z;
+    double zv = x->st_host->z;
+    if (x->boxed) {  // + sum of c_j u_j over the non-basic columns at upper, ascending j
+        const size_t n = (size_t)x->n;
+        std::vector<double> c(n);
+        std::vector<int8_t> up(n);
+        std::vector<int32_t> pos(n);
+        HIP_TRY(hipMemcpy(c.data(), x->c, n * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        double zu = 0.0;
+        for (size_t j = 0; j < n; ++j)
+            if (up[j] && pos[j] >= 0) zu += c[j] * x->ub[j];
+        zv += zu;
+    }
+    if (z) *z = zv;
     return SPX_OK;
 }
 

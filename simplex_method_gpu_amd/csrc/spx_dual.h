@@ -30,6 +30,15 @@
 // before the pivot), k_dual_step_se's commit turns them into the weights after
 // the pivot (DualSeArgs::w) and its selection takes argmin -x_b^2 / w.
 // k_dual_norms recomputes w from B^-1 where no pass has kept it.
+//
+// Boxed variables 0 <= x <= u (spx_set_bounds) run k_dual_step_box /
+// k_dual_step_se_box and k_dual_price<., true>: the selection takes the two-sided
+// violation delta and leaves its side s in DualRec, the ratio test flips a_j and
+// d_j by s and sigma_j (DualBoxArgs::at_upper), the commit starts the entering
+// column from the bound it sat at and keeps at_upper / ub_B with the basis.
+// k_dual_update and k_dual_norms are shared: alpha, tau and wex do not depend on
+// bounds.  P.b is then the effective right-hand side (k_box_rhs).  A context
+// with no finite bound launches the unboxed kernels only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,7 +58,7 @@ struct alignas(16) DualRec {  // the pass in flight
     int64_t p;      // entering column (k_dual_update)
     double d_p;     // its reduced cost
     int32_t fresh;  // 1: k_dual_update ran the FTRAN, the pivot awaits k_dual_step
-    int32_t pad;
+    int32_t s;      // boxed passes: +1 the row leaves to its lower bound, -1 to its upper bound
 };
 
 struct DualArgs {
@@ -70,6 +79,14 @@ struct DualSeArgs : DualArgs {
     double* w;    // L: the weights of the current basis (k_dual_step_se, k_dual_norms)
 };
 
+// the boxed instantiations' arguments (0 <= x <= u; a context with no finite
+// bound never launches them)
+struct DualBoxArgs : DualSeArgs {
+    const double* ub;   // n: upper bounds, +inf = none
+    double* ub_B;       // L: the bound of row i's basic column (ub[b_ixs[i]])
+    int8_t* at_upper;   // n: 1 = the non-basic column sits at its upper bound
+};
+
 struct DualCfg {
     int price_grid = 0;
     bool price_lds = false;  // rho and y staged in LDS (2 * 8 * L bytes) or read from global
@@ -87,12 +104,19 @@ constexpr double DUAL_W_FLOOR = 1e-300;  // steepest-edge weights stay positive:
 // (and the steepest-edge update's operands) in global memory
 hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, bool se_rho_lds, DualCfg* cfg);
 // se: the steepest-edge instantiations (leaving row by -x_b^2 / w, weights kept in D.w)
-hipError_t launch_dual_step(const Params& P, const DualSeArgs& D, bool se, bool finish_only, hipStream_t s);
-hipError_t launch_dual_price(const Params& P, const DualArgs& D, const DualCfg& c, hipStream_t s, hipEvent_t e0,
-                             hipEvent_t e1);
+// box: the boxed instantiations (two-sided leaving rows, sigma_j in the ratio test)
+hipError_t launch_dual_step(const Params& P, const DualBoxArgs& D, bool se, bool box, bool finish_only, hipStream_t s);
+hipError_t launch_dual_price(const Params& P, const DualBoxArgs& D, const DualCfg& c, bool box, hipStream_t s,
+                             hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_dual_update(const Params& P, const DualSeArgs& D, const DualCfg& c, bool se, hipStream_t s,
                               hipEvent_t e0, hipEvent_t e1);
 // D.w = squared row norms of the true B^-1 (pending pivot applied in registers)
 hipError_t launch_dual_norms(const Params& P, const DualSeArgs& D, const DualCfg& c, hipStream_t s);
+
+// b_eff = b_user - sum over the non-basic columns at upper of u_j A_j (ascending
+// j, one thread per row: no atomics), and D.ub_B from b_ixs
+hipError_t launch_box_rhs(const Params& P, const DualBoxArgs& D, const double* b_user, double* b_eff, hipStream_t s);
+// x_b = (true B^-1) P.b, the pending pivot applied in registers (k_dual_norms' form)
+hipError_t launch_box_xb(const Params& P, const DualCfg& c, hipStream_t s);
 
 }  // namespace spx

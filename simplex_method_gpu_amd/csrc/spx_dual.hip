@@ -75,6 +75,7 @@ struct SeDots<0> {};
 #define SPX_STEP_KERNEL k_dual_step
 #define SPX_STEP_ARGS DualArgs
 #define SPX_STEP_SE 0
+#define SPX_STEP_BOX 0
 #include "spx_dual_step.inc"
 #undef SPX_STEP_KERNEL
 #undef SPX_STEP_ARGS
@@ -86,6 +87,22 @@ struct SeDots<0> {};
 #undef SPX_STEP_KERNEL
 #undef SPX_STEP_ARGS
 #undef SPX_STEP_SE
+#undef SPX_STEP_BOX
+// boxed variables (0 <= x <= u): Dantzig and steepest edge
+#define SPX_STEP_KERNEL k_dual_step_box
+#define SPX_STEP_ARGS DualBoxArgs
+#define SPX_STEP_SE 0
+#define SPX_STEP_BOX 1
+#include "spx_dual_step.inc"
+#undef SPX_STEP_KERNEL
+#undef SPX_STEP_SE
+#define SPX_STEP_KERNEL k_dual_step_se_box
+#define SPX_STEP_SE 1
+#include "spx_dual_step.inc"
+#undef SPX_STEP_KERNEL
+#undef SPX_STEP_ARGS
+#undef SPX_STEP_SE
+#undef SPX_STEP_BOX
 
 // ---------------------------------------------------------------------------
 // Dual ratio test (the hot kernel): two dots per streamed non-basic column
@@ -96,8 +113,12 @@ struct SeDots<0> {};
 // k_price's A stream.  Per lane the chunks are accumulated in ascending order
 // into four partial sums, then one butterfly: a column's a_j and d_j do not
 // depend on the grid or on which wave prices it.
-template <bool LDS>
-__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, DualArgs D) {
+// BOX (0 <= x <= u): with s the pass's direction (DualRec::s) and sigma_j = -1
+// for a column at its upper bound (one wave-uniform flag read per column, ahead
+// of its stream), candidates are s sigma_j a_j < -piv_tol and the key is
+// max(sigma_j d_j, 0) / -(s sigma_j a_j); the partial carries the raw a_j, d_j.
+template <bool LDS, bool BOX>
+__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, std::conditional_t<BOX, DualBoxArgs, DualArgs> D) {
     constexpr int WAVES = DUAL_WAVES, U = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
     __shared__ DualPartial s_red[WAVES];
@@ -129,8 +150,12 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, DualArgs D)
     double bkey = INFINITY, ba = 0.0, bd = 0.0;
     int64_t bidx = INT64_MAX;
     const int nwv = (int)gridDim.x * WAVES;
+    [[maybe_unused]] double dir = 1.0;
+    if constexpr (BOX) dir = D.rec->s < 0 ? -1.0 : 1.0;
     for (int s = (int)blockIdx.x * WAVES + wave; s < cnt; s += nwv) {
         const int64_t j = P.nb_list[s];
+        [[maybe_unused]] int up = 0;
+        if constexpr (BOX) up = D.at_upper[j];
         double a, d;
         if (P.slack_unit && j >= P.ns) {  // A_j = e_k: no stream
             const int64_t k = j - P.ns;
@@ -165,7 +190,19 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, DualArgs D)
             wave_sum2(a, d);
             d -= P.c[j];
         }
-        if (a < -D.piv_tol) {
+        if constexpr (BOX) {
+            const double sg = up ? -1.0 : 1.0;
+            const double ah = dir * sg * a, dh = sg * d;  // (sign flips: exact)
+            if (ah < -D.piv_tol) {
+                const double key = (dh > 0.0 ? dh : 0.0) / (-ah);
+                if (argmin_better(key, j, bkey, bidx)) {
+                    bkey = key;
+                    bidx = j;
+                    ba = a;
+                    bd = d;
+                }
+            }
+        } else if (a < -D.piv_tol) {
             const double key = (d > 0.0 ? d : 0.0) / (-a);
             if (argmin_better(key, j, bkey, bidx)) {
                 bkey = key;
@@ -339,6 +376,56 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_norms(Params P, DualSeArgs 
 }
 
 // ---------------------------------------------------------------------------
+// Boxed variables: the effective right-hand side and x_b from it
+// ---------------------------------------------------------------------------
+// One thread per row: b_eff_i = b_i - sum_j u_j A_ij over the non-basic columns
+// at their upper bound, in ascending j (a fixed order, no atomics); rows m..L-1
+// stay 0.  Also ub_B_i = ub[b_ixs[i]].  Runs between passes, before anything
+// that recomputes x_b from P.b.
+constexpr int BOX_BLOCK = 256;
+__global__ __launch_bounds__(BOX_BLOCK) void k_box_rhs(Params P, DualBoxArgs D, const double* b_user, double* b_eff) {
+    const int64_t i = (int64_t)blockIdx.x * BOX_BLOCK + threadIdx.x;
+    const int64_t m = P.m, n = P.n, L = P.L;
+    if (i >= L) return;
+    double acc = i < m ? b_user[i] : 0.0;
+    if (i < m) {
+        for (int64_t j = 0; j < n; ++j)
+            if (D.at_upper[j] && P.nb_pos[j] >= 0) acc = fma(-D.ub[j], P.A[j * L + i], acc);
+        D.ub_B[i] = D.ub[P.b_ixs[i]];
+    }
+    b_eff[i] = acc;
+}
+
+// One row per wave: x_b_i = (S[i] + E_i r') . b, the pending pivot applied in
+// registers as k_dual_norms does (nothing is written to B^-1).
+__global__ __launch_bounds__(DUAL_BLOCK) void k_box_xb(Params P) {
+    constexpr int WAVES = DUAL_WAVES;
+    const DevState* st = P.st;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t it = st->iter, qp = st->q;
+    const double aqp = st->aq;
+    const int64_t m = P.m, L = P.L;
+    const int nch = (int)(L >> 7);
+    const int64_t i = (int64_t)blockIdx.x * WAVES + wave;
+    if (i >= m) return;
+    const bool pend = it > 0 && qp >= 0 && qp < m;
+    const double* a_prev = (it & 1) ? P.alpha1 : P.alpha0;
+    const double ei = pend ? eta_entry(a_prev[i], i, qp, aqp) : 0.0;
+    const dbl2* row = reinterpret_cast<const dbl2*>(P.B0 + i * L) + lane;
+    const dbl2* rp = reinterpret_cast<const dbl2*>(pend ? P.B0 + qp * L : P.zeros) + lane;
+    const dbl2* bv = reinterpret_cast<const dbl2*>(P.b) + lane;
+    double x0 = 0.0, x1 = 0.0;
+    for (int c = 0; c < nch; ++c) {
+        const dbl2 s = row[64 * c], r = rp[64 * c], b = bv[64 * c];
+        x0 = fma(fma(ei, r.x, s.x), b.x, x0);
+        x1 = fma(fma(ei, r.y, s.y), b.y, x1);
+    }
+    const double x = wave_sum(x0 + x1);
+    if (lane == 0) P.x_b[i] = x;
+}
+
+// ---------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------
 namespace {
@@ -372,11 +459,12 @@ hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool globa
     hipError_t e = hipSuccess;
     int per_cu = 0;
     if (cfg->price_lds) {
-        e = set_lds(k_dual_price<true>, vec2);
+        e = set_lds(k_dual_price<true, false>, vec2);
+        if (e == hipSuccess) e = set_lds(k_dual_price<true, true>, vec2);  // (the same grid: DESIGN.md 7d)
         if (e == hipSuccess)
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dual_price<true>, DUAL_BLOCK, vec2);
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dual_price<true, false>, DUAL_BLOCK, vec2);
     } else {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dual_price<false>, DUAL_BLOCK, 0);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dual_price<false, false>, DUAL_BLOCK, 0);
     }
     if (e != hipSuccess) return e;
     if (cfg->update_lds) {
@@ -398,17 +486,28 @@ hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool globa
     return hipSuccess;
 }
 
-hipError_t launch_dual_step(const Params& P, const DualSeArgs& D, bool se, bool finish_only, hipStream_t s) {
+hipError_t launch_dual_step(const Params& P, const DualBoxArgs& D, bool se, bool box, bool finish_only,
+                            hipStream_t s) {
+    const DualSeArgs& D1 = D;
     const DualArgs& D0 = D;
-    if (se) hipLaunchKernelGGL(k_dual_step_se, dim3(1), dim3(1024), 0, s, P, D, finish_only ? 1 : 0);
-    else hipLaunchKernelGGL(k_dual_step, dim3(1), dim3(1024), 0, s, P, D0, finish_only ? 1 : 0);
+    const int fin = finish_only ? 1 : 0;
+    if (box && se) hipLaunchKernelGGL(k_dual_step_se_box, dim3(1), dim3(1024), 0, s, P, D, fin);
+    else if (box) hipLaunchKernelGGL(k_dual_step_box, dim3(1), dim3(1024), 0, s, P, D, fin);
+    else if (se) hipLaunchKernelGGL(k_dual_step_se, dim3(1), dim3(1024), 0, s, P, D1, fin);
+    else hipLaunchKernelGGL(k_dual_step, dim3(1), dim3(1024), 0, s, P, D0, fin);
     return hipGetLastError();
 }
 
-hipError_t launch_dual_price(const Params& P, const DualArgs& D, const DualCfg& c, hipStream_t s, hipEvent_t e0,
-                             hipEvent_t e1) {
-    if (c.price_lds) return launch_timed(k_dual_price<true>, c.price_grid, (size_t)P.L * 16, s, e0, e1, P, D);
-    return launch_timed(k_dual_price<false>, c.price_grid, 0, s, e0, e1, P, D);
+hipError_t launch_dual_price(const Params& P, const DualBoxArgs& D, const DualCfg& c, bool box, hipStream_t s,
+                             hipEvent_t e0, hipEvent_t e1) {
+    const size_t lds = c.price_lds ? (size_t)P.L * 16 : 0;
+    if (box) {
+        if (c.price_lds) return launch_timed(k_dual_price<true, true>, c.price_grid, lds, s, e0, e1, P, D);
+        return launch_timed(k_dual_price<false, true>, c.price_grid, 0, s, e0, e1, P, D);
+    }
+    const DualArgs& D0 = D;
+    if (c.price_lds) return launch_timed(k_dual_price<true, false>, c.price_grid, lds, s, e0, e1, P, D0);
+    return launch_timed(k_dual_price<false, false>, c.price_grid, 0, s, e0, e1, P, D0);
 }
 
 hipError_t launch_dual_update(const Params& P, const DualSeArgs& D, const DualCfg& c, bool se, hipStream_t s,
@@ -425,6 +524,17 @@ hipError_t launch_dual_update(const Params& P, const DualSeArgs& D, const DualCf
 
 hipError_t launch_dual_norms(const Params& P, const DualSeArgs& D, const DualCfg& c, hipStream_t s) {
     hipLaunchKernelGGL(k_dual_norms, dim3(c.update_grid), dim3(DUAL_BLOCK), 0, s, P, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_box_rhs(const Params& P, const DualBoxArgs& D, const double* b_user, double* b_eff, hipStream_t s) {
+    const int grid = (int)((P.L + BOX_BLOCK - 1) / BOX_BLOCK);
+    hipLaunchKernelGGL(k_box_rhs, dim3(grid), dim3(BOX_BLOCK), 0, s, P, D, b_user, b_eff);
+    return hipGetLastError();
+}
+
+hipError_t launch_box_xb(const Params& P, const DualCfg& c, hipStream_t s) {
+    hipLaunchKernelGGL(k_box_xb, dim3(c.update_grid), dim3(DUAL_BLOCK), 0, s, P);
     return hipGetLastError();
 }
 

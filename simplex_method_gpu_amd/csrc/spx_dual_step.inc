@@ -3,6 +3,7 @@
 //   SPX_STEP_KERNEL  the kernel's name
 //   SPX_STEP_ARGS    DualArgs (Dantzig) or DualSeArgs (steepest edge)
 //   SPX_STEP_SE      0 / 1
+//   SPX_STEP_BOX     0 / 1 (1: SPX_STEP_ARGS is DualBoxArgs)
 // Text inclusion, not a template: as a template instantiation (and as a
 // forceinline body shared by two kernels) the Dantzig kernel compiled to a
 // different schedule than the plain function it has always been; included
@@ -10,6 +11,15 @@
 // SE: the commit also turns the pass's exact row norms wex and tau = B^-1 rho
 // (k_dual_update<., SE>) into the weights of the basis after the pivot, D.w,
 // and the leaving row is the argmin of -x_b^2 / w.
+// BOX (0 <= x <= u): a row leaves when x_b < -feas_tol (to its lower bound, s =
+// +1) or x_b > u + feas_tol (to its upper bound, s = -1); delta is the violation
+// on that side and takes x_b's place in both rules and in theta.  The side
+// travels through the argmin in the row index's low bit (2 i + side: the order
+// of the rows, hence the first index on ties, is kept, and the reduction is the
+// unboxed one), the selection leaves s in the pass record, the commit forms
+// delta_q from x_b[q] and ub_B[q] (loaded beside alpha_q: no longer chain),
+// offsets the entering value by u_p when p sat at its upper bound and keeps
+// at_upper / ub_B with the basis.
 __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS D, int finish_only) {
     constexpr int BLOCK = 1024, WAVES = BLOCK / 64;
     DevState* st = P.st;
@@ -44,7 +54,15 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
         // pivot it: alpha = B^-1 A_p is in alpha[(it + 1) & 1] (k_dual_update)
         const int64_t q = S.q, p = S.p;
         const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
+#if SPX_STEP_BOX
+        const double aq = al[q], xq0 = P.x_b[q], ubq = D.ub_B[q];  // (every thread: the same words)
+        const int32_t sgn = D.rec->s;
+        const double xq = sgn > 0 ? xq0 : xq0 - ubq;  // delta_q
+        const double u_p = D.ub[p];
+        const double x_off = D.at_upper[p] ? u_p : 0.0;  // where the entering column starts from
+#else
         const double aq = al[q], xq = P.x_b[q];  // (every thread: the same two words)
+#endif
 #if SPX_STEP_SE
         const double wq = D.tau[q];  // rho . rho
 #endif
@@ -80,7 +98,11 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
                 const int64_t i = i0 + (int64_t)u * BLOCK;
+#if SPX_STEP_BOX
+                if (i < m) P.x_b[i] = (i == q) ? x_off + theta : fma(-theta, av[u], xv[u]);
+#else
                 if (i < m) P.x_b[i] = (i == q) ? theta : fma(-theta, av[u], xv[u]);
+#endif
                 if (i < L) y[i] = fma(sy, rv[u], yv[u]);
 #if SPX_STEP_SE
                 // w'_i = w_i - 2 r_i tau_i + r_i^2 w_q, r_i = alpha_i / alpha_q; w'_q = w_q / alpha_q^2
@@ -93,6 +115,11 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
         if (book) {
             P.c_B[q] = c_p;
             P.b_ixs[q] = p;
+#if SPX_STEP_BOX
+            D.ub_B[q] = u_p;
+            D.at_upper[p] = 0;
+            D.at_upper[leave] = sgn < 0 ? 1 : 0;
+#endif
             // nb_list / nb_pos as pivot_bookkeeping keeps them: swap-remove p, append the leaving column
             int cnt = S.cnt;
             P.nb_list[kp] = last;
@@ -125,6 +152,22 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
     // -x_b^2 / w among them), first index on ties
     double bv = INFINITY;
     int64_t bi = INT64_MAX;
+#if SPX_STEP_BOX
+    for (int64_t i = tid; i < m; i += BLOCK) {
+        const double x = P.x_b[i], ub = D.ub_B[i];
+        const double dl = x < -D.feas_tol ? x : (x > ub + D.feas_tol ? x - ub : 0.0);
+#if SPX_STEP_SE
+        const double v = -(dl * dl) / D.w[i];
+#else
+        const double v = -fabs(dl);
+#endif
+        const int64_t i2 = 2 * i + (dl > 0.0 ? 1 : 0);  // (row, side)
+        if (dl != 0.0 && argmin_better(v, i2, bv, bi)) {
+            bv = v;
+            bi = i2;
+        }
+    }
+#else
     for (int64_t i = tid; i < m; i += BLOCK) {
 #if SPX_STEP_SE
         const double x = P.x_b[i];
@@ -138,6 +181,7 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
             bi = i;
         }
     }
+#endif
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         const double v2 = __shfl_xor(bv, off, 64);
@@ -153,6 +197,12 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
         ArgMinEntry t = s_red[0];
         for (int w = 1; w < WAVES; ++w)
             if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
+#if SPX_STEP_BOX
+        if (t.idx != INT64_MAX) {
+            D.rec->s = (t.idx & 1) ? -1 : 1;
+            t.idx >>= 1;
+        }
+#endif
         S.q = t.idx;
         if (t.idx == INT64_MAX) st->status = ST_OPTIMAL;  // primal feasible: optimum
         else D.rec->q = t.idx;

@@ -19,8 +19,24 @@ are compared with.  --solve also times a whole solve of the covering LP to the
 optimum under the rule (pivots and seconds, refactor_every = --refactor), and
 --solve-shape M N SEED adds further shapes to that.
 
+--boxed measures bounded variables (spx_set_bounds; tests/dual_box_ref.py
+boxed(m, n, seed): the same covering LP with upper bounds): for both rules, at
+the same timed-pivot protocol, this build's boxed kernels ("boxed_<rule>"), its
+unbounded kernels on the plain covering LP ("plain_<rule>"), the boxed kernels
+on that plain LP's pivots ("boxedk_<rule>": one finite bound that no x reaches,
+so both walk the same pivots and the kernel times compare like for like), and with
+--parent-root the parent's unbounded dual loop beside them ("parent_<rule>"),
+all between two runs of the primal explicit pass.  rest_us is what a pass takes
+beyond k_dual_price and k_dual_update (1e6 / it_per_s - price_us - update_us):
+k_dual_step and the launch gaps.  --solve then times whole boxed solves under
+both rules at the shape and at every --solve-shape, each checked by the CPU
+certificate recomputed from the returned basis and placements
+(tests/dual_box_ref.py certificate); --solve-max-iter caps a solve.
+
     python tools/dual_bench.py [--k 1000 --warm 200] [--dual-pricing steepest] [--solve]
                                [--parent-root DIR] [--out profiles/dual_c3.json]
+    python tools/dual_bench.py --boxed --parent-root DIR --solve --solve-shape 1024 4096 4
+                               --out profiles/dual_box_c3.json
 """
 import argparse
 import json
@@ -36,7 +52,7 @@ sys.path.insert(1, os.path.join(ROOT, "tests"))
 PEAK = 8.0e12  # MI355X HBM bytes/s the fractions are quoted against
 
 
-def measure(make_ctx, k, warm):
+def measure(make_ctx, k, warm, rest=False):
     """it/s from an untimed context, kernel means from a timing one."""
     with make_ctx(False) as ctx:
         ctx.iterate(warm)
@@ -55,13 +71,16 @@ def measure(make_ctx, k, warm):
     price_us = 1e3 * kt["price_ms"] / nl
     update_us = 1e3 * kt["update_ms"] / max(kt["update_launches"], 1)
     bytes_price = 0.5 * (b0["bytes_price"] + b1["bytes_price"])
-    return {"pivots": p1 - p0, "status": int(st), "it_per_s": round((p1 - p0) / dt, 1),
+    res = {"pivots": p1 - p0, "status": int(st), "it_per_s": round((p1 - p0) / dt, 1),
             "price_us": round(price_us, 2), "update_us": round(update_us, 2),
             "timed_passes": kt["price_launches"],
             "bytes_price": bytes_price, "bytes_update": b1["bytes_update"],
             "price_TBps": round(bytes_price / (price_us * 1e-6) / 1e12, 3),
             "price_frac_of_8TBps": round(bytes_price / (price_us * 1e-6) / PEAK, 3),
             "update_TBps": round(b1["bytes_update"] / (update_us * 1e-6) / 1e12, 3)}
+    if rest:  # (--boxed) the pass outside its two big kernels
+        res["rest_us"] = round(1e6 * dt / max(p1 - p0, 1) - price_us - update_us, 2)
+    return res
 
 
 def run_primal(a):
@@ -70,7 +89,7 @@ def run_primal(a):
     def make(timing):
         return spx.Context(m=a.m, n=a.n, seed=0, device=0, window=-1, timing=timing)
 
-    return measure(make, a.k, a.warm)
+    return measure(make, a.k, a.warm, a.rest)
 
 
 def rule_kw(a, spx):
@@ -84,16 +103,28 @@ def run_dual(a):
     import dual_ref
     import simplex_method_gpu_amd as spx
 
-    A, b, c = dual_ref.covering(a.m, a.n, a.seed)
+    kw = rule_kw(a, spx)
+    if a.boxed:
+        import dual_box_ref
+
+        A, b, c, u = dual_box_ref.boxed(a.m, a.n, a.seed)
+        kw["upper"] = u
+    else:
+        A, b, c = dual_ref.covering(a.m, a.n, a.seed)
+        if a.boxed_kernels:  # one finite bound no x reaches: the boxed kernels on the plain LP's pivots
+            u = np.full(a.n, np.inf)
+            u[0] = 1e30
+            kw["upper"] = u
     A_cols = np.ascontiguousarray(A.T)
     del A
 
     def make(timing):
-        return spx.Context(A_cols, b, c, device=0, window=-1, algorithm=spx.ALGO_DUAL, timing=timing,
-                           **rule_kw(a, spx))
+        return spx.Context(A_cols, b, c, device=0, window=-1, algorithm=spx.ALGO_DUAL, timing=timing, **kw)
 
-    res = measure(make, a.k, a.warm)
+    res = measure(make, a.k, a.warm, a.rest)
     res["dual_pricing"] = a.dual_pricing
+    if a.boxed or a.boxed_kernels:
+        res["boxed"] = "lp" if a.boxed else "kernels"
     return res
 
 
@@ -106,19 +137,83 @@ def run_solve(a):
 
     out = []
     for (m, n, seed) in [(a.m, a.n, a.seed)] + [tuple(s) for s in a.solve_shape]:
-        A, b, c = dual_ref.covering(m, n, seed)
+        kw = rule_kw(a, spx)
+        if a.boxed:
+            import dual_box_ref
+
+            A, b, c, u = dual_box_ref.boxed(m, n, seed)
+            kw["upper"] = u
+        else:
+            A, b, c = dual_ref.covering(m, n, seed)
         A_cols = np.ascontiguousarray(A.T)
-        del A
+        if not a.boxed:
+            del A
         with spx.Context(A_cols, b, c, device=0, window=-1, algorithm=spx.ALGO_DUAL,
-                         refactor_every=a.refactor, **rule_kw(a, spx)) as ctx:
+                         refactor_every=a.refactor, **kw) as ctx:
             ctx.iterate(20)  # (first-launch costs)
             ctx.reset()
             t0 = time.perf_counter()
-            r = ctx.solve()
+            r = ctx.solve(a.solve_max_iter) if a.solve_max_iter > 0 else ctx.solve()
             dt = time.perf_counter() - t0
-        out.append({"m": m, "n": n, "seed": seed, "dual_pricing": a.dual_pricing, "refactor_every": a.refactor,
-                    "status": int(r.status), "pivots": r.pivots, "z": r.z, "seconds": round(dt, 4)})
+            xu = ctx.primal() if a.boxed else None
+        rec = {"m": m, "n": n, "seed": seed, "dual_pricing": a.dual_pricing, "refactor_every": a.refactor,
+               "status": int(r.status), "pivots": r.pivots, "z": r.z, "seconds": round(dt, 4)}
+        if a.boxed and int(r.status) == 1:  # the CPU certificate, from the basis and the placements alone
+            viol, dviol, zc = dual_box_ref.certificate(A, b, c, u, r.b_ixs, xu[1])
+            rec.update({"at_upper": int(xu[1].sum()), "cert_bound_violation": viol, "cert_dual_violation": dviol,
+                        "cert_z_rel": abs(zc - r.z) / abs(zc), "cert_ok": bool(viol <= 1e-9 and dviol <= 1e-7)})
+        if a.boxed and int(r.status) == 4:  # infeasible: a row whose range over the box misses its bounds
+            row, margin = dual_box_ref.farkas(A, b, u, r.b_ixs, xu[1])
+            rec.update({"farkas_row": row, "farkas_margin": margin, "cert_ok": bool(row >= 0 and margin > 1e-7)})
+        out.append(rec)
     return out
+
+
+def main_boxed(a):
+    """--boxed: parent / plain / boxed for both rules, then the solves."""
+    res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "covering_seed": a.seed,
+           "parent": "parent commit" if a.parent_root else None}
+    plan = [("primal", "primal", bool(a.parent_root), "dantzig", False)]
+    for rule in ("dantzig", "steepest"):
+        if a.parent_root:
+            plan.append((f"parent_{rule}", "dual", True, rule, False))
+        plan.append((f"plain_{rule}", "dual", False, rule, False))
+        plan.append((f"boxedk_{rule}", "dual", False, rule, "kernels"))
+        plan.append((f"boxed_{rule}", "dual", False, rule, True))
+    if a.solve:
+        plan += [("solve_steepest", "solve", False, "steepest", True), ("solve_dantzig", "solve", False, "dantzig", True)]
+    plan.append(("primal_again", "primal", bool(a.parent_root), "dantzig", False))
+    for key, role, parent, rule, boxed in plan:
+        res[key] = child(a, role, parent, rule, boxed, key)
+        sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+        sys.stderr.flush()
+    for rule in ("dantzig", "steepest"):
+        for top in ("boxed", "boxedk"):
+            bx = res[f"{top}_{rule}"]
+            for base in ("parent", "plain"):
+                if f"{base}_{rule}" in res:
+                    q = res[f"{base}_{rule}"]
+                    res[f"{rule}_{top}_over_{base}"] = {k: round(bx[k] / q[k], 3)
+                                                        for k in ("price_us", "update_us", "rest_us", "it_per_s")}
+    return res
+
+
+def child(a, role, parent, rule, boxed, key):
+    env = dict(os.environ)
+    if parent:
+        env["SPX_BENCH_ROOT"] = os.path.abspath(a.parent_root)
+    cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--m", str(a.m), "--n", str(a.n),
+           "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--dual-pricing", rule,
+           "--refactor", str(a.refactor), "--solve-max-iter", str(a.solve_max_iter), "--rest"]
+    if boxed:
+        cmd.append("--boxed-kernels" if boxed == "kernels" else "--boxed")
+    for shape in a.solve_shape:
+        cmd += ["--solve-shape"] + [str(v) for v in shape]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    if out.returncode != 0:
+        sys.stderr.write(out.stdout + out.stderr)
+        raise SystemExit(f"{key} run failed ({out.returncode})")
+    return json.loads(out.stdout.strip().splitlines()[-1])
 
 
 def main():
@@ -134,11 +229,22 @@ def main():
     ap.add_argument("--solve", action="store_true")
     ap.add_argument("--solve-shape", type=int, nargs=3, action="append", default=[], metavar=("M", "N", "SEED"))
     ap.add_argument("--refactor", type=int, default=500)
+    ap.add_argument("--boxed", action="store_true")
+    ap.add_argument("--boxed-kernels", action="store_true", help=argparse.SUPPRESS)  # (children of --boxed)
+    ap.add_argument("--rest", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--solve-max-iter", type=int, default=0)
     ap.add_argument("--role", default=None, choices=[None, "primal", "dual", "solve"])
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
         run = {"primal": run_primal, "dual": run_dual, "solve": run_solve}[a.role]
         print(json.dumps(run(a)), flush=True)
+        return
+    if a.boxed:
+        res = main_boxed(a)
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
         return
     res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "covering_seed": a.seed,
            "primal_build": "parent commit" if a.parent_root else "this build"}
@@ -151,19 +257,7 @@ def main():
         plan.append(("solve", "solve", False, a.dual_pricing))
     plan.append(("primal_again", "primal", bool(a.parent_root), "dantzig"))
     for key, role, parent, rule in plan:
-        env = dict(os.environ)
-        if parent:
-            env["SPX_BENCH_ROOT"] = os.path.abspath(a.parent_root)
-        cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--m", str(a.m), "--n", str(a.n),
-               "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--dual-pricing", rule,
-               "--refactor", str(a.refactor)]
-        for shape in a.solve_shape:
-            cmd += ["--solve-shape"] + [str(v) for v in shape]
-        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
-        if out.returncode != 0:
-            sys.stderr.write(out.stdout + out.stderr)
-            raise SystemExit(f"{key} run failed ({out.returncode})")
-        res[key] = json.loads(out.stdout.strip().splitlines()[-1])
+        res[key] = child(a, role, parent, rule, False, key)
     d, p = res["dual"], res["primal"]
     res["price_ratio_dual_over_primal"] = round(d["price_us"] / p["price_us"], 3)
     res["update_ratio_dual_over_primal"] = round(d["update_us"] / p["update_us"], 3)
