@@ -11,6 +11,7 @@ HIPFLAGS  := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-resul
 LDFLAGS   := -L$(ROCM)/lib -Wl,-rpath,$(ROCM)/lib -lrccl
 
 LIB       := $(PKG)/libsimplex.so
+OBJS      := $(addprefix $(BUILD)/,spx_kernels.o spx_reinv.o spx_tableau.o spx_loop.o spx_dual.o spx_api.o spx_api_dual.o)
 CLI       := solver
 GLPKDRV   := solver_glpk
 
@@ -36,11 +37,18 @@ $(BUILD)/spx_dual.o: $(SRC)/spx_dual.hip $(SRC)/spx_dual_step.inc $(SRC)/spx_dua
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/spx_api.o: $(SRC)/spx_api.cpp $(SRC)/spx_loop.h $(SRC)/spx_dual.h $(SRC)/spx_kernels.h $(SRC)/spx_reinv.h $(SRC)/spx_tableau.h $(SRC)/spx_device.h include/simplex.h
+# the host runtime's two units and the headers both see through spx_ctx.h
+HOST_HDRS := $(SRC)/spx_ctx.h $(SRC)/spx_loop.h $(SRC)/spx_dual.h $(SRC)/spx_kernels.h $(SRC)/spx_reinv.h $(SRC)/spx_device.h include/simplex.h
+
+$(BUILD)/spx_api.o: $(SRC)/spx_api.cpp $(HOST_HDRS) $(SRC)/spx_tableau.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(BUILD)/spx_loop.o $(BUILD)/spx_dual.o $(BUILD)/spx_api.o
+$(BUILD)/spx_api_dual.o: $(SRC)/spx_api_dual.cpp $(HOST_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ $(LDFLAGS)
 
 $(CLI): $(SRC)/solver_main.cpp $(SRC)/lp_io.cpp $(SRC)/lp_io.h $(SRC)/mps_io.cpp $(SRC)/mps_io.h include/simplex.h $(LIB)
@@ -68,13 +76,13 @@ AB        := $(PKG)/_ab
 xlib:
 	@mkdir -p $(AB)/x$(X)
 	$(HIPCC) $(HIPFLAGS) $(XFLAGS) -c $(SRC)/spx_kernels.hip -o $(AB)/x$(X)/spx_kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/x$(X)/libsimplex.so $(AB)/x$(X)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(BUILD)/spx_loop.o $(BUILD)/spx_dual.o $(BUILD)/spx_api.o $(LDFLAGS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/x$(X)/libsimplex.so $(AB)/x$(X)/spx_kernels.o $(filter-out %/spx_kernels.o,$(OBJS)) $(LDFLAGS)
 
 # persistent-loop experiment build: make xloop X=name XFLAGS="-DSPX_LOOP_FU=4"
 xloop:
 	@mkdir -p $(AB)/l$(X)
 	$(HIPCC) $(HIPFLAGS) $(XFLAGS) -c $(SRC)/spx_loop.hip -o $(AB)/l$(X)/spx_loop.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/l$(X)/libsimplex.so $(BUILD)/spx_kernels.o $(BUILD)/spx_reinv.o $(BUILD)/spx_tableau.o $(AB)/l$(X)/spx_loop.o $(BUILD)/spx_dual.o $(BUILD)/spx_api.o $(LDFLAGS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/l$(X)/libsimplex.so $(AB)/l$(X)/spx_loop.o $(filter-out %/spx_loop.o,$(OBJS)) $(LDFLAGS)
 
 abclean:
 	rm -rf $(AB)

@@ -7,9 +7,6 @@
 // pass is two kernels, termination is a device-side status word, and batches
 // of passes are replayed from one captured hipGraph with a single
 // synchronisation per batch.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -19,21 +16,19 @@
 #include <string>
 #include <vector>
 
-#include "../../include/simplex.h"
-#include "spx_device.h"
-#include "spx_dual.h"
-#include "spx_kernels.h"
-#include "spx_reinv.h"
+#include "spx_ctx.h"
 #include "spx_tableau.h"
-#include "spx_loop.h"
 
 using namespace spx;
+using namespace spx_host;
 
 namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
+}  // namespace
+
+int spx_host::fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -43,26 +38,7 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? SPX_ERR_OOM : SPX_ERR_HIP, "%s: %s (%s:%d)", \
-                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                    \
-    } while (0)
-
-#define NCCL_TRY(expr)                                                                                  \
-    do {                                                                                                \
-        ncclResult_t r_ = (expr);                                                                       \
-        if (r_ != ncclSuccess)                                                                          \
-            return fail(SPX_ERR_RCCL, "%s: %s (%s:%d)", #expr, ncclGetErrorString(r_), __FILE__, __LINE__); \
-    } while (0)
-
-#define SPX_TRY(expr)          \
-    do {                       \
-        int rc_ = (expr);      \
-        if (rc_ != SPX_OK) return rc_; \
-    } while (0)
+namespace {
 
 int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
@@ -78,132 +54,6 @@ void shard_range(int64_t m, int64_t n, int r, int G, int64_t out[4]) {
 }
 
 }  // namespace
-
-struct spx_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int cus = 256;
-    int64_t m = 0, n = 0, L = 0, ns = 0;
-    spx_opts opts{};
-    Params P{};
-    PriceCfg pcfg{};
-    UpdateCfg ucfg{};
-    int64_t max_local_cols = 0;
-
-    // device allocations
-    std::vector<void*> allocs;
-    double* A = nullptr;
-    double* b = nullptr;
-    double* c = nullptr;
-    ArgMinEntry* send = nullptr;
-    ArgMinEntry* recv = nullptr;
-
-    // pinned host mirrors
-    DevState* st_host = nullptr;
-    int64_t* limit_host = nullptr;
-
-    // multi-rank
-    ncclComm_t comm = nullptr;
-    bool comm_ready = false;
-    bool use_comm = false;  // MINLOC through RCCL: nranks > 1, or SPX_FLAG_COMM1 (one-rank test of that path)
-    bool graph_fallback = false;  // a capture with RCCL calls failed: eager passes
-    // peer mailboxes (spx_mbox_export / spx_mbox_attach): MINLOC by k_exchange
-    uint64_t* mbox = nullptr;
-    uint32_t* mbox_seq = nullptr;
-    uint64_t** mbox_peer = nullptr;  // device array of nranks mailbox pointers
-    std::vector<void*> mbox_opened;  // IPC mappings of the other ranks' mailboxes
-    bool mbox_ready = false;
-    bool mbox_fused = false;  // loop passes exchange inside k_price / k_ftran_bc (Params::mbox_fused)
-    bool bc_want = false;      // compact FTRAN operand wanted (allocated by set_slack_flags)
-    bool slack_ident = false;  // A[:, n-m:] = I (checked before setup_common)
-    bool defer_ok = false;        // loop passes defer the pricing tail into k_update (Params::defer_price)
-    bool defer_tail = false;      // loop passes defer the ratio-test tail into k_price (Params::defer_tail)
-    // steepest edge: k_ftran_bc stores k_se_part's sums (Params::se_fused) when
-    // se_fuse is set; se_chain = the last pass enqueued did, and nothing since
-    // changed B_w, U or alpha, so the next pass's k_se_fin reads them
-    bool se_fuse = false;
-    bool se_chain = false;
-    int64_t se_rows = 0;
-
-    // graph replay of `batch` passes
-    hipGraphExec_t graph_exec = nullptr;
-    hipGraph_t graph = nullptr;
-    int batch = 0;
-
-    // in-process group exchange
-    hipEvent_t ev_sent = nullptr, ev_recv = nullptr, ev_sent2 = nullptr, ev_recv2 = nullptr;
-    // row-sharded B^-1
-    int64_t mb = 0;
-    unsigned char* rs_recv = nullptr;
-
-    // per-kernel timing
-    bool timing = false;
-    std::vector<hipEvent_t> ev_price, ev_update;  // pairs (start, stop)
-    std::vector<hipEvent_t> ev_xend;              // after the MINLOC exchange
-    size_t n_price = 0, n_update = 0;
-
-    int64_t pivots = 0;
-    int32_t status = SPX_STATUS_MAX_ITER;
-    bool stepped_price = false;
-    int nw = 0;  // eta window: device st->nw as of the last readback, advanced per enqueued pass
-    // what the loop actually enqueued (spx_dispatch_stats)
-    int64_t n_eager = 0, n_graph_launch = 0, n_graph_pass = 0, n_persist_launch = 0, n_persist_pass = 0;
-    int64_t n_persist_fallback = 0;  // persistent launches found not co-resident
-    int64_t n_folds = 0;
-    int64_t n_graph_builds = 0;  // batch graphs captured + instantiated + uploaded
-    int graph_folds = 0;     // folds inside one captured batch
-    bool capturing = false;  // build_graph: passes are recorded, not run
-
-    // persistent loop kernel (spx_loop.h): window mode, one rank
-    LoopCfg lcfg{};
-    LoopArgs la{};
-    bool persist = false;
-    double loop_clock[3] = {0.0, 0.0, 0.0};  // timing: phase A / B / C microseconds (in-kernel clock)
-    int64_t loop_clock_passes = 0;
-    uint32_t loop_epoch = 0;  // persistent launches so far (LoopArgs::epoch)
-    std::vector<hipEvent_t> ev_loop;
-    std::vector<int32_t> ev_loop_passes;
-    size_t n_loop = 0;
-    std::vector<hipEvent_t> ev_fold;  // timing: the window folds between loop launches
-    size_t n_fold = 0;
-
-    // basis reinversion (spx_reinv.h): work buffers allocated on first use
-    RvParams rv{};
-    double* rv_Pa = nullptr;
-    double* rv_Pb = nullptr;
-    double* rv_Ypart = nullptr;
-    int64_t* rv_cols = nullptr;
-    int64_t* rv_pos = nullptr;
-    int64_t refactor_base = 0;  // pivots at the last reinversion (opts.refactor_every)
-    bool broken = false;        // a failed spx_set_basis left no valid basis
-
-    // dual simplex loop (spx_dual.h): buffers allocated when the context first runs it
-    int32_t algo = SPX_ALGO_PRIMAL;
-    DualBoxArgs dual{};
-    DualCfg dcfg{};
-    bool dual_checked = false;  // dual feasibility of the basis verified since it was last set
-    double* dual_e = nullptr;   // n reduced costs (the check)
-    int32_t dual_rule = SPX_DUAL_PRICING_DANTZIG;  // leaving-row rule (spx_set_dual_pricing)
-    bool dual_w_stale = true;   // steepest edge: dual.w is not the current basis's (k_dual_norms before the next pass)
-    // boxed variables 0 <= x <= u (spx_set_bounds; the dual loop only).  While boxed,
-    // P.b (= b) is the effective right-hand side b_user - sum_{j at upper} u_j A_j
-    bool boxed = false;          // some bound is finite: the passes run the boxed kernels
-    std::vector<double> ub;      // n host copy (empty: never set)
-    double* b_user = nullptr;    // L: the caller's b
-
-    template <typename T>
-    int alloc(T** p, size_t count, unsigned ext_flags = ~0u) {
-        void* d = nullptr;
-        size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        hipError_t e = ext_flags == ~0u ? hipMalloc(&d, bytes) : hipExtMallocWithFlags(&d, bytes, ext_flags);
-        if (e != hipSuccess) return fail(SPX_ERR_OOM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        allocs.push_back(d);
-        e = hipMemsetAsync(d, 0, bytes, stream);
-        if (e != hipSuccess) return fail(SPX_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-        *p = static_cast<T*>(d);
-        return SPX_OK;
-    }
-};
 
 extern "C" {
 
@@ -242,27 +92,11 @@ const char* spx_status_string(int32_t s) {
 namespace {
 
 int reset_stamps(spx_ctx* x);
-int box_sync(spx_ctx* x);
 
-bool env_on(const char* name);
-bool env_off(const char* name);
 // the compact FTRAN operand applies: eta window (no tableau, replicated
 // storage) and A[:, n-m:] = I (x->slack_ident, known before setup)
 bool bc_possible(const spx_ctx* x, const Params& P) {
     return P.win && !P.tab && !P.row_shard && x->slack_ident && !env_on("SPX_DENSE_FTRAN");
-}
-
-// The dual simplex loop's scope (spx_dual.h): one rank, explicit B^-1, Dantzig
-// pricing, no Harris pass.  Returns the combination it does not run with (for
-// the error message), or nullptr.  win: the eta window in use (0 = explicit).
-const char* dual_conflict(const spx_opts& o, int win) {
-    if (o.nranks > 1) return "on more than one rank (nranks > 1: no column or row sharding)";
-    if (o.flags & SPX_FLAG_COMM1) return "through a communicator (SPX_FLAG_COMM1)";
-    if (o.flags & SPX_FLAG_TABLEAU) return "with the window tableau (SPX_FLAG_TABLEAU)";
-    if (win > 0) return "on an eta window (it needs the explicit B^-1: window -1)";
-    if (o.ratio_test == SPX_RATIO_HARRIS) return "with the Harris ratio test";
-    if (o.pricing != SPX_PRICING_DANTZIG) return "with Devex or steepest-edge pricing";
-    return nullptr;
 }
 
 int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
@@ -334,7 +168,7 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
             return fail(SPX_ERR_ARG, "piv_tol and feas_tol must be >= 0");
     }
     x->algo = x->opts.algorithm;
-    x->dual_rule = (x->opts.flags & SPX_FLAG_DUAL_STEEPEST) ? SPX_DUAL_PRICING_STEEPEST : SPX_DUAL_PRICING_DANTZIG;
+    dual_on_create(x);
     P.ratio = rule;
     P.piv_tol = rule == SPX_RATIO_REFERENCE ? 0.0 : x->opts.piv_tol;
     P.feas_tol = rule == SPX_RATIO_HARRIS ? x->opts.feas_tol : 0.0;
@@ -662,15 +496,6 @@ int tab_rebuild(spx_ctx* x, bool slack) {
     return SPX_OK;
 }
 
-// k_price's column tickets (WM 2): each pass zeroes the other parity's
-// counter for the pass after it, so a pass that prices twice at one iteration
-// count (spx_price repeated, a basis set or rebuilt after the last pricing)
-// needs both cleared first
-int clear_tickets(spx_ctx* x) {
-    HIP_TRY(hipMemsetAsync(x->P.tickets, 0, TICKET_WORDS * sizeof(uint32_t), x->stream));
-    return SPX_OK;
-}
-
 int do_reset(spx_ctx* x) {
     const size_t mb = (size_t)(std::max<int64_t>(x->P.mloc, 1) * x->L) * sizeof(double);
     HIP_TRY(hipMemsetAsync(x->P.B0, 0, mb, x->stream));
@@ -678,10 +503,7 @@ int do_reset(spx_ctx* x) {
     for (double* v : {x->P.alpha0, x->P.alpha1, x->P.y0, x->P.y1, x->P.x_b, x->P.c_B})
         HIP_TRY(hipMemsetAsync(v, 0, (size_t)x->L * sizeof(double), x->stream));
     SPX_TRY(clear_tickets(x));
-    if (x->boxed) {  // every column back at its lower bound: b_eff = b
-        HIP_TRY(hipMemsetAsync(x->dual.at_upper, 0, (size_t)x->n, x->stream));
-        HIP_TRY(hipMemcpyAsync(x->b, x->b_user, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
-    }
+    SPX_TRY(dual_on_reset(x));
     HIP_TRY(launch_reset(x->P, x->stream));
     SPX_TRY(box_sync(x));
     HIP_TRY(launch_se_init(x->P, x->stream));  // steepest edge: gamma_j = 1 + ||A_j||^2
@@ -691,9 +513,6 @@ int do_reset(spx_ctx* x) {
         HIP_TRY(hipMemsetAsync(x->P.bc_n, 0, BC_N_WORDS * sizeof(int32_t), x->stream));
     }
     SPX_TRY(tab_rebuild(x, true));
-    if (x->dual.rec) HIP_TRY(hipMemsetAsync(x->dual.rec, 0, sizeof(DualRec), x->stream));
-    x->dual_checked = false;
-    x->dual_w_stale = true;
     HIP_TRY(hipStreamSynchronize(x->stream));
     x->pivots = 0;
     x->status = SPX_STATUS_MAX_ITER;
@@ -729,33 +548,7 @@ int fold_events(spx_ctx* x, hipEvent_t* f0, hipEvent_t* f1) {
 // One loop pass: pricing, (MINLOC exchange), fused update.
 int enqueue_pass(spx_ctx* x, bool timed) {
     hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
-    if (timed) {
-        if (x->ev_price.size() < 2 * (x->n_price + 1)) {
-            for (int k = 0; k < 2; ++k) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreate(&e));
-                x->ev_price.push_back(e);
-            }
-        }
-        if (x->ev_update.size() < 2 * (x->n_update + 1)) {
-            for (int k = 0; k < 2; ++k) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreate(&e));
-                x->ev_update.push_back(e);
-            }
-        }
-        if (x->ev_xend.size() < x->n_price + 1) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            x->ev_xend.push_back(e);
-        }
-        p0 = x->ev_price[2 * x->n_price];
-        p1 = x->ev_price[2 * x->n_price + 1];
-        u0 = x->ev_update[2 * x->n_update];
-        u1 = x->ev_update[2 * x->n_update + 1];
-        ++x->n_price;
-        ++x->n_update;
-    }
+    if (timed) SPX_TRY(pass_events(x, &p0, &p1, &u0, &u1));
     const bool fold = fold_due(x);
     if (x->capturing) x->graph_folds += fold ? 1 : 0;
     else {
@@ -858,31 +651,6 @@ int check_tickets(spx_ctx* x) {
     return SPX_OK;
 }
 
-int read_state(spx_ctx* x) {
-    HIP_TRY(hipMemcpyAsync(x->st_host, x->P.st, sizeof(DevState), hipMemcpyDeviceToHost, x->stream));
-    HIP_TRY(hipStreamSynchronize(x->stream));
-    x->pivots = x->st_host->iter;
-    x->status = x->st_host->status;  // ST_RUNNING == SPX_STATUS_MAX_ITER
-    x->nw = x->st_host->nw;
-    if (x->status == ST_WINDOW_FULL) return fail(SPX_ERR_STATE, "internal error: eta window overflow");
-    if (x->status == ST_HANDOFF_TIMEOUT) return fail(SPX_ERR_STATE, "internal error: ratio-test hand-off timed out");
-    SPX_TRY(check_tickets(x));
-    return SPX_OK;
-}
-
-// Apply the deferred y / x_b updates of the last pivot (spx_device.h) so the
-// vectors in HBM are current.  Not valid between spx_price and spx_pivot.
-int flush(spx_ctx* x) {
-    if (x->stepped_price) return fail(SPX_ERR_STATE, "state readback between spx_price and spx_pivot");
-    if (x->P.win) {  // fold every complete pivot: the explicit form the readback kernels expect
-        HIP_TRY(launch_fold(x->P, 2, x->cus, x->stream));
-        HIP_TRY(launch_tab_binv(x->P, x->stream));  // tableau without k_fold: B_w from T_w
-        x->nw = std::min(x->nw, 1);
-    }
-    HIP_TRY(launch_flush(x->P, x->stream));
-    return SPX_OK;
-}
-
 int reset_stamps(spx_ctx* x) {
     unsigned long long init[32] = {0};
     init[0] = init[4] = init[16] = init[20] = ~0ull;  // running minima
@@ -895,12 +663,6 @@ int reset_stamps(spx_ctx* x) {
 int gather_xb(spx_ctx* x) {
     if (!x->P.row_shard || !x->comm_ready) return SPX_OK;
     NCCL_TRY(ncclAllGather(x->P.x_b + x->P.r0, x->P.x_b, (size_t)x->mb, ncclFloat64, x->comm, x->stream));
-    return SPX_OK;
-}
-
-int set_limit(spx_ctx* x, int64_t limit) {
-    *x->limit_host = limit;
-    HIP_TRY(hipMemcpyAsync(&x->P.st->limit, x->limit_host, sizeof(int64_t), hipMemcpyHostToDevice, x->stream));
     return SPX_OK;
 }
 
@@ -1008,164 +770,6 @@ int iterate_persist(spx_ctx* x, int64_t k) {
     }
     if (ls.err) return fail(SPX_ERR_STATE, "persistent loop: a grid barrier timed out");
     return SPX_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Dual simplex loop (spx_dual.h)
-// ---------------------------------------------------------------------------
-// Buffers and launch geometry, on first use (spx_create with SPX_ALGO_DUAL, or
-// spx_set_algorithm).
-int dual_setup(spx_ctx* x) {
-    if (x->dual.rho) return SPX_OK;
-    if (!kernels_inplace()) return fail(SPX_ERR_STATE, "the dual simplex loop needs the in-place B^-1 build");
-    // steepest edge, k_dual_update's third operand rho: staged in LDS, or (SPX_DUAL_RHO_LDS=0) read from global memory
-    HIP_TRY(dual_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
-                         !env_off("SPX_DUAL_RHO_LDS"), &x->dcfg));
-    SPX_TRY(x->alloc(&x->dual.tau, (size_t)x->L));
-    SPX_TRY(x->alloc(&x->dual.wex, (size_t)x->L));
-    SPX_TRY(x->alloc(&x->dual.w, (size_t)x->L));
-    x->dual_w_stale = true;
-    SPX_TRY(x->alloc(&x->dual.rho, (size_t)x->L));
-    SPX_TRY(x->alloc(&x->dual.parts, (size_t)x->dcfg.price_grid));
-    SPX_TRY(x->alloc(&x->dual.rec, 1));
-    SPX_TRY(x->alloc(&x->dual_e, (size_t)x->n));
-    x->dual.price_grid = x->dcfg.price_grid;
-    x->dual.feas_tol = x->opts.feas_tol;
-    x->dual.piv_tol = x->opts.piv_tol;
-    return SPX_OK;
-}
-
-// Boxed contexts: the effective right-hand side for the current placements
-// (k_box_rhs), before anything that recomputes x_b from P.b
-int box_sync(spx_ctx* x) {
-    if (!x->boxed) return SPX_OK;
-    HIP_TRY(launch_box_rhs(x->P, x->dual, x->b_user, x->b, x->stream));
-    return SPX_OK;
-}
-
-// ... and x_b = B^-1 b_eff from it (B^-1 untouched)
-int box_recompute_xb(spx_ctx* x) {
-    SPX_TRY(box_sync(x));
-    HIP_TRY(launch_box_xb(x->P, x->dcfg, x->stream));
-    return SPX_OK;
-}
-
-// Boxed entry normalisation: every non-basic column on the side where its
-// reduced cost is dual feasible (e_j >= -eps at lower, e_j <= eps at upper;
-// |e_j| <= eps keeps its side); x_b recomputed when a placement changed (or
-// `force`).  A column with e_j < -eps and no upper bound has no such side.
-int box_normalise(spx_ctx* x, bool force) {
-    HIP_TRY(launch_reduced_costs(x->P, x->dual_e, x->stream));
-    const size_t n = (size_t)x->n;
-    std::vector<double> e(n);
-    std::vector<int32_t> pos(n);
-    std::vector<int8_t> up(n);
-    HIP_TRY(hipStreamSynchronize(x->stream));
-    HIP_TRY(hipMemcpy(e.data(), x->dual_e, n * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
-    const double eps = x->opts.eps;
-    bool changed = false;
-    for (size_t j = 0; j < n; ++j) {
-        if (pos[j] < 0) {  // basic: no placement
-            if (up[j]) { up[j] = 0; changed = true; }
-            continue;
-        }
-        if (e[j] < -eps) {
-            if (!std::isfinite(x->ub[j]))
-                return fail(SPX_ERR_STATE, "basis is not dual feasible (reduced cost %g at column %lld, eps %g): the "
-                            "column has no upper bound to sit at, and the dual simplex loop needs e_j >= -eps at a "
-                            "lower bound", e[j], (long long)j, eps);
-            if (!up[j]) { up[j] = 1; changed = true; }
-        } else if (e[j] > eps && up[j]) {
-            up[j] = 0;
-            changed = true;
-        }
-    }
-    if (changed) HIP_TRY(hipMemcpy(x->dual.at_upper, up.data(), n, hipMemcpyHostToDevice));
-    if (changed || force) SPX_TRY(box_recompute_xb(x));
-    x->dual_checked = true;
-    return SPX_OK;
-}
-
-// min over the non-basic columns of e_j = y.A_j - c_j must be >= -eps (x_b and
-// y are current: nothing of theirs is pending when the dual loop starts)
-int dual_check_feasible(spx_ctx* x) {
-    if (x->boxed) return box_normalise(x, false);
-    HIP_TRY(launch_reduced_costs(x->P, x->dual_e, x->stream));
-    std::vector<double> e((size_t)x->n);
-    std::vector<int32_t> pos((size_t)x->n);
-    HIP_TRY(hipStreamSynchronize(x->stream));
-    HIP_TRY(hipMemcpy(e.data(), x->dual_e, e.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, pos.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    double worst = INFINITY;
-    int64_t at = -1;
-    for (int64_t j = 0; j < x->n; ++j)
-        if (pos[(size_t)j] >= 0 && !(e[(size_t)j] >= worst)) {
-            worst = e[(size_t)j];
-            at = j;
-        }
-    if (at >= 0 && !(worst >= -x->opts.eps))
-        return fail(SPX_ERR_STATE, "basis is not dual feasible (reduced cost %g at column %lld, eps %g): the dual "
-                    "simplex loop needs every non-basic e_j >= -eps", worst, (long long)at, x->opts.eps);
-    x->dual_checked = true;
-    return SPX_OK;
-}
-
-// Steepest edge: the weights of the current basis from scratch where no pass
-// has kept them (k_dual_norms; between passes, nothing of the dual loop's in flight)
-int dual_refresh_weights(spx_ctx* x) {
-    if (!x->dual_w_stale) return SPX_OK;
-    HIP_TRY(launch_dual_norms(x->P, x->dual, x->dcfg, x->stream));
-    x->dual_w_stale = false;
-    return SPX_OK;
-}
-
-// One dual pass: leaving row + pivot row, ratio test, FTRAN + update.
-int enqueue_dual_pass(spx_ctx* x, hipEvent_t p0, hipEvent_t p1, hipEvent_t u0, hipEvent_t u1) {
-    const bool se = x->dual_rule == SPX_DUAL_PRICING_STEEPEST;
-    HIP_TRY(launch_dual_step(x->P, x->dual, se, x->boxed, false, x->stream));
-    HIP_TRY(launch_dual_price(x->P, x->dual, x->dcfg, x->boxed, x->stream, p0, p1));
-    if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
-    HIP_TRY(launch_dual_update(x->P, x->dual, x->dcfg, se, x->stream, u0, u1));
-    return SPX_OK;
-}
-
-// k dual passes, eager launches, one host synchronisation at the end.  Every
-// kernel returns at once when the device status is not running or the limit is
-// reached; the closing k_dual_step only commits the last pass's pivot.
-// (Replaying the passes from a captured hipGraph was measured at C3's shape:
-// 7,675 against 7,641 it/s, so the passes stay eager)
-int iterate_dual(spx_ctx* x, int64_t k) {
-    SPX_TRY(dual_setup(x));
-    if (!x->dual_checked) SPX_TRY(dual_check_feasible(x));
-    const bool se = x->dual_rule == SPX_DUAL_PRICING_STEEPEST;
-    if (se) SPX_TRY(dual_refresh_weights(x));
-    else x->dual_w_stale = true;  // Dantzig passes keep no weights
-    SPX_TRY(set_limit(x, x->pivots + k));
-    for (int64_t i = 0; i < k; ++i) {
-        hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
-        if (x->timing) {
-            while (x->ev_price.size() < 2 * (x->n_price + 1) || x->ev_update.size() < 2 * (x->n_update + 1) ||
-                   x->ev_xend.size() < x->n_price + 1) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreate(&e));
-                if (x->ev_price.size() < 2 * (x->n_price + 1)) x->ev_price.push_back(e);
-                else if (x->ev_update.size() < 2 * (x->n_update + 1)) x->ev_update.push_back(e);
-                else x->ev_xend.push_back(e);
-            }
-            p0 = x->ev_price[2 * x->n_price];
-            p1 = x->ev_price[2 * x->n_price + 1];
-            u0 = x->ev_update[2 * x->n_update];
-            u1 = x->ev_update[2 * x->n_update + 1];
-            ++x->n_price;
-            ++x->n_update;
-        }
-        SPX_TRY(enqueue_dual_pass(x, p0, p1, u0, u1));
-        ++x->n_eager;
-    }
-    HIP_TRY(launch_dual_step(x->P, x->dual, se, x->boxed, true, x->stream));  // (steepest edge: the last pivot's weights too)
-    return read_state(x);
 }
 
 int iterate_raw(spx_ctx* x, int64_t k) {
@@ -1293,7 +897,7 @@ int reinvert_basis(spx_ctx* x, const int64_t* basis) {
     }
     SPX_TRY(tab_rebuild(x, false));
     x->nw = 0;
-    x->dual_w_stale = true;
+    dual_on_reinvert(x);
     return read_state(x);
 }
 
@@ -1322,14 +926,6 @@ int reinvert_current(spx_ctx* x) {
 // Window tableau without k_fold (Params::tab_slack): needs A[:, n-m:] = I
 // exactly (the slack basis the reference's init assumes, v4:272-275).
 // A == nullptr: generated [U | I].  SPX_TAB_BW=1 keeps B_w and k_fold.
-bool env_on(const char* name) {
-    const char* env = std::getenv(name);
-    return env && env[0] == '1';
-}
-bool env_off(const char* name) {
-    const char* env = std::getenv(name);
-    return env && env[0] == '0';
-}
 bool slack_identity(const double* A, int64_t m, int64_t n) {
     if (!A) return true;
     for (int64_t i = 0; i < m; ++i) {
@@ -1414,6 +1010,91 @@ int create_tail(spx_ctx* x) {
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------
+// Helpers the dual loop's unit (spx_api_dual.cpp) calls too (spx_ctx.h)
+// ---------------------------------------------------------------------------
+namespace spx_host {
+
+bool env_on(const char* name) {
+    const char* env = std::getenv(name);
+    return env && env[0] == '1';
+}
+bool env_off(const char* name) {
+    const char* env = std::getenv(name);
+    return env && env[0] == '0';
+}
+
+// k_price's column tickets (WM 2): each pass zeroes the other parity's
+// counter for the pass after it, so a pass that prices twice at one iteration
+// count (spx_price repeated, a basis set or rebuilt after the last pricing)
+// needs both cleared first
+int clear_tickets(spx_ctx* x) {
+    HIP_TRY(hipMemsetAsync(x->P.tickets, 0, TICKET_WORDS * sizeof(uint32_t), x->stream));
+    return SPX_OK;
+}
+
+int pass_events(spx_ctx* x, hipEvent_t* p0, hipEvent_t* p1, hipEvent_t* u0, hipEvent_t* u1) {
+    auto grow = [](std::vector<hipEvent_t>& pool, size_t want) -> int {
+        while (pool.size() < want) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            pool.push_back(e);
+        }
+        return SPX_OK;
+    };
+    SPX_TRY(grow(x->ev_price, 2 * (x->n_price + 1)));
+    SPX_TRY(grow(x->ev_update, 2 * (x->n_update + 1)));
+    SPX_TRY(grow(x->ev_xend, x->n_price + 1));
+    *p0 = x->ev_price[2 * x->n_price];
+    *p1 = x->ev_price[2 * x->n_price + 1];
+    *u0 = x->ev_update[2 * x->n_update];
+    *u1 = x->ev_update[2 * x->n_update + 1];
+    ++x->n_price;
+    ++x->n_update;
+    return SPX_OK;
+}
+
+int read_state(spx_ctx* x) {
+    HIP_TRY(hipMemcpyAsync(x->st_host, x->P.st, sizeof(DevState), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    x->pivots = x->st_host->iter;
+    x->status = x->st_host->status;  // ST_RUNNING == SPX_STATUS_MAX_ITER
+    x->nw = x->st_host->nw;
+    if (x->status == ST_WINDOW_FULL) return fail(SPX_ERR_STATE, "internal error: eta window overflow");
+    if (x->status == ST_HANDOFF_TIMEOUT) return fail(SPX_ERR_STATE, "internal error: ratio-test hand-off timed out");
+    SPX_TRY(check_tickets(x));
+    return SPX_OK;
+}
+
+// Apply the deferred y / x_b updates of the last pivot (spx_device.h) so the
+// vectors in HBM are current.  Not valid between spx_price and spx_pivot.
+int flush(spx_ctx* x) {
+    if (x->stepped_price) return fail(SPX_ERR_STATE, "state readback between spx_price and spx_pivot");
+    if (x->P.win) {  // fold every complete pivot: the explicit form the readback kernels expect
+        HIP_TRY(launch_fold(x->P, 2, x->cus, x->stream));
+        HIP_TRY(launch_tab_binv(x->P, x->stream));  // tableau without k_fold: B_w from T_w
+        x->nw = std::min(x->nw, 1);
+    }
+    HIP_TRY(launch_flush(x->P, x->stream));
+    return SPX_OK;
+}
+
+int set_limit(spx_ctx* x, int64_t limit) {
+    *x->limit_host = limit;
+    HIP_TRY(hipMemcpyAsync(&x->P.st->limit, x->limit_host, sizeof(int64_t), hipMemcpyHostToDevice, x->stream));
+    return SPX_OK;
+}
+
+int set_running(spx_ctx* x) {
+    SPX_TRY(read_state(x));
+    const int32_t run = ST_RUNNING;
+    HIP_TRY(hipMemcpy(&x->P.st->status, &run, sizeof(run), hipMemcpyHostToDevice));
+    x->status = SPX_STATUS_MAX_ITER;
+    return SPX_OK;
+}
+
+}  // namespace spx_host
 
 extern "C" {
 
@@ -1628,7 +1309,7 @@ int spx_set_basis(spx_ctx* x, const int64_t* basis) {
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_basis between spx_price and spx_pivot");
     SPX_TRY(check_basis(x, basis));
     if (x->P.row_shard) return fail(SPX_ERR_STATE, "spx_set_basis needs replicated B^-1 (no row sharding)");
-    x->dual_checked = false;
+    dual_on_new_basis(x);
     // this rank's non-basic list (ascending, owned columns only) and positions
     std::vector<char> basic((size_t)x->n, 0);
     for (int64_t k = 0; k < x->m; ++k) basic[(size_t)basis[k]] = 1;
@@ -1665,63 +1346,15 @@ int spx_set_basis(spx_ctx* x, const int64_t* basis) {
     return SPX_OK;
 }
 
-// the device and host status back to running (pivot count kept)
-static int set_running(spx_ctx* x) {
-    SPX_TRY(read_state(x));
-    const int32_t run = ST_RUNNING;
-    HIP_TRY(hipMemcpy(&x->P.st->status, &run, sizeof(run), hipMemcpyHostToDevice));
-    x->status = SPX_STATUS_MAX_ITER;
-    return SPX_OK;
-}
-
 int spx_set_algorithm(spx_ctx* x, int32_t algo) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (algo != SPX_ALGO_PRIMAL && algo != SPX_ALGO_DUAL) return fail(SPX_ERR_ARG, "bad algorithm %d", algo);
     if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_algorithm between spx_price and spx_pivot");
-    if (algo == SPX_ALGO_PRIMAL && x->boxed)
-        return fail(SPX_ERR_STATE, "the primal loop does not run with finite upper bounds (spx_set_bounds): bounded "
-                    "variables are the dual simplex loop's; remove the bounds first");
-    if (algo == SPX_ALGO_DUAL) {
-        if (const char* why = dual_conflict(x->opts, x->P.win))
-            return fail(SPX_ERR_STATE, "the dual simplex loop does not run %s", why);
-        SPX_TRY(dual_setup(x));
-        // the primal loop's pending y / x_b updates applied; its pending rank-1
-        // update of B^-1 is the form the dual kernels continue from
-        SPX_TRY(flush(x));
-    } else {
-        // the dual loop leaves y and x_b current and B^-1 in the primal loop's
-        // pending form; the next pricing pass runs at a new iteration count
-        SPX_TRY(clear_tickets(x));
-    }
+    SPX_TRY(dual_switch_algorithm(x, algo));
     x->algo = algo;
     x->opts.algorithm = algo;
-    x->dual_checked = false;
-    x->dual_w_stale = true;  // (primal passes keep no dual weights)
     return set_running(x);
-}
-
-int spx_set_dual_pricing(spx_ctx* x, int32_t rule) {
-    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
-    if (rule != SPX_DUAL_PRICING_DANTZIG && rule != SPX_DUAL_PRICING_STEEPEST)
-        return fail(SPX_ERR_ARG, "bad dual pricing rule %d", rule);
-    if (rule != x->dual_rule) x->dual_w_stale = true;
-    x->dual_rule = rule;
-    return SPX_OK;
-}
-
-int spx_get_dual_weights(spx_ctx* x, double* w) {
-    if (!x || !w) return fail(SPX_ERR_ARG, "NULL argument");
-    if (x->dual_rule != SPX_DUAL_PRICING_STEEPEST)
-        return fail(SPX_ERR_STATE, "no dual pricing weights: the dual leaving-row rule is Dantzig");
-    if (x->algo != SPX_ALGO_DUAL)
-        return fail(SPX_ERR_STATE, "no dual pricing weights: the context runs the primal loop");
-    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
-    SPX_TRY(dual_setup(x));
-    SPX_TRY(dual_refresh_weights(x));
-    HIP_TRY(hipStreamSynchronize(x->stream));
-    HIP_TRY(hipMemcpy(w, x->dual.w, sizeof(double) * (size_t)x->m, hipMemcpyDeviceToHost));
-    return SPX_OK;
 }
 
 int spx_set_rhs(spx_ctx* x, const double* b) {
@@ -1733,106 +1366,9 @@ int spx_set_rhs(spx_ctx* x, const double* b) {
     if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_rhs between spx_price and spx_pivot");
     HIP_TRY(hipStreamSynchronize(x->stream));
-    // (rows m..L-1 stay 0; boxed: the caller's b, reinvert_basis forms b_eff from it)
-    HIP_TRY(hipMemcpy(x->boxed ? x->b_user : x->b, b, (size_t)x->m * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dual_rhs_target(x), b, (size_t)x->m * sizeof(double), hipMemcpyHostToDevice));
     SPX_TRY(reinvert_current(x));  // x_b = B^-1 b (and the window / tableau rebuilds)
     return set_running(x);
-}
-
-int spx_set_bounds(spx_ctx* x, const double* ub) {
-    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
-    const size_t n = (size_t)x->n;
-    bool finite = false;
-    for (size_t j = 0; ub && j < n; ++j) {
-        if (std::isnan(ub[j])) return fail(SPX_ERR_ARG, "upper bound of column %lld is NaN", (long long)j);
-        if (ub[j] < 0.0)
-            return fail(SPX_ERR_ARG, "upper bound %g of column %lld is negative (lower bounds are 0)", ub[j], (long long)j);
-        finite = finite || std::isfinite(ub[j]);
-    }
-    if (x->opts.nranks > 1 || x->P.row_shard)
-        return fail(SPX_ERR_STATE, "spx_set_bounds needs one rank and replicated B^-1 (nranks %d%s)", x->opts.nranks,
-                    x->P.row_shard ? ", row-sharded" : "");
-    if (x->algo != SPX_ALGO_DUAL)
-        return fail(SPX_ERR_STATE, "upper bounds need the dual simplex loop (SPX_ALGO_DUAL): the primal loop does not "
-                    "run bounded variables");
-    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
-    if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_bounds between spx_price and spx_pivot");
-    SPX_TRY(dual_setup(x));
-    {  // refused before anything changes: a column that would have no dual feasible side
-        HIP_TRY(launch_reduced_costs(x->P, x->dual_e, x->stream));
-        std::vector<double> e(n);
-        std::vector<int32_t> pos(n);
-        HIP_TRY(hipStreamSynchronize(x->stream));
-        HIP_TRY(hipMemcpy(e.data(), x->dual_e, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (size_t j = 0; j < n; ++j)
-            if (pos[j] >= 0 && e[j] < -x->opts.eps && !(ub && std::isfinite(ub[j])))
-                return fail(SPX_ERR_STATE, "basis is not dual feasible (reduced cost %g at column %lld, eps %g): the "
-                            "column has no upper bound to sit at, and the dual simplex loop needs e_j >= -eps at a "
-                            "lower bound", e[j], (long long)j, x->opts.eps);
-    }
-    if (!finite && !x->boxed) {  // nothing to keep: today's kernels, today's state
-        x->ub.assign(n, INFINITY);
-        return set_running(x);
-    }
-    if (!x->dual.ub) {
-        double* d_ub = nullptr;
-        SPX_TRY(x->alloc(&d_ub, n));
-        x->dual.ub = d_ub;
-        SPX_TRY(x->alloc(&x->dual.ub_B, (size_t)x->L));
-        SPX_TRY(x->alloc(&x->dual.at_upper, n));
-        SPX_TRY(x->alloc(&x->b_user, (size_t)x->L));
-    }
-    HIP_TRY(hipStreamSynchronize(x->stream));
-    if (!x->boxed) {  // P.b is still the caller's b, every column at lower
-        HIP_TRY(hipMemcpy(x->b_user, x->b, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemset(x->dual.at_upper, 0, n));
-    }
-    x->ub.assign(n, INFINITY);
-    if (ub) x->ub.assign(ub, ub + n);
-    HIP_TRY(hipMemcpy(const_cast<double*>(x->dual.ub), x->ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    // a column at an upper bound that no longer exists goes to lower
-    std::vector<int8_t> up(n);
-    HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < n; ++j)
-        if (up[j] && !std::isfinite(x->ub[j])) up[j] = 0;
-    HIP_TRY(hipMemcpy(x->dual.at_upper, up.data(), n, hipMemcpyHostToDevice));
-    x->boxed = true;  // (the normalisation and b_eff below run on the boxed state either way)
-    x->dual_checked = false;
-    SPX_TRY(set_running(x));
-    const int rc = box_normalise(x, true);
-    if (!finite && rc == SPX_OK) {  // no bound left: P.b is b again (no column at upper), the plain kernels run
-        HIP_TRY(hipStreamSynchronize(x->stream));
-        x->boxed = false;
-    }
-    return rc;
-}
-
-int spx_get_bounds(spx_ctx* x, double* ub) {
-    if (!x || !ub) return fail(SPX_ERR_ARG, "NULL argument");
-    for (size_t j = 0; j < (size_t)x->n; ++j) ub[j] = x->ub.empty() ? INFINITY : x->ub[j];
-    return SPX_OK;
-}
-
-int spx_get_primal(spx_ctx* x, double* xv, int8_t* at_upper) {
-    if (!x || !xv) return fail(SPX_ERR_ARG, "NULL argument");
-    const size_t n = (size_t)x->n, m = (size_t)x->m;
-    std::vector<double> xb(m);
-    std::vector<int64_t> bix(m);
-    SPX_TRY(spx_get_state(x, xb.data(), bix.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
-    std::vector<int8_t> up(n, 0);
-    std::vector<int32_t> pos(n, 0);
-    if (x->boxed) {
-        HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    for (size_t j = 0; j < n; ++j) {
-        up[j] = (x->boxed && up[j] && pos[j] >= 0) ? 1 : 0;
-        xv[j] = up[j] ? x->ub[j] : 0.0;
-    }
-    for (size_t i = 0; i < m; ++i) xv[(size_t)bix[i]] = xb[i];
-    if (at_upper) std::memcpy(at_upper, up.data(), n);
-    return SPX_OK;
 }
 
 int spx_iterate(spx_ctx* x, int64_t k, int32_t* status, int64_t* pivots) {
@@ -1975,21 +1511,9 @@ int spx_objective(spx_ctx* x, double* z) {
     SPX_TRY(gather_xb(x));
     HIP_TRY(launch_objective(x->P, x->stream));
     SPX_TRY(read_state(x));
-    double zv = x->st_host->z;
-    if (x->boxed) {  // + sum of c_j u_j over the non-basic columns at upper, ascending j
-        const size_t n = (size_t)x->n;
-        std::vector<double> c(n);
-        std::vector<int8_t> up(n);
-        std::vector<int32_t> pos(n);
-        HIP_TRY(hipMemcpy(c.data(), x->c, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(up.data(), x->dual.at_upper, n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        double zu = 0.0;
-        for (size_t j = 0; j < n; ++j)
-            if (up[j] && pos[j] >= 0) zu += c[j] * x->ub[j];
-        zv += zu;
-    }
-    if (z) *z = zv;
+    double zu = 0.0;  // boxed: the non-basic columns at upper
+    SPX_TRY(dual_objective_offset(x, &zu));
+    if (z) *z = x->st_host->z + zu;
     return SPX_OK;
 }
 

@@ -1,0 +1,385 @@
+// spx_api_dual.cpp — the dual simplex loop's host side (kernels: spx_dual.h):
+// its state (DualState, spx_ctx.h, with the invariants), the pass loop, the
+// feasibility check and boxed entry normalisation, the hooks through which the
+// rest of the runtime (spx_api.cpp) touches any of it, and the entry points
+// that are the dual loop's alone.
+#include <cmath>
+#include <cstring>
+
+#include "spx_ctx.h"
+
+using namespace spx;
+
+namespace spx_host {
+
+namespace {
+
+// The only writers of DualState::checked and ::w_stale.  Who calls them:
+//   event                                  checked          w_stale
+//   dual_setup (first use)                 -                true
+//   do_reset                               false            true
+//   reinvert_basis (spx_reinvert,          kept             true
+//     spx_set_rhs, refactor_every)
+//   spx_set_basis                          false            true (its reinversion)
+//   spx_set_algorithm, either way          false            true
+//   spx_set_dual_pricing, another rule     kept             true
+//   iterate_dual under Dantzig             -                true
+//   spx_set_bounds past its early return   false, then true kept
+//                                          (normalisation)
+//   dual_check_feasible / box_normalise ok true             -
+//   dual_refresh_weights                   -                false
+void feasibility_unknown(spx_ctx* x) { x->dual.checked = false; }  // the basis or its bounds were set from outside
+void feasibility_verified(spx_ctx* x) { x->dual.checked = true; }  // the check (boxed: the normalisation) passed
+void weights_lost(spx_ctx* x) { x->dual.w_stale = true; }          // B^-1 or the rule changed with no steepest pass keeping w
+void weights_recomputed(spx_ctx* x) { x->dual.w_stale = false; }   // k_dual_norms enqueued
+
+// e_j = y.A_j - c_j of every column and nb_pos (>= 0: non-basic) on the host
+int fetch_reduced_costs(spx_ctx* x, std::vector<double>& e, std::vector<int32_t>& pos) {
+    const size_t n = (size_t)x->n;
+    HIP_TRY(launch_reduced_costs(x->P, x->dual.e, x->stream));
+    e.resize(n);
+    pos.resize(n);
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(e.data(), x->dual.e, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+// a non-basic column with e_j < -eps and no upper bound has no dual feasible side
+int no_feasible_side(const spx_ctx* x, double e_j, size_t j) {
+    return fail(SPX_ERR_STATE, "basis is not dual feasible (reduced cost %g at column %lld, eps %g): the "
+                "column has no upper bound to sit at, and the dual simplex loop needs e_j >= -eps at a "
+                "lower bound", e_j, (long long)j, x->opts.eps);
+}
+
+// up[j] = 1: column j is non-basic at its upper bound (all 0 when not boxed; the
+// stream is drained).  stale: the device's at_upper marked some basic column
+// (spx_set_basis of a column that sat at upper).
+int fetch_placements(spx_ctx* x, std::vector<int8_t>& up, bool* stale = nullptr) {
+    const size_t n = (size_t)x->n;
+    up.assign(n, 0);
+    if (stale) *stale = false;
+    if (!x->dual.boxed) return SPX_OK;
+    std::vector<int32_t> pos(n);
+    HIP_TRY(hipMemcpy(up.data(), x->dual.args.at_upper, n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < n; ++j) {
+        if (stale && up[j] && pos[j] < 0) *stale = true;
+        up[j] = (up[j] && pos[j] >= 0) ? 1 : 0;
+    }
+    return SPX_OK;
+}
+
+// ... and x_b = B^-1 b_eff from the effective right-hand side (B^-1 untouched)
+int box_recompute_xb(spx_ctx* x) {
+    SPX_TRY(box_sync(x));
+    HIP_TRY(launch_box_xb(x->P, x->dual.cfg, x->stream));
+    return SPX_OK;
+}
+
+// Boxed entry normalisation: every non-basic column on the side where its
+// reduced cost is dual feasible (e_j >= -eps at lower, e_j <= eps at upper;
+// |e_j| <= eps keeps its side); x_b recomputed when a placement changed (or
+// `force`).  A column with e_j < -eps and no upper bound has no such side.
+int box_normalise(spx_ctx* x, bool force) {
+    std::vector<double> e;
+    std::vector<int32_t> pos;
+    std::vector<int8_t> up;
+    bool changed = false;
+    SPX_TRY(fetch_reduced_costs(x, e, pos));
+    SPX_TRY(fetch_placements(x, up, &changed));  // (a basic column has no placement)
+    const size_t n = (size_t)x->n;
+    const double eps = x->opts.eps;
+    for (size_t j = 0; j < n; ++j) {
+        if (pos[j] < 0) continue;
+        if (e[j] < -eps) {
+            if (!std::isfinite(x->dual.ub[j])) return no_feasible_side(x, e[j], j);
+            if (!up[j]) { up[j] = 1; changed = true; }
+        } else if (e[j] > eps && up[j]) {
+            up[j] = 0;
+            changed = true;
+        }
+    }
+    if (changed) HIP_TRY(hipMemcpy(x->dual.args.at_upper, up.data(), n, hipMemcpyHostToDevice));
+    if (changed || force) SPX_TRY(box_recompute_xb(x));
+    feasibility_verified(x);
+    return SPX_OK;
+}
+
+// min over the non-basic columns of e_j = y.A_j - c_j must be >= -eps (x_b and
+// y are current: nothing of theirs is pending when the dual loop starts)
+int dual_check_feasible(spx_ctx* x) {
+    if (x->dual.boxed) return box_normalise(x, false);
+    std::vector<double> e;
+    std::vector<int32_t> pos;
+    SPX_TRY(fetch_reduced_costs(x, e, pos));
+    double worst = INFINITY;
+    int64_t at = -1;
+    for (int64_t j = 0; j < x->n; ++j)
+        if (pos[(size_t)j] >= 0 && !(e[(size_t)j] >= worst)) {
+            worst = e[(size_t)j];
+            at = j;
+        }
+    if (at >= 0 && !(worst >= -x->opts.eps))
+        return fail(SPX_ERR_STATE, "basis is not dual feasible (reduced cost %g at column %lld, eps %g): the dual "
+                    "simplex loop needs every non-basic e_j >= -eps", worst, (long long)at, x->opts.eps);
+    feasibility_verified(x);
+    return SPX_OK;
+}
+
+// Steepest edge: the weights of the current basis from scratch where no pass
+// has kept them (k_dual_norms; between passes, nothing of the dual loop's in flight)
+int dual_refresh_weights(spx_ctx* x) {
+    if (!x->dual.w_stale) return SPX_OK;
+    HIP_TRY(launch_dual_norms(x->P, x->dual.args, x->dual.cfg, x->stream));
+    weights_recomputed(x);
+    return SPX_OK;
+}
+
+// One dual pass: leaving row + pivot row, ratio test, FTRAN + update.
+int enqueue_dual_pass(spx_ctx* x, hipEvent_t p0, hipEvent_t p1, hipEvent_t u0, hipEvent_t u1) {
+    const DualState& d = x->dual;
+    const bool se = d.rule == SPX_DUAL_PRICING_STEEPEST;
+    HIP_TRY(launch_dual_step(x->P, d.args, se, d.boxed, false, x->stream));
+    HIP_TRY(launch_dual_price(x->P, d.args, d.cfg, d.boxed, x->stream, p0, p1));
+    if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
+    HIP_TRY(launch_dual_update(x->P, d.args, d.cfg, se, x->stream, u0, u1));
+    return SPX_OK;
+}
+
+}  // namespace
+
+// The dual simplex loop's scope (spx_dual.h): one rank, explicit B^-1, Dantzig
+// pricing, no Harris pass.
+const char* dual_conflict(const spx_opts& o, int win) {
+    if (o.nranks > 1) return "on more than one rank (nranks > 1: no column or row sharding)";
+    if (o.flags & SPX_FLAG_COMM1) return "through a communicator (SPX_FLAG_COMM1)";
+    if (o.flags & SPX_FLAG_TABLEAU) return "with the window tableau (SPX_FLAG_TABLEAU)";
+    if (win > 0) return "on an eta window (it needs the explicit B^-1: window -1)";
+    if (o.ratio_test == SPX_RATIO_HARRIS) return "with the Harris ratio test";
+    if (o.pricing != SPX_PRICING_DANTZIG) return "with Devex or steepest-edge pricing";
+    return nullptr;
+}
+
+void dual_on_create(spx_ctx* x) {
+    x->dual.rule = (x->opts.flags & SPX_FLAG_DUAL_STEEPEST) ? SPX_DUAL_PRICING_STEEPEST : SPX_DUAL_PRICING_DANTZIG;
+}
+
+// (spx_create with SPX_ALGO_DUAL, spx_set_algorithm, or the first entry point that needs a buffer)
+int dual_setup(spx_ctx* x) {
+    DualState& d = x->dual;
+    if (d.args.rho) return SPX_OK;
+    if (!kernels_inplace()) return fail(SPX_ERR_STATE, "the dual simplex loop needs the in-place B^-1 build");
+    // steepest edge, k_dual_update's third operand rho: staged in LDS, or (SPX_DUAL_RHO_LDS=0) read from global memory
+    HIP_TRY(dual_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
+                         !env_off("SPX_DUAL_RHO_LDS"), &d.cfg));
+    SPX_TRY(x->alloc(&d.args.tau, (size_t)x->L));
+    SPX_TRY(x->alloc(&d.args.wex, (size_t)x->L));
+    SPX_TRY(x->alloc(&d.args.w, (size_t)x->L));
+    weights_lost(x);  // (a fresh buffer)
+    SPX_TRY(x->alloc(&d.args.rho, (size_t)x->L));
+    SPX_TRY(x->alloc(&d.args.parts, (size_t)d.cfg.price_grid));
+    SPX_TRY(x->alloc(&d.args.rec, 1));
+    SPX_TRY(x->alloc(&d.e, (size_t)x->n));
+    d.args.price_grid = d.cfg.price_grid;
+    d.args.feas_tol = x->opts.feas_tol;
+    d.args.piv_tol = x->opts.piv_tol;
+    return SPX_OK;
+}
+
+int box_sync(spx_ctx* x) {
+    if (!x->dual.boxed) return SPX_OK;
+    HIP_TRY(launch_box_rhs(x->P, x->dual.args, x->dual.b_user, x->b, x->stream));
+    return SPX_OK;
+}
+
+// k dual passes, eager launches, one host synchronisation at the end.  Every
+// kernel returns at once when the device status is not running or the limit is
+// reached; the closing k_dual_step only commits the last pass's pivot.
+// (Replaying the passes from a captured hipGraph was measured at C3's shape:
+// 7,675 against 7,641 it/s, so the passes stay eager)
+int iterate_dual(spx_ctx* x, int64_t k) {
+    SPX_TRY(dual_setup(x));
+    if (!x->dual.checked) SPX_TRY(dual_check_feasible(x));
+    const bool se = x->dual.rule == SPX_DUAL_PRICING_STEEPEST;
+    if (se) SPX_TRY(dual_refresh_weights(x));
+    else weights_lost(x);  // Dantzig passes keep no weights
+    SPX_TRY(set_limit(x, x->pivots + k));
+    for (int64_t i = 0; i < k; ++i) {
+        hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
+        if (x->timing) SPX_TRY(pass_events(x, &p0, &p1, &u0, &u1));
+        SPX_TRY(enqueue_dual_pass(x, p0, p1, u0, u1));
+        ++x->n_eager;
+    }
+    // (steepest edge: the last pivot's weights too)
+    HIP_TRY(launch_dual_step(x->P, x->dual.args, se, x->dual.boxed, true, x->stream));
+    return read_state(x);
+}
+
+int dual_on_reset(spx_ctx* x) {
+    DualState& d = x->dual;
+    if (d.boxed) {  // every column back at its lower bound: b_eff = b
+        HIP_TRY(hipMemsetAsync(d.args.at_upper, 0, (size_t)x->n, x->stream));
+        HIP_TRY(hipMemcpyAsync(x->b, d.b_user, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
+    }
+    if (d.args.rec) HIP_TRY(hipMemsetAsync(d.args.rec, 0, sizeof(DualRec), x->stream));
+    feasibility_unknown(x);
+    weights_lost(x);
+    return SPX_OK;
+}
+
+void dual_on_reinvert(spx_ctx* x) { weights_lost(x); }
+
+void dual_on_new_basis(spx_ctx* x) { feasibility_unknown(x); }
+
+// (rows m..L-1 stay 0; boxed: the caller's b, reinvert_basis forms b_eff from it)
+double* dual_rhs_target(spx_ctx* x) { return x->dual.boxed ? x->dual.b_user : x->b; }
+
+int dual_switch_algorithm(spx_ctx* x, int32_t algo) {
+    if (algo == SPX_ALGO_PRIMAL && x->dual.boxed)
+        return fail(SPX_ERR_STATE, "the primal loop does not run with finite upper bounds (spx_set_bounds): bounded "
+                    "variables are the dual simplex loop's; remove the bounds first");
+    if (algo == SPX_ALGO_DUAL) {
+        if (const char* why = dual_conflict(x->opts, x->P.win))
+            return fail(SPX_ERR_STATE, "the dual simplex loop does not run %s", why);
+        SPX_TRY(dual_setup(x));
+        // the primal loop's pending y / x_b updates applied; its pending rank-1
+        // update of B^-1 is the form the dual kernels continue from
+        SPX_TRY(flush(x));
+    } else {
+        // the dual loop leaves y and x_b current and B^-1 in the primal loop's
+        // pending form; the next pricing pass runs at a new iteration count
+        SPX_TRY(clear_tickets(x));
+    }
+    feasibility_unknown(x);
+    weights_lost(x);  // (primal passes keep no dual weights)
+    return SPX_OK;
+}
+
+int dual_objective_offset(spx_ctx* x, double* zu) {
+    *zu = 0.0;
+    if (!x->dual.boxed) return SPX_OK;
+    const size_t n = (size_t)x->n;
+    std::vector<double> c(n);
+    std::vector<int8_t> up;
+    HIP_TRY(hipMemcpy(c.data(), x->c, n * sizeof(double), hipMemcpyDeviceToHost));
+    SPX_TRY(fetch_placements(x, up));
+    for (size_t j = 0; j < n; ++j)  // ascending j
+        if (up[j]) *zu += c[j] * x->dual.ub[j];
+    return SPX_OK;
+}
+
+}  // namespace spx_host
+
+using namespace spx_host;
+
+extern "C" {
+
+int spx_set_dual_pricing(spx_ctx* x, int32_t rule) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (rule != SPX_DUAL_PRICING_DANTZIG && rule != SPX_DUAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_ARG, "bad dual pricing rule %d", rule);
+    if (rule != x->dual.rule) weights_lost(x);
+    x->dual.rule = rule;
+    return SPX_OK;
+}
+
+int spx_get_dual_weights(spx_ctx* x, double* w) {
+    if (!x || !w) return fail(SPX_ERR_ARG, "NULL argument");
+    if (x->dual.rule != SPX_DUAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "no dual pricing weights: the dual leaving-row rule is Dantzig");
+    if (x->algo != SPX_ALGO_DUAL)
+        return fail(SPX_ERR_STATE, "no dual pricing weights: the context runs the primal loop");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    SPX_TRY(dual_setup(x));
+    SPX_TRY(dual_refresh_weights(x));
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(w, x->dual.args.w, sizeof(double) * (size_t)x->m, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_set_bounds(spx_ctx* x, const double* ub) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    const size_t n = (size_t)x->n;
+    bool finite = false;
+    for (size_t j = 0; ub && j < n; ++j) {
+        if (std::isnan(ub[j])) return fail(SPX_ERR_ARG, "upper bound of column %lld is NaN", (long long)j);
+        if (ub[j] < 0.0)
+            return fail(SPX_ERR_ARG, "upper bound %g of column %lld is negative (lower bounds are 0)", ub[j], (long long)j);
+        finite = finite || std::isfinite(ub[j]);
+    }
+    if (x->opts.nranks > 1 || x->P.row_shard)
+        return fail(SPX_ERR_STATE, "spx_set_bounds needs one rank and replicated B^-1 (nranks %d%s)", x->opts.nranks,
+                    x->P.row_shard ? ", row-sharded" : "");
+    if (x->algo != SPX_ALGO_DUAL)
+        return fail(SPX_ERR_STATE, "upper bounds need the dual simplex loop (SPX_ALGO_DUAL): the primal loop does not "
+                    "run bounded variables");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_bounds between spx_price and spx_pivot");
+    SPX_TRY(dual_setup(x));
+    DualState& d = x->dual;
+    {  // refused before anything changes: a column that would have no dual feasible side
+        std::vector<double> e;
+        std::vector<int32_t> pos;
+        SPX_TRY(fetch_reduced_costs(x, e, pos));
+        for (size_t j = 0; j < n; ++j)
+            if (pos[j] >= 0 && e[j] < -x->opts.eps && !(ub && std::isfinite(ub[j]))) return no_feasible_side(x, e[j], j);
+    }
+    if (!finite && !d.boxed) {  // nothing to keep: today's kernels, today's state
+        d.ub.assign(n, INFINITY);
+        return set_running(x);
+    }
+    if (!d.args.ub) {
+        double* d_ub = nullptr;
+        SPX_TRY(x->alloc(&d_ub, n));
+        d.args.ub = d_ub;
+        SPX_TRY(x->alloc(&d.args.ub_B, (size_t)x->L));
+        SPX_TRY(x->alloc(&d.args.at_upper, n));
+        SPX_TRY(x->alloc(&d.b_user, (size_t)x->L));
+    }
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    if (!d.boxed) {  // P.b is still the caller's b, every column at lower
+        HIP_TRY(hipMemcpy(d.b_user, x->b, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemset(d.args.at_upper, 0, n));
+    }
+    d.ub.assign(n, INFINITY);
+    if (ub) d.ub.assign(ub, ub + n);
+    HIP_TRY(hipMemcpy(const_cast<double*>(d.args.ub), d.ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    // a column at an upper bound that no longer exists goes to lower
+    std::vector<int8_t> up(n);
+    HIP_TRY(hipMemcpy(up.data(), d.args.at_upper, n, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < n; ++j)
+        if (up[j] && !std::isfinite(d.ub[j])) up[j] = 0;
+    HIP_TRY(hipMemcpy(d.args.at_upper, up.data(), n, hipMemcpyHostToDevice));
+    d.boxed = true;  // (the normalisation and b_eff below run on the boxed state either way)
+    feasibility_unknown(x);
+    SPX_TRY(set_running(x));
+    const int rc = box_normalise(x, true);
+    if (!finite && rc == SPX_OK) {  // no bound left: P.b is b again (no column at upper), the plain kernels run
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        d.boxed = false;
+    }
+    return rc;
+}
+
+int spx_get_bounds(spx_ctx* x, double* ub) {
+    if (!x || !ub) return fail(SPX_ERR_ARG, "NULL argument");
+    for (size_t j = 0; j < (size_t)x->n; ++j) ub[j] = x->dual.ub.empty() ? INFINITY : x->dual.ub[j];
+    return SPX_OK;
+}
+
+int spx_get_primal(spx_ctx* x, double* xv, int8_t* at_upper) {
+    if (!x || !xv) return fail(SPX_ERR_ARG, "NULL argument");
+    const size_t n = (size_t)x->n, m = (size_t)x->m;
+    std::vector<double> xb(m);
+    std::vector<int64_t> bix(m);
+    SPX_TRY(spx_get_state(x, xb.data(), bix.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+    std::vector<int8_t> up;
+    SPX_TRY(fetch_placements(x, up));
+    for (size_t j = 0; j < n; ++j) xv[j] = up[j] ? x->dual.ub[j] : 0.0;
+    for (size_t i = 0; i < m; ++i) xv[(size_t)bix[i]] = xb[i];
+    if (at_upper) std::memcpy(at_upper, up.data(), n);
+    return SPX_OK;
+}
+
+}  // extern "C"

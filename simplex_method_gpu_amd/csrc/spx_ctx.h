@@ -1,0 +1,230 @@
+// spx_ctx.h — what the host translation units behind include/simplex.h share
+// (spx_api.cpp, spx_api_dual.cpp): the context, the error plumbing and the few
+// helpers one unit calls in the other.  Internal: not installed, not part of
+// the ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/simplex.h"
+#include "spx_device.h"
+#include "spx_dual.h"
+#include "spx_kernels.h"
+#include "spx_loop.h"
+#include "spx_reinv.h"
+
+namespace spx_host {
+
+// records the message spx_last_error returns (thread-local) and returns `code`
+int fail(int code, const char* fmt, ...);
+
+}  // namespace spx_host
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return spx_host::fail(e_ == hipErrorOutOfMemory ? SPX_ERR_OOM : SPX_ERR_HIP, "%s: %s (%s:%d)", \
+                                  #expr, hipGetErrorString(e_), __FILE__, __LINE__);          \
+    } while (0)
+
+#define NCCL_TRY(expr)                                                                                  \
+    do {                                                                                                \
+        ncclResult_t r_ = (expr);                                                                       \
+        if (r_ != ncclSuccess)                                                                          \
+            return spx_host::fail(SPX_ERR_RCCL, "%s: %s (%s:%d)", #expr, ncclGetErrorString(r_), __FILE__, __LINE__); \
+    } while (0)
+
+#define SPX_TRY(expr)          \
+    do {                       \
+        int rc_ = (expr);      \
+        if (rc_ != SPX_OK) return rc_; \
+    } while (0)
+
+// The dual simplex loop's host state (spx_dual.h; everything that reads or
+// writes it is in spx_api_dual.cpp, the rest of the runtime goes through the
+// hooks at the end of this file).  Invariants, between any two API calls:
+//  - args.rho != nullptr  <=>  dual_setup ran: every buffer of DualSeArgs, cfg
+//    and e are allocated.  args.ub / ub_B / at_upper and b_user are allocated by
+//    the first spx_set_bounds with a finite bound, and never freed.
+//  - checked: the current basis passed the dual feasibility check (boxed: the
+//    entry normalisation) since it was last set from outside the dual loop.
+//    Cleared by reset, spx_set_basis, spx_set_algorithm and spx_set_bounds;
+//    reinversion keeps the basis and so keeps it.
+//  - the steepest-edge weights args.w are those of the current B^-1, or w_stale
+//    is set (k_dual_norms runs before the next steepest pass or readback).
+//    Only steepest-edge dual passes keep them: everything else that changes
+//    B^-1 or the rule sets w_stale.
+//  - boxed  <=>  some upper bound is finite.  Then the passes run the boxed
+//    kernels, b_user holds the caller's right-hand side and Params::b (= ctx b)
+//    is the effective one, b_user - sum_{j non-basic at upper} u_j A_j.  Not
+//    boxed: Params::b is the caller's b and no column is at upper.
+//  - ub is empty (never set: all +inf) or holds n bounds, the host copy of args.ub.
+struct DualState {
+    spx::DualBoxArgs args{};
+    spx::DualCfg cfg{};
+    double* e = nullptr;  // n reduced costs (the feasibility check)
+    int32_t rule = SPX_DUAL_PRICING_DANTZIG;  // leaving-row rule (spx_set_dual_pricing)
+    bool checked = false;
+    bool w_stale = true;
+    bool boxed = false;
+    std::vector<double> ub;
+    double* b_user = nullptr;  // L
+};
+
+struct spx_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int cus = 256;
+    int64_t m = 0, n = 0, L = 0, ns = 0;
+    spx_opts opts{};
+    spx::Params P{};
+    spx::PriceCfg pcfg{};
+    spx::UpdateCfg ucfg{};
+    int64_t max_local_cols = 0;
+
+    // device allocations
+    std::vector<void*> allocs;
+    double* A = nullptr;
+    double* b = nullptr;
+    double* c = nullptr;
+    spx::ArgMinEntry* send = nullptr;
+    spx::ArgMinEntry* recv = nullptr;
+
+    // pinned host mirrors
+    spx::DevState* st_host = nullptr;
+    int64_t* limit_host = nullptr;
+
+    // multi-rank
+    ncclComm_t comm = nullptr;
+    bool comm_ready = false;
+    bool use_comm = false;  // MINLOC through RCCL: nranks > 1, or SPX_FLAG_COMM1 (one-rank test of that path)
+    bool graph_fallback = false;  // a capture with RCCL calls failed: eager passes
+    // peer mailboxes (spx_mbox_export / spx_mbox_attach): MINLOC by k_exchange
+    uint64_t* mbox = nullptr;
+    uint32_t* mbox_seq = nullptr;
+    uint64_t** mbox_peer = nullptr;  // device array of nranks mailbox pointers
+    std::vector<void*> mbox_opened;  // IPC mappings of the other ranks' mailboxes
+    bool mbox_ready = false;
+    bool mbox_fused = false;  // loop passes exchange inside k_price / k_ftran_bc (Params::mbox_fused)
+    bool bc_want = false;      // compact FTRAN operand wanted (allocated by set_slack_flags)
+    bool slack_ident = false;  // A[:, n-m:] = I (checked before setup_common)
+    bool defer_ok = false;        // loop passes defer the pricing tail into k_update (Params::defer_price)
+    bool defer_tail = false;      // loop passes defer the ratio-test tail into k_price (Params::defer_tail)
+    // steepest edge: k_ftran_bc stores k_se_part's sums (Params::se_fused) when
+    // se_fuse is set; se_chain = the last pass enqueued did, and nothing since
+    // changed B_w, U or alpha, so the next pass's k_se_fin reads them
+    bool se_fuse = false;
+    bool se_chain = false;
+    int64_t se_rows = 0;
+
+    // graph replay of `batch` passes
+    hipGraphExec_t graph_exec = nullptr;
+    hipGraph_t graph = nullptr;
+    int batch = 0;
+
+    // in-process group exchange
+    hipEvent_t ev_sent = nullptr, ev_recv = nullptr, ev_sent2 = nullptr, ev_recv2 = nullptr;
+    // row-sharded B^-1
+    int64_t mb = 0;
+    unsigned char* rs_recv = nullptr;
+
+    // per-kernel timing
+    bool timing = false;
+    std::vector<hipEvent_t> ev_price, ev_update;  // pairs (start, stop)
+    std::vector<hipEvent_t> ev_xend;              // after the MINLOC exchange
+    size_t n_price = 0, n_update = 0;
+
+    int64_t pivots = 0;
+    int32_t status = SPX_STATUS_MAX_ITER;
+    bool stepped_price = false;
+    int nw = 0;  // eta window: device st->nw as of the last readback, advanced per enqueued pass
+    // what the loop actually enqueued (spx_dispatch_stats)
+    int64_t n_eager = 0, n_graph_launch = 0, n_graph_pass = 0, n_persist_launch = 0, n_persist_pass = 0;
+    int64_t n_persist_fallback = 0;  // persistent launches found not co-resident
+    int64_t n_folds = 0;
+    int64_t n_graph_builds = 0;  // batch graphs captured + instantiated + uploaded
+    int graph_folds = 0;     // folds inside one captured batch
+    bool capturing = false;  // build_graph: passes are recorded, not run
+
+    // persistent loop kernel (spx_loop.h): window mode, one rank
+    spx::LoopCfg lcfg{};
+    spx::LoopArgs la{};
+    bool persist = false;
+    double loop_clock[3] = {0.0, 0.0, 0.0};  // timing: phase A / B / C microseconds (in-kernel clock)
+    int64_t loop_clock_passes = 0;
+    uint32_t loop_epoch = 0;  // persistent launches so far (LoopArgs::epoch)
+    std::vector<hipEvent_t> ev_loop;
+    std::vector<int32_t> ev_loop_passes;
+    size_t n_loop = 0;
+    std::vector<hipEvent_t> ev_fold;  // timing: the window folds between loop launches
+    size_t n_fold = 0;
+
+    // basis reinversion (spx_reinv.h): work buffers allocated on first use
+    spx::RvParams rv{};
+    double* rv_Pa = nullptr;
+    double* rv_Pb = nullptr;
+    double* rv_Ypart = nullptr;
+    int64_t* rv_cols = nullptr;
+    int64_t* rv_pos = nullptr;
+    int64_t refactor_base = 0;  // pivots at the last reinversion (opts.refactor_every)
+    bool broken = false;        // a failed spx_set_basis left no valid basis
+
+    int32_t algo = SPX_ALGO_PRIMAL;  // the loop spx_iterate runs
+    DualState dual;                  // the dual one's state (spx_api_dual.cpp)
+
+    template <typename T>
+    int alloc(T** p, size_t count, unsigned ext_flags = ~0u) {
+        void* d = nullptr;
+        size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        hipError_t e = ext_flags == ~0u ? hipMalloc(&d, bytes) : hipExtMallocWithFlags(&d, bytes, ext_flags);
+        if (e != hipSuccess)
+            return spx_host::fail(SPX_ERR_OOM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        allocs.push_back(d);
+        e = hipMemsetAsync(d, 0, bytes, stream);
+        if (e != hipSuccess) return spx_host::fail(SPX_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+        *p = static_cast<T*>(d);
+        return SPX_OK;
+    }
+};
+
+namespace spx_host {
+
+// spx_api.cpp, called by the dual loop
+bool env_on(const char* name);   // the variable is set and starts with '1'
+bool env_off(const char* name);  // ... with '0'
+int clear_tickets(spx_ctx* x);
+int read_state(spx_ctx* x);  // the device state to the host: the one synchronisation of an iterate call
+int flush(spx_ctx* x);
+int set_limit(spx_ctx* x, int64_t limit);
+int set_running(spx_ctx* x);  // the device and host status back to running (pivot count kept)
+// timing: the next price / update event pairs of a pass; its exchange-end
+// event is ev_xend[n_price - 1] afterwards
+int pass_events(spx_ctx* x, hipEvent_t* p0, hipEvent_t* p1, hipEvent_t* u0, hipEvent_t* u1);
+
+// spx_api_dual.cpp: all the rest of the runtime knows of the dual loop
+// the combination of options the dual loop does not run with (for the error
+// message), or nullptr.  win: the eta window in use (0 = explicit)
+const char* dual_conflict(const spx_opts& o, int win);
+void dual_on_create(spx_ctx* x);  // the leaving-row rule opts.flags asks for
+int dual_setup(spx_ctx* x);       // buffers and launch geometry, on first use
+int iterate_dual(spx_ctx* x, int64_t k);
+// boxed: Params::b = the effective right-hand side of the current placements,
+// before anything that recomputes x_b from it (not boxed: nothing)
+int box_sync(spx_ctx* x);
+// do_reset, before launch_reset: boxed, every column back at lower; no pass
+// in flight, nothing checked, no weights
+int dual_on_reset(spx_ctx* x);
+void dual_on_reinvert(spx_ctx* x);   // B^-1 rebuilt for the same or a new basis: no weights
+void dual_on_new_basis(spx_ctx* x);  // spx_set_basis: nothing checked
+double* dual_rhs_target(spx_ctx* x);  // where spx_set_rhs writes the caller's b
+// spx_set_algorithm's refusals and state changes around the switch to `algo`
+int dual_switch_algorithm(spx_ctx* x, int32_t algo);
+// boxed: zu = sum of c_j u_j over the non-basic columns at upper; else 0
+int dual_objective_offset(spx_ctx* x, double* zu);
+
+}  // namespace spx_host
