@@ -1,6 +1,9 @@
 # Build: libsimplex.so (gfx950 kernels + C-ABI), the ./solver CLI, and the
 # CPU oracle (test infrastructure).  `make -j8`.  Outputs stay in-tree (git-ignored,
 # shipped to the GPU box with the snapshot).
+# UNITS is the one list of translation units (.hip kernel units and the .cpp host
+# runtime, told apart by the source that exists); the compiler writes each
+# unit's header dependencies ($(BUILD)/*.d).
 ROCM      ?= /opt/rocm
 HIPCC     ?= $(ROCM)/bin/hipcc
 ARCH      ?= gfx950
@@ -11,42 +14,24 @@ HIPFLAGS  := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-resul
 LDFLAGS   := -L$(ROCM)/lib -Wl,-rpath,$(ROCM)/lib -lrccl
 
 LIB       := $(PKG)/libsimplex.so
-OBJS      := $(addprefix $(BUILD)/,spx_kernels.o spx_reinv.o spx_tableau.o spx_loop.o spx_dual.o spx_api.o spx_api_dual.o)
+# the primal loop's kernel units (make xlib rebuilds these)
+KUNITS    := spx_kernels spx_price spx_update spx_foldk
+UNITS     := $(KUNITS) spx_reinv spx_tableau spx_loop spx_dual spx_api spx_api_dual
+OBJS      := $(UNITS:%=$(BUILD)/%.o)
 CLI       := solver
 GLPKDRV   := solver_glpk
 
 all: $(LIB) $(CLI) $(GLPKDRV) oracle
 
-$(BUILD)/spx_kernels.o: $(SRC)/spx_kernels.hip $(SRC)/spx_kernels.h $(SRC)/spx_tableau.h $(SRC)/spx_tabdev.h $(SRC)/spx_device.h $(SRC)/spx_fold.h $(SRC)/spx_common.h
+$(BUILD)/%.o: $(SRC)/%.hip
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
 
-$(BUILD)/spx_reinv.o: $(SRC)/spx_reinv.hip $(SRC)/spx_reinv.h $(SRC)/spx_device.h $(SRC)/spx_fold.h
+$(BUILD)/%.o: $(SRC)/%.cpp
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
 
-$(BUILD)/spx_tableau.o: $(SRC)/spx_tableau.hip $(SRC)/spx_tableau.h $(SRC)/spx_tabdev.h $(SRC)/spx_grid.h $(SRC)/spx_loop.h $(SRC)/spx_device.h $(SRC)/spx_fold.h $(SRC)/spx_common.h
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/spx_loop.o: $(SRC)/spx_loop.hip $(SRC)/spx_loop.h $(SRC)/spx_grid.h $(SRC)/spx_device.h $(SRC)/spx_common.h
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/spx_dual.o: $(SRC)/spx_dual.hip $(SRC)/spx_dual_step.inc $(SRC)/spx_dual.h $(SRC)/spx_device.h $(SRC)/spx_common.h
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# the host runtime's two units and the headers both see through spx_ctx.h
-HOST_HDRS := $(SRC)/spx_ctx.h $(SRC)/spx_loop.h $(SRC)/spx_dual.h $(SRC)/spx_kernels.h $(SRC)/spx_reinv.h $(SRC)/spx_device.h include/simplex.h
-
-$(BUILD)/spx_api.o: $(SRC)/spx_api.cpp $(HOST_HDRS) $(SRC)/spx_tableau.h
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/spx_api_dual.o: $(SRC)/spx_api_dual.cpp $(HOST_HDRS)
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+-include $(OBJS:.o=.d)
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ $(LDFLAGS)
@@ -73,10 +58,14 @@ clean:
 AB        := $(PKG)/_ab
 
 # generic experiment build: make xlib X=name XFLAGS="-DSPX_PRICE_DEEP=0"
-xlib:
-	@mkdir -p $(AB)/x$(X)
-	$(HIPCC) $(HIPFLAGS) $(XFLAGS) -c $(SRC)/spx_kernels.hip -o $(AB)/x$(X)/spx_kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/x$(X)/libsimplex.so $(AB)/x$(X)/spx_kernels.o $(filter-out %/spx_kernels.o,$(OBJS)) $(LDFLAGS)
+# (XFLAGS reach every kernel unit of the primal loop; the rest link as built)
+XOBJS     := $(KUNITS:%=$(AB)/x$(X)/%.o)
+XREST     := $(filter-out $(KUNITS:%=$(BUILD)/%.o),$(OBJS))
+$(AB)/x$(X)/%.o: $(SRC)/%.hip FORCE
+	@mkdir -p $(@D)
+	$(HIPCC) $(HIPFLAGS) $(XFLAGS) -c $< -o $@
+xlib: $(XOBJS) $(XREST)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(AB)/x$(X)/libsimplex.so $(XOBJS) $(XREST) $(LDFLAGS)
 
 # persistent-loop experiment build: make xloop X=name XFLAGS="-DSPX_LOOP_FU=4"
 xloop:
@@ -87,4 +76,5 @@ xloop:
 abclean:
 	rm -rf $(AB)
 
-.PHONY: xlib xloop abclean
+FORCE:
+.PHONY: xlib xloop abclean FORCE

@@ -178,7 +178,7 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
     P.mloc = P.row_shard ? std::min<int64_t>(m, P.r0 + x->mb) - P.r0 : m;
     if (P.row_shard && P.mloc <= 0) return fail(SPX_ERR_ARG, "row sharding needs m >= nranks rows per rank");
     SPX_TRY(x->alloc(&P.B0, (size_t)(std::max<int64_t>(P.mloc, 1) * L)));
-    if (kernels_inplace() && !P.row_shard)
+    if (!P.row_shard)  // one buffer, updated in place; row shards ping-pong
         P.B1 = P.B0;
     else
         SPX_TRY(x->alloc(&P.B1, (size_t)(std::max<int64_t>(P.mloc, 1) * L)));

@@ -169,7 +169,6 @@ void dual_on_create(spx_ctx* x) {
 int dual_setup(spx_ctx* x) {
     DualState& d = x->dual;
     if (d.args.rho) return SPX_OK;
-    if (!kernels_inplace()) return fail(SPX_ERR_STATE, "the dual simplex loop needs the in-place B^-1 build");
     // steepest edge, k_dual_update's third operand rho: staged in LDS, or (SPX_DUAL_RHO_LDS=0) read from global memory
     HIP_TRY(dual_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
                          !env_off("SPX_DUAL_RHO_LDS"), &d.cfg));

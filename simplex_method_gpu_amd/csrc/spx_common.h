@@ -1,4 +1,4 @@
-// spx_common.h — device helpers shared by the loop kernels (spx_kernels.hip)
+// spx_common.h — device helpers shared by the loop kernels (spx_kernels.h)
 // and the persistent loop kernel (spx_loop.hip): vector types, cache-policy
 // loads/stores, wave reductions, agent-scope hand-off primitives and the
 // pieces of the deferred pivot (one definition, so every consumer produces

@@ -1,13 +1,13 @@
 // spx_device.h — device-state layout and kernel parameter block shared by the
-// gfx950 kernels (spx_kernels.hip) and the host runtime (spx_api.cpp).
+// gfx950 kernels (the units spx_kernels.h lists) and the host runtime (spx_api.cpp).
 //
 // HBM layout (all fp64, L = round_up(m, 128) doubles = whole 1 KiB lines):
 //   A      L x n, column-major (column j at A + j*L; rows m..L-1 zero).  The
 //          reference's D = [-c; A] copy (v4:248,278-279) is not built: pricing
 //          reads A and c directly.
 //   B      m x L, ROW-major B^-1 S (the reference is column-major, v4:59-60),
-//          updated in place by k_update (SPX_INPLACE=1, default; the ping-pong
-//          variant B0/B1 is a build option kept for A/B measurements).
+//          updated in place by k_update (one buffer, B0 = B1; only row
+//          sharding keeps its rows in ping-pong buffers B0 / B1).
 //   rbuf   L: the pending pivot row, staged by k_price (k_update overwrites
 //          row q while every wave still needs it).
 //

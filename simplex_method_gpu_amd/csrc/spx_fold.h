@@ -1,5 +1,5 @@
 // spx_fold.h — device helpers shared by the eta-window fold (k_fold,
-// spx_kernels.hip) and the basis reinversion (spx_reinv.hip): a rank-nf
+// spx_foldk.hip) and the basis reinversion (spx_reinv.hip): a rank-nf
 // update B += U R of a 64-column stripe of a row-major matrix with fp64 MFMA
 // tiles (v_mfma_f64_16x16x4f64), R rebuilt from base rows and coefficients.
 //

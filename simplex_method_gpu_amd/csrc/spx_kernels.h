@@ -1,4 +1,42 @@
-// spx_kernels.h — host-side launchers for the gfx950 kernels (spx_kernels.hip).
+// spx_kernels.h — host-side launchers for the gfx950 kernels of the dense
+// revised-simplex hot loop: the only interface of the kernel units below to
+// the host code.
+//
+// One loop pass is two launches (SURVEY.md §7 design notes):
+//   k_price   stages y in LDS (applying the last pivot's y update on the fly),
+//             then e_j = y.A_j - c_j over this rank's non-basic columns fused
+//             with the entering argmin (v4:288-302).  One wave per column, A
+//             read with 16-byte non-temporal loads, wave shuffle + LDS argmin,
+//             last-workgroup-done fan-in.
+//   k_update  applies the pending rank-1 update B^-1 += E r^T (v4:331-333)
+//             while streaming B^-1 once, and in the same pass computes FTRAN
+//             alpha = B^-1_new A_p (v4:307-308), the last pivot's x_b update
+//             (v4:347-348) for the rows it owns, compute_theta and the leaving
+//             argmin (v4:199-208,324); the last workgroup then finds q, the
+//             y-update scalar (v4:352-355) and does the basis bookkeeping
+//             (v4:339-342).
+// Host synchronisation per pass: none.  Termination (optimum / unbounded /
+// iteration limit) is a device-side status word every kernel checks first.
+// The deferred pivot state is described in spx_device.h.
+//
+// Cross-workgroup hand-offs inside a launch (partials, alpha) use agent-scope
+// relaxed atomic stores/loads (global_* sc1: L1 bypass) drained with
+// s_waitcnt vmcnt(0) before a workgroup barrier and one agent-scope ticket
+// add per workgroup (MI355X_MICROARCH.md, Valid forms, first table row), on
+// sharded counters (arrive_last, spx_common.h).
+// Everything is deterministic: fixed reduction orders, no float atomics, so
+// results are bit-identical for any grid / block size and any shard count.
+//
+// The kernel units, one family each with its launchers:
+//   spx_price.hip    k_price and the pricing-only build switches
+//   spx_update.hip   k_update, k_ftran_bc (compact operand), k_tab_update
+//                    (window tableau) and the one-workgroup tail kernels
+//   spx_foldk.hip    the eta window's folds (k_fold, k_cfold) and the compact
+//                    operand's list and gather
+//   spx_kernels.hip  off the two launches: flush and readbacks, setup, the
+//                    mailbox exchange, steepest edge's preparation
+//   spx_handoff.h    device helpers k_price and the FTRAN kernels share: the
+//                    partials, the pivot tail, mailbox records, phase stamps
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,7 +63,6 @@ struct UpdateCfg {
     int mark;      // diagnostic: k_mark before the launch (SPX_DIAG_MARK=1, stamps only)
 };
 
-bool kernels_inplace();  // B^-1 updated in place (one buffer) or ping-pong
 hipError_t price_prepare(const PriceCfg& c, int* blocks_per_cu);
 hipError_t launch_price(const Params& P, const PriceCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_update(const Params& P, const UpdateCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);

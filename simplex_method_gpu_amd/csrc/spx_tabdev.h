@@ -1,6 +1,6 @@
 // spx_tabdev.h — per-lane arithmetic of the window tableau,
 // shared by the two-kernel passes (k_price WM 3 and k_tab_update,
-// spx_kernels.hip) and the persistent tableau loop (k_tab_loop,
+// spx_price.hip / spx_update.hip) and the persistent tableau loop (k_tab_loop,
 // spx_tableau.hip), so every path produces the same bits for a column or a
 // row.  One lane owns one column (pricing) or one row (FTRAN); the window
 // sums run in pivot order s = 0, 1, ... inside the lane, so no cross-lane
