@@ -142,8 +142,9 @@ typedef struct spx_opts {
  *         max(sigma_j d_j, 0) / -(s sigma_j a_j); theta = delta_q / alpha_q and
  *         the entering column starts from the bound it sat at.  Without a
  *         finite bound the loop and its kernels are the unbounded ones.  Finite
- *         bounds with SPX_ALGO_PRIMAL are SPX_ERR_STATE; no bound-flipping ratio
- *         test, no non-zero or free lower bounds. */
+ *         bounds with SPX_ALGO_PRIMAL are SPX_ERR_STATE; the bound-flipping ratio
+ *         test is SPX_DUAL_RATIO_LONG_STEP (below); no non-zero or free lower
+ *         bounds. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
 
@@ -166,6 +167,28 @@ typedef struct spx_opts {
  *           recomputed from B^-1 before the next pass. */
 #define SPX_DUAL_PRICING_DANTZIG  0
 #define SPX_DUAL_PRICING_STEEPEST 1
+
+/* Ratio tests of the dual loop's boxed passes (SPX_FLAG_DUAL_LONG_STEP at
+ * spx_create, spx_set_dual_ratio later).
+ * TEXTBOOK:  the entering column is the first candidate in (key, column) order
+ *            (above).
+ * LONG_STEP: the bound-flipping (long-step) ratio test.  The candidates are
+ *            walked in that order with slope = |delta_q|: a candidate with u_j =
+ *            +inf enters; otherwise slope' = slope - u_j (-ahat_j), ahat_j = s
+ *            sigma_j a_j; slope' < 0: it enters, else it is flipped to its other
+ *            bound, slope = slope' and the walk goes on.  No candidate, or all
+ *            flipped and none enters: SPX_STATUS_INFEASIBLE with no flip applied.
+ *            With dx_j = +u_j for a flipped column at lower, -u_j at upper, and v
+ *            = sum dx_j A_j: x_b -= B^-1 v, the effective right-hand side -= v,
+ *            the flipped columns change side, delta_q is taken again from the
+ *            new x_b[q] (same s) and the pivot on the entering column is the
+ *            textbook one with the walk's d_p.  Flips are not pivots: the pivot
+ *            count, the trace and refactor_every count pivots only, and the
+ *            steepest-edge weights do not depend on placements.  A pass that
+ *            flips nothing is the textbook pass bit for bit; a context with no
+ *            finite bound launches the unbounded kernels under either rule. */
+#define SPX_DUAL_RATIO_TEXTBOOK  0
+#define SPX_DUAL_RATIO_LONG_STEP 1
 
 /* Entering-column rules (README.md:16-17 "steepest edge").
  * DANTZIG: most negative e_j (v4:288-302).
@@ -265,6 +288,11 @@ typedef struct spx_opts {
                                        accepted and inert while the context runs the
                                        primal loop                                */
 
+#define SPX_FLAG_DUAL_LONG_STEP 4096 /* the dual loop starts with the ratio test
+                                       SPX_DUAL_RATIO_LONG_STEP (default TEXTBOOK);
+                                       accepted and inert while the context runs the
+                                       primal loop or has no finite bound          */
+
 void spx_default_opts(spx_opts* opts);
 
 /* Allocate device state, upload A (column-major, ld = m), b, c and set the
@@ -362,6 +390,18 @@ int spx_set_algorithm(spx_ctx* ctx, int32_t algorithm);
  * the primal loop too (e.g. before spx_set_algorithm(SPX_ALGO_DUAL) repairs a
  * primal solve after spx_set_rhs).  SPX_ERR_ARG for NULL or an unknown rule. */
 int spx_set_dual_pricing(spx_ctx* ctx, int32_t rule);
+
+/* Ratio test of the dual loop's boxed passes (SPX_DUAL_RATIO_*), between any
+ * two calls; takes effect with the next dual pass and invalidates nothing (the
+ * feasibility check and the steepest-edge weights stay).  Valid while the
+ * context runs the primal loop too.  SPX_ERR_ARG for NULL or an unknown rule. */
+int spx_set_dual_ratio(spx_ctx* ctx, int32_t rule);
+
+/* Bound flips of the long-step ratio test since spx_create or spx_reset:
+ * out[0] columns flipped, out[1] passes that flipped at least one column,
+ * out[2] the largest flip count of one pass.  Counted on the device by the
+ * kernel that walks the candidates. */
+int spx_get_dual_flips(spx_ctx* ctx, int64_t out[3]);
 
 /* Dual steepest-edge weights w[0..m) of the current basis (squared row norms
  * of B^-1, basis order), recomputed first where no pass has kept them.

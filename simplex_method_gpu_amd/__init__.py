@@ -26,7 +26,8 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "shard_range", "minloc_merge", "group_iterate", "group_sync", "check_ranks",
            "SimplexError", "FLAG_TIMING", "RATIO_REFERENCE", "RATIO_GUARDED", "RATIO_HARRIS",
            "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL",
-           "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST"]
+           "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST",
+           "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -51,6 +52,9 @@ PRICING_DANTZIG, PRICING_DEVEX, PRICING_STEEPEST = 0, 1, 2
 ALGO_PRIMAL, ALGO_DUAL = 0, 1
 # leaving-row rules of the dual loop (include/simplex.h SPX_DUAL_PRICING_*)
 DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST = 0, 1
+# ratio tests of the dual loop's boxed passes (include/simplex.h SPX_DUAL_RATIO_*)
+DUAL_RATIO_TEXTBOOK, DUAL_RATIO_LONG_STEP = 0, 1
+FLAG_DUAL_LONG_STEP = 4096  # the dual loop starts with the bound-flipping ratio test (default: textbook)
 
 
 class SolveStatus(IntEnum):
@@ -164,7 +168,8 @@ class Context:
                  pricing: int = 0, persist: bool | None = None, loop_block: int = 0, comm1: bool = False,
                  tableau: bool = False, trace: int = 0, counted_tail: bool = False,
                  price_tail: bool = False, algorithm: int = ALGO_PRIMAL,
-                 dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None):
+                 dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None,
+                 dual_ratio: int = DUAL_RATIO_TEXTBOOK):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -181,13 +186,17 @@ class Context:
         if dual_pricing not in (DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST):
             raise ValueError("dual_pricing must be DUAL_PRICING_DANTZIG or DUAL_PRICING_STEEPEST")
         self._dual_pricing = dual_pricing
+        if dual_ratio not in (DUAL_RATIO_TEXTBOOK, DUAL_RATIO_LONG_STEP):
+            raise ValueError("dual_ratio must be DUAL_RATIO_TEXTBOOK or DUAL_RATIO_LONG_STEP")
+        self._dual_ratio = dual_ratio
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
                    | ({None: 0, True: FLAG_PERSIST, False: FLAG_NO_PERSIST}[persist])
                    | (FLAG_COMM1 if comm1 else 0) | (FLAG_TABLEAU if tableau else 0)
                    | (FLAG_COUNTED_TAIL if counted_tail else 0) | (FLAG_PRICE_TAIL if price_tail else 0)
-                   | (FLAG_DUAL_STEEPEST if dual_pricing == DUAL_PRICING_STEEPEST else 0))
+                   | (FLAG_DUAL_STEEPEST if dual_pricing == DUAL_PRICING_STEEPEST else 0)
+                   | (FLAG_DUAL_LONG_STEP if dual_ratio == DUAL_RATIO_LONG_STEP else 0))
         h = ctypes.c_void_p()
         if A_cols is not None:
             A_cols = np.ascontiguousarray(A_cols, dtype=np.float64)
@@ -292,6 +301,21 @@ class Context:
         (spx_set_dual_pricing): DUAL_PRICING_DANTZIG / DUAL_PRICING_STEEPEST."""
         check(self._L.spx_set_dual_pricing(self._h, rule))
         self._dual_pricing = rule
+
+    def set_dual_ratio(self, rule: int):
+        """Ratio test of the dual loop's boxed passes from the next dual pass on
+        (spx_set_dual_ratio): DUAL_RATIO_TEXTBOOK / DUAL_RATIO_LONG_STEP (the
+        bound-flipping ratio test)."""
+        check(self._L.spx_set_dual_ratio(self._h, rule))
+        self._dual_ratio = rule
+
+    def dual_flips(self):
+        """(columns flipped, passes with at least one flip, largest flip count
+        of one pass) of the long-step ratio test since create / reset
+        (spx_get_dual_flips)."""
+        out = (ctypes.c_int64 * 3)()
+        check(self._L.spx_get_dual_flips(self._h, out))
+        return tuple(int(v) for v in out)
 
     def dual_weights(self):
         """Dual steepest-edge weights of the current basis, the squared row
@@ -504,6 +528,7 @@ class Context:
                 "ftran_rows_per_wave", "mbox_fused")
         cfg = dict(zip(keys, list(out)))
         cfg["dual_pricing"] = self._dual_pricing  # (the library keeps it outside spx_config)
+        cfg["dual_ratio"] = self._dual_ratio
         return cfg
 
 

@@ -30,6 +30,9 @@
 //                  a slack basis that is not dual feasible is an error (exit 1)
 //   --dual-pricing R  leaving-row rule of --dual: dantzig (most negative x_b, default)
 //                  | steepest (dual steepest edge, SPX_DUAL_PRICING_STEEPEST)
+//   --dual-ratio R ratio test of --dual with --bounds: textbook (default) | long (the
+//                  bound-flipping ratio test, SPX_DUAL_RATIO_LONG_STEP; --json
+//                  then carries the flip counts).  --ratio stays the primal rule
 //   --bounds F     upper bounds 0 <= x_j <= u_j of all n columns for --dual
 //                  (spx_set_bounds): F holds n whitespace-separated values, "inf"
 //                  = none; without --dual the library's refusal is printed (exit
@@ -79,7 +82,7 @@ static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
                  " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual]"
-                 " [--dual-pricing dantzig|steepest] [--bounds F]"
+                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -98,7 +101,7 @@ int main(int argc, char* argv[]) {
     int ratio = -1, window = 0, pricing = SPX_PRICING_DANTZIG;
     double piv_tol = 1e-9, feas_tol = 1e-9, big_m = 0.0;
     int64_t refactor = 0;
-    bool mps_in = false, tableau = false, dual = false, dual_steepest = false;
+    bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -139,6 +142,12 @@ int main(int argc, char* argv[]) {
             const std::string r = argv[++a];
             if (r != "dantzig" && r != "steepest") { usage(); return 1; }
             dual_steepest = r == "steepest";
+        }
+        else if (s == "--dual-ratio") {
+            need(1);
+            const std::string r = argv[++a];
+            if (r != "textbook" && r != "long") { usage(); return 1; }
+            dual_long = r == "long";
         }
         else if (s == "--pricing") {
             need(1);
@@ -215,6 +224,7 @@ int main(int argc, char* argv[]) {
     if (tableau) o.flags |= SPX_FLAG_TABLEAU;
     if (dual) o.algorithm = SPX_ALGO_DUAL;
     if (dual_steepest) o.flags |= SPX_FLAG_DUAL_STEEPEST;
+    if (dual_long) o.flags |= SPX_FLAG_DUAL_LONG_STEP;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)
@@ -262,6 +272,8 @@ int main(int argc, char* argv[]) {
         return EXIT_FAILURE;
     }
     const TimePoint t_loop_end = Clock::now();
+    int64_t flips[3] = {0, 0, 0};
+    if (dual) spx_get_dual_flips(ctx, flips);
     spx_destroy(ctx);
     const TimePoint t_dealloc_end = Clock::now();
 
@@ -341,8 +353,11 @@ int main(int argc, char* argv[]) {
     if (json) {
         std::cout << std::defaultfloat << std::setprecision(17);
         std::cout << "{\"status\": " << status << ", \"z\": " << z << ", \"pivots\": " << pivots
-                  << ", \"m\": " << m << ", \"n\": " << n
-                  << ", \"solve_s\": " << seconds(t_init_end, t_loop_end) << "}\n";
+                  << ", \"m\": " << m << ", \"n\": " << n;
+        if (dual)
+            std::cout << ", \"dual_ratio\": \"" << (dual_long ? "long" : "textbook") << "\", \"flips\": " << flips[0]
+                      << ", \"flip_passes\": " << flips[1] << ", \"max_flips\": " << flips[2];
+        std::cout << ", \"solve_s\": " << seconds(t_init_end, t_loop_end) << "}\n";
     }
     return 0;
 }

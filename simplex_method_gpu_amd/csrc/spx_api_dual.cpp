@@ -28,6 +28,7 @@ namespace {
 //                                          (normalisation)
 //   dual_check_feasible / box_normalise ok true             -
 //   dual_refresh_weights                   -                false
+//   spx_set_dual_ratio                     kept             kept
 void feasibility_unknown(spx_ctx* x) { x->dual.checked = false; }  // the basis or its bounds were set from outside
 void feasibility_verified(spx_ctx* x) { x->dual.checked = true; }  // the check (boxed: the normalisation) passed
 void weights_lost(spx_ctx* x) { x->dual.w_stale = true; }          // B^-1 or the rule changed with no steepest pass keeping w
@@ -136,10 +137,49 @@ int dual_refresh_weights(spx_ctx* x) {
     return SPX_OK;
 }
 
-// One dual pass: leaving row + pivot row, ratio test, FTRAN + update.
+// the bound-flipping ratio test runs where there is something to flip
+bool long_step(const spx_ctx* x) { return x->dual.boxed && x->dual.ratio == SPX_DUAL_RATIO_LONG_STEP; }
+
+// its buffers, on first use (n list slots: the non-basic count never exceeds n)
+int long_setup(spx_ctx* x) {
+    DualState& d = x->dual;
+    if (d.args.lrec) return SPX_OK;
+    const size_t n = (size_t)x->n;
+    SPX_TRY(x->alloc(&d.args.rkey, n));
+    SPX_TRY(x->alloc(&d.args.rcd, 2 * n));
+    SPX_TRY(x->alloc(&d.args.flist, n));
+    SPX_TRY(x->alloc(&d.args.v, (size_t)x->L));
+    SPX_TRY(x->alloc(&d.args.fl, (size_t)x->L));
+    SPX_TRY(x->alloc(&d.args.lrec, 1));
+    d.args.walk_global = env_on("SPX_DUAL_LONG_GLOBAL") ? 1 : 0;  // (test: the walk's path for more than 16,384 list slots)
+    return SPX_OK;
+}
+
+// the launch that commits the last pass's pivot (and its flips)
+int enqueue_dual_finish(spx_ctx* x) {
+    const DualState& d = x->dual;
+    const bool se = d.rule == SPX_DUAL_PRICING_STEEPEST;
+    if (long_step(x)) HIP_TRY(launch_dual_step_long(x->P, d.args, se, true, x->stream));
+    else HIP_TRY(launch_dual_step(x->P, d.args, se, d.boxed, true, x->stream));
+    return SPX_OK;
+}
+
+// One dual pass: leaving row + pivot row, ratio test, FTRAN + update; five
+// launches with the bound-flipping ratio test (spx_dual.h).
 int enqueue_dual_pass(spx_ctx* x, hipEvent_t p0, hipEvent_t p1, hipEvent_t u0, hipEvent_t u1) {
     const DualState& d = x->dual;
     const bool se = d.rule == SPX_DUAL_PRICING_STEEPEST;
+    if (long_step(x)) {
+        HIP_TRY(launch_dual_step_long(x->P, d.args, se, false, x->stream));
+        HIP_TRY(launch_dual_price_long(x->P, d.args, d.cfg, x->stream, p0, p1));
+        HIP_TRY(launch_dual_long(x->P, d.args, x->stream));
+        HIP_TRY(launch_dual_flips(x->P, d.args, x->b, x->stream));
+        // (timing: the "exchange end" event closes the walk and the flips, so
+        // spx_pass_times' out[1] - out[0] is k_dual_long + k_dual_flips)
+        if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
+        HIP_TRY(launch_dual_update_long(x->P, d.args, d.cfg, se, x->stream, u0, u1));
+        return SPX_OK;
+    }
     HIP_TRY(launch_dual_step(x->P, d.args, se, d.boxed, false, x->stream));
     HIP_TRY(launch_dual_price(x->P, d.args, d.cfg, d.boxed, x->stream, p0, p1));
     if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
@@ -163,6 +203,7 @@ const char* dual_conflict(const spx_opts& o, int win) {
 
 void dual_on_create(spx_ctx* x) {
     x->dual.rule = (x->opts.flags & SPX_FLAG_DUAL_STEEPEST) ? SPX_DUAL_PRICING_STEEPEST : SPX_DUAL_PRICING_DANTZIG;
+    x->dual.ratio = (x->opts.flags & SPX_FLAG_DUAL_LONG_STEP) ? SPX_DUAL_RATIO_LONG_STEP : SPX_DUAL_RATIO_TEXTBOOK;
 }
 
 // (spx_create with SPX_ALGO_DUAL, spx_set_algorithm, or the first entry point that needs a buffer)
@@ -203,6 +244,7 @@ int iterate_dual(spx_ctx* x, int64_t k) {
     const bool se = x->dual.rule == SPX_DUAL_PRICING_STEEPEST;
     if (se) SPX_TRY(dual_refresh_weights(x));
     else weights_lost(x);  // Dantzig passes keep no weights
+    if (long_step(x)) SPX_TRY(long_setup(x));
     SPX_TRY(set_limit(x, x->pivots + k));
     for (int64_t i = 0; i < k; ++i) {
         hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
@@ -211,7 +253,7 @@ int iterate_dual(spx_ctx* x, int64_t k) {
         ++x->n_eager;
     }
     // (steepest edge: the last pivot's weights too)
-    HIP_TRY(launch_dual_step(x->P, x->dual.args, se, x->dual.boxed, true, x->stream));
+    SPX_TRY(enqueue_dual_finish(x));
     return read_state(x);
 }
 
@@ -222,6 +264,7 @@ int dual_on_reset(spx_ctx* x) {
         HIP_TRY(hipMemcpyAsync(x->b, d.b_user, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
     }
     if (d.args.rec) HIP_TRY(hipMemsetAsync(d.args.rec, 0, sizeof(DualRec), x->stream));
+    if (d.args.lrec) HIP_TRY(hipMemsetAsync(d.args.lrec, 0, sizeof(DualLongRec), x->stream));  // the flip counters too
     feasibility_unknown(x);
     weights_lost(x);
     return SPX_OK;
@@ -280,6 +323,27 @@ int spx_set_dual_pricing(spx_ctx* x, int32_t rule) {
         return fail(SPX_ERR_ARG, "bad dual pricing rule %d", rule);
     if (rule != x->dual.rule) weights_lost(x);
     x->dual.rule = rule;
+    return SPX_OK;
+}
+
+int spx_set_dual_ratio(spx_ctx* x, int32_t rule) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (rule != SPX_DUAL_RATIO_TEXTBOOK && rule != SPX_DUAL_RATIO_LONG_STEP)
+        return fail(SPX_ERR_ARG, "bad dual ratio test %d", rule);
+    x->dual.ratio = rule;  // (x_b, b_eff and at_upper are consistent between calls under either rule)
+    return SPX_OK;
+}
+
+int spx_get_dual_flips(spx_ctx* x, int64_t out[3]) {
+    if (!x || !out) return fail(SPX_ERR_ARG, "NULL argument");
+    out[0] = out[1] = out[2] = 0;
+    if (!x->dual.args.lrec) return SPX_OK;  // no long-step pass yet
+    DualLongRec r;
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(&r, x->dual.args.lrec, sizeof r, hipMemcpyDeviceToHost));
+    out[0] = r.flips;
+    out[1] = r.passes;
+    out[2] = r.max_pass;
     return SPX_OK;
 }
 

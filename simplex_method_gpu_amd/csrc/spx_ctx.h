@@ -64,11 +64,18 @@ int fail(int code, const char* fmt, ...);
 //    is the effective one, b_user - sum_{j non-basic at upper} u_j A_j.  Not
 //    boxed: Params::b is the caller's b and no column is at upper.
 //  - ub is empty (never set: all +inf) or holds n bounds, the host copy of args.ub.
+//  - ratio is the ratio test of the next boxed pass (spx_set_dual_ratio); it
+//    invalidates nothing: x_b, Params::b and at_upper are consistent between any
+//    two calls under either rule.  args.lrec != nullptr  <=>  the long-step
+//    buffers (rkey .. lrec) are allocated: by the first boxed pass under
+//    SPX_DUAL_RATIO_LONG_STEP, never freed.  The flip counters live in args.lrec
+//    (all 0 while it is not allocated).
 struct DualState {
-    spx::DualBoxArgs args{};
+    spx::DualLongArgs args{};
     spx::DualCfg cfg{};
     double* e = nullptr;  // n reduced costs (the feasibility check)
     int32_t rule = SPX_DUAL_PRICING_DANTZIG;  // leaving-row rule (spx_set_dual_pricing)
+    int32_t ratio = SPX_DUAL_RATIO_TEXTBOOK;  // ratio test of the boxed passes (spx_set_dual_ratio)
     bool checked = false;
     bool w_stale = true;
     bool boxed = false;

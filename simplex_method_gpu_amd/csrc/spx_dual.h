@@ -39,6 +39,23 @@
 // k_dual_update and k_dual_norms are shared: alpha, tau and wex do not depend on
 // bounds.  P.b is then the effective right-hand side (k_box_rhs).  A context
 // with no finite bound launches the unboxed kernels only.
+//
+// The bound-flipping (long-step) ratio test (SPX_DUAL_RATIO_LONG_STEP, boxed
+// contexts only) makes a pass five launches:
+//   k_dual_step_long / k_dual_step_se_long   as above; the commit also takes the
+//                  flipped columns' B^-1 v (DualLongArgs::fl) off x_b.
+//   k_dual_price<., ., true>   the boxed ratio test, which also stores every list
+//                  slot's record: key, u_j (-ahat_j), d_j.
+//   k_dual_long    one workgroup: merges the partials and walks the candidates in
+//                  (key, column) order with slope |delta_q|; a bounded candidate
+//                  whose u_j (-ahat_j) leaves the slope >= 0 is flipped, the first
+//                  other one enters (p, d_p into DualRec; none: ST_INFEASIBLE,
+//                  nothing flipped).  Leaves the flip list and the counters.
+//   k_dual_flips   returns at once without flips; else v = sum_F dx_j A_j in the
+//                  list's order (one thread per row), P.b -= v, at_upper toggled.
+//   k_dual_update<., ., true>   takes p from DualRec and, when the pass has flips,
+//                  also dots every updated row with v into fl.
+// Without a flip every value is the textbook boxed pass's, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,6 +104,31 @@ struct DualBoxArgs : DualSeArgs {
     int8_t* at_upper;   // n: 1 = the non-basic column sits at its upper bound
 };
 
+struct alignas(16) DualLongRec {  // the long-step pass in flight (k_dual_long) and its counters
+    int32_t nflip;     // columns this pass flips (0: fl and v are not read)
+    int32_t pad;
+    int64_t flips;     // columns flipped since create / spx_reset
+    int64_t passes;    // passes with at least one flip
+    int64_t max_pass;  // the largest flip count of one pass
+};
+
+struct alignas(16) DualFlip {  // one flipped column, in the walk's order
+    int64_t j;
+    double dx;  // +u_j from lower to upper, -u_j back
+};
+
+// the long-step instantiations' arguments (boxed contexts under SPX_DUAL_RATIO_LONG_STEP)
+struct DualLongArgs : DualBoxArgs {
+    double* rkey;       // n: list slot s: the candidate's key, +inf when nb_list[s] is none
+    double* rcd;        // 2 n: (u_j (-ahat_j), d_j) of the slot's column
+    DualFlip* flist;    // n
+    double* v;          // L: sum over the flipped columns of dx_j A_j
+    double* fl;         // L: B^-1 v (k_dual_update<., ., true>)
+    DualLongRec* lrec;
+    int32_t walk_global;  // 1: k_dual_long reads the keys from global memory every round (its path beyond
+    int32_t pad2;         //    16,384 list slots, forced: SPX_DUAL_LONG_GLOBAL=1)
+};
+
 struct DualCfg {
     int price_grid = 0;
     bool price_lds = false;  // rho and y staged in LDS (2 * 8 * L bytes) or read from global
@@ -106,6 +148,15 @@ hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool globa
 // se: the steepest-edge instantiations (leaving row by -x_b^2 / w, weights kept in D.w)
 // box: the boxed instantiations (two-sided leaving rows, sigma_j in the ratio test)
 hipError_t launch_dual_step(const Params& P, const DualBoxArgs& D, bool se, bool box, bool finish_only, hipStream_t s);
+// the long-step pass (boxed): the step and price instantiations above with the
+// flips, then k_dual_long + k_dual_flips (one timed span e0..e1), then the update
+hipError_t launch_dual_step_long(const Params& P, const DualLongArgs& D, bool se, bool finish_only, hipStream_t s);
+hipError_t launch_dual_price_long(const Params& P, const DualLongArgs& D, const DualCfg& c, hipStream_t s,
+                                  hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_dual_long(const Params& P, const DualLongArgs& D, hipStream_t s);
+hipError_t launch_dual_flips(const Params& P, const DualLongArgs& D, double* b_eff, hipStream_t s);
+hipError_t launch_dual_update_long(const Params& P, const DualLongArgs& D, const DualCfg& c, bool se, hipStream_t s,
+                                   hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_dual_price(const Params& P, const DualBoxArgs& D, const DualCfg& c, bool box, hipStream_t s,
                              hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_dual_update(const Params& P, const DualSeArgs& D, const DualCfg& c, bool se, hipStream_t s,

@@ -67,6 +67,16 @@ struct SeDots {  // k_dual_update: rho's operand and the two extra dots' accumul
 template <>
 struct SeDots<0> {};
 
+// ... and only its long-step instantiations
+template <bool LONG>
+struct FlipDots {  // k_dual_update: whether the pass flipped columns, v, and the dot's accumulators
+    bool on = false;
+    const dbl2* xv;
+    double f0 = 0.0, f1 = 0.0;
+};
+template <>
+struct FlipDots<false> {};
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -102,6 +112,21 @@ struct SeDots<0> {};
 #undef SPX_STEP_KERNEL
 #undef SPX_STEP_ARGS
 #undef SPX_STEP_SE
+// ... with the bound-flipping ratio test's flips in the commit
+#define SPX_STEP_LONG 1
+#define SPX_STEP_KERNEL k_dual_step_long
+#define SPX_STEP_ARGS DualLongArgs
+#define SPX_STEP_SE 0
+#include "spx_dual_step.inc"
+#undef SPX_STEP_KERNEL
+#undef SPX_STEP_SE
+#define SPX_STEP_KERNEL k_dual_step_se_long
+#define SPX_STEP_SE 1
+#include "spx_dual_step.inc"
+#undef SPX_STEP_KERNEL
+#undef SPX_STEP_ARGS
+#undef SPX_STEP_SE
+#undef SPX_STEP_LONG
 #undef SPX_STEP_BOX
 
 // ---------------------------------------------------------------------------
@@ -117,8 +142,13 @@ struct SeDots<0> {};
 // for a column at its upper bound (one wave-uniform flag read per column, ahead
 // of its stream), candidates are s sigma_j a_j < -piv_tol and the key is
 // max(sigma_j d_j, 0) / -(s sigma_j a_j); the partial carries the raw a_j, d_j.
-template <bool LDS, bool BOX>
-__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, std::conditional_t<BOX, DualBoxArgs, DualArgs> D) {
+// LONG (BOX with the bound-flipping ratio test): lane 0 also stores the list
+// slot's record after the butterfly, key (+inf: no candidate), u_j (-ahat_j)
+// and d_j: 24 bytes beside the 8 (m + 1) streamed; u_j is read with the flag.
+template <bool LDS, bool BOX, bool LONG = false>
+__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(
+    Params P, std::conditional_t<LONG, DualLongArgs, std::conditional_t<BOX, DualBoxArgs, DualArgs>> D) {
+    static_assert(BOX || !LONG, "the long-step ratio test is the boxed one's");
     constexpr int WAVES = DUAL_WAVES, U = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
     __shared__ DualPartial s_red[WAVES];
@@ -156,6 +186,8 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, std::condit
         const int64_t j = P.nb_list[s];
         [[maybe_unused]] int up = 0;
         if constexpr (BOX) up = D.at_upper[j];
+        [[maybe_unused]] double uj = 0.0;
+        if constexpr (LONG) uj = D.ub[j];
         double a, d;
         if (P.slack_unit && j >= P.ns) {  // A_j = e_k: no stream
             const int64_t k = j - P.ns;
@@ -193,13 +225,21 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, std::condit
         if constexpr (BOX) {
             const double sg = up ? -1.0 : 1.0;
             const double ah = dir * sg * a, dh = sg * d;  // (sign flips: exact)
+            [[maybe_unused]] double rk = INFINITY;
             if (ah < -D.piv_tol) {
                 const double key = (dh > 0.0 ? dh : 0.0) / (-ah);
+                if constexpr (LONG) rk = key;
                 if (argmin_better(key, j, bkey, bidx)) {
                     bkey = key;
                     bidx = j;
                     ba = a;
                     bd = d;
+                }
+            }
+            if constexpr (LONG) {
+                if (lane == 0) {  // (s < cnt <= n: the buffers hold n slots)
+                    D.rkey[s] = rk;
+                    reinterpret_cast<dbl2*>(D.rcd)[s] = dbl2{uj * (-ah), d};
                 }
             }
         } else if (a < -D.piv_tol) {
@@ -229,8 +269,14 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_price(Params P, std::condit
 // rho (tau_i) and with itself (the exact weight wex_i), in acc0 / acc1's fixed
 // order, so neither depends on the grid.  SE 1 stages rho in LDS beside the
 // pending row and A_p (24 L bytes), SE 2 reads it from global memory (L2 hits).
-template <bool XL, int SE>
-__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgsOf<SE != 0> D) {
+// LONG (the bound-flipping ratio test): p comes from the pass record (k_dual_long
+// merged the partials), and when the pass flipped columns the updated row is
+// also dotted with v (global memory, L2 hits: a fourth LDS operand would halve
+// the occupancy of the passes without flips) into fl, in acc0 / acc1's order;
+// the test is wave-uniform and a pass without flips reads nothing more.
+template <bool XL, int SE, bool LONG = false>
+__global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(
+    Params P, std::conditional_t<LONG, DualLongArgs, DualArgsOf<SE != 0>> D) {
     constexpr int WAVES = DUAL_WAVES, U = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
     __shared__ DualPartial s_red[WAVES];
@@ -246,6 +292,10 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgsOf
         Sv.limit = st->limit;
         Sv.qprev = st->q;
         Sv.aqprev = st->aq;
+        if constexpr (LONG) {
+            Sv.p = D.rec->p;
+            Sv.cnt = D.lrec->nflip;
+        }
     }
     __syncthreads();
     const int64_t it = Sv.it, qp = Sv.qprev;
@@ -253,24 +303,34 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgsOf
     if (Sv.status != ST_RUNNING || it >= Sv.limit) return;
 
     // the ratio test's grid step: every workgroup merges the same partials
+    // (LONG: k_dual_long did, and left the entering column in the pass record)
     DualPartial w{INFINITY, INT64_MAX, 0.0, 0.0};
-    for (int g = tid; g < D.price_grid; g += DUAL_BLOCK) {
-        const DualPartial v = D.parts[g];
-        if (argmin_better(v.key, v.idx, w.key, w.idx)) w = v;
+    if constexpr (!LONG) {
+        for (int g = tid; g < D.price_grid; g += DUAL_BLOCK) {
+            const DualPartial v = D.parts[g];
+            if (argmin_better(v.key, v.idx, w.key, w.idx)) w = v;
+        }
+        wave_argmin4(w);
+        if (lane == 0) s_red[wave] = w;
+        __syncthreads();
     }
-    wave_argmin4(w);
-    if (lane == 0) s_red[wave] = w;
-    __syncthreads();
-    const DualPartial t = merge_waves<WAVES>(s_red);
+    const DualPartial t = LONG ? DualPartial{0.0, Sv.p, 0.0, 0.0} : merge_waves<WAVES>(s_red);
     if (t.idx == INT64_MAX) {  // no a_j < -piv_tol in a row with x_b < 0: primal infeasible
         if (blockIdx.x == 0 && tid == 0) st->status = ST_INFEASIBLE;
         return;
     }
     const int64_t p = t.idx;
     if (blockIdx.x == 0 && tid == 0) {
-        D.rec->p = p;
-        D.rec->d_p = t.d;
+        if constexpr (!LONG) {
+            D.rec->p = p;
+            D.rec->d_p = t.d;
+        }
         D.rec->fresh = 1;
+    }
+    [[maybe_unused]] FlipDots<LONG> fd;
+    if constexpr (LONG) {
+        fd.on = Sv.cnt > 0;
+        fd.xv = reinterpret_cast<const dbl2*>(D.v);
     }
 
     const int64_t m = P.m, L = P.L, L2 = L >> 1;
@@ -325,6 +385,13 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgsOf
                     se.w0 = fma(nv.x, nv.x, se.w0);
                     se.w1 = fma(nv.y, nv.y, se.w1);
                 }
+                if constexpr (LONG) {
+                    if (fd.on) {
+                        const dbl2 vv = fd.xv[k];
+                        fd.f0 = fma(nv.x, vv.x, fd.f0);
+                        fd.f1 = fma(nv.y, vv.y, fd.f1);
+                    }
+                }
             }
         }
 #pragma unroll
@@ -332,6 +399,12 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_dual_update(Params P, DualArgsOf
     }
     const double alpha = wave_sum(acc0 + acc1);
     if (lane == 0) a_new[i] = alpha;
+    if constexpr (LONG) {
+        if (fd.on) {
+            const double f = wave_sum(fd.f0 + fd.f1);
+            if (lane == 0) D.fl[i] = f;
+        }
+    }
     if constexpr (SE != 0) {
         double t = se.t0 + se.t1, w = se.w0 + se.w1;
         wave_sum2(t, w);
@@ -426,6 +499,200 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_box_xb(Params P) {
 }
 
 // ---------------------------------------------------------------------------
+// Bound-flipping ratio test: the walk over k_dual_price<., ., true>'s records
+// ---------------------------------------------------------------------------
+// One workgroup.  Round 0 merges the pricing workgroups' partials (the textbook
+// winner); every later round is the argmin over the records strictly beyond the
+// last (key, column) taken, so the candidates come in (key, column) order.
+// Thread 0 keeps the slope: a candidate with no bound, or whose u_j (-ahat_j)
+// takes the slope below 0, enters; any other is flipped and the walk goes on.
+// A pass without flips is round 0 alone.  The first round that scans loads each
+// thread's LONG_SLOTS keys and columns into registers (nb_count <= LONG_SLOTS x
+// LONG_BLOCK; beyond that, or with DualLongArgs::walk_global, every round reads
+// them from global memory), so a later round costs two reductions and thread
+// 0's one round trip for the winner's record.  At most nb_count + 1 rounds
+// (every round takes a distinct slot or ends the walk); nothing here waits on
+// another workgroup.  No candidate left: ST_INFEASIBLE, no flip applied, no
+// counter moved.
+constexpr int LONG_BLOCK = 512;
+constexpr int LONG_SLOTS = 32;
+__global__ __launch_bounds__(LONG_BLOCK) void k_dual_long(Params P, DualLongArgs D) {
+    constexpr int WAVES = LONG_BLOCK / 64;
+    __shared__ double s_key[WAVES];
+    __shared__ int64_t s_j[WAVES];
+    __shared__ int32_t s_s[WAVES];
+    __shared__ double w_key;
+    __shared__ int64_t w_j;
+    __shared__ int32_t w_state;  // 0 flipped: go on, 1 entering column found, 2 no candidate left
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int32_t status = st->status, cnt = st->nb_count;
+    const int64_t iter = st->iter, limit = st->limit;
+    if (status != ST_RUNNING || iter >= limit) return;  // (thread 0 stores the status after a barrier only)
+    double slope = 0.0;
+    int nfl = 0;
+    if (tid == 0) {
+        const int64_t q = D.rec->q;
+        const double xq = P.x_b[q];
+        slope = fabs(D.rec->s > 0 ? xq : xq - D.ub_B[q]);  // |delta_q|
+    }
+    // one round's end: the workgroup's (key, column, slot) argmin, then thread 0's decision
+    auto decide = [&](double bk, int64_t bj, int32_t bs) -> int {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double k2 = __shfl_xor(bk, off, 64);
+            const int64_t j2 = __shfl_xor(bj, off, 64);
+            const int32_t s2 = __shfl_xor(bs, off, 64);
+            const bool t = argmin_better(k2, j2, bk, bj);
+            bk = t ? k2 : bk;
+            bj = t ? j2 : bj;
+            bs = t ? s2 : bs;
+        }
+        if (lane == 0) {
+            s_key[wave] = bk;
+            s_j[wave] = bj;
+            s_s[wave] = bs;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < WAVES; ++w) {
+                const bool t = argmin_better(s_key[w], s_j[w], bk, bj);
+                bk = t ? s_key[w] : bk;
+                bj = t ? s_j[w] : bj;
+                bs = t ? s_s[w] : bs;
+            }
+            if (bj == INT64_MAX) {
+                w_state = 2;
+            } else {
+                const int64_t sl = bs >= 0 ? bs : P.nb_pos[bj];  // its list slot: 0 <= sl < cnt
+                const double cap = D.rcd[2 * sl], d = D.rcd[2 * sl + 1];
+                const double u = D.ub[bj];
+                const int up = D.at_upper[bj];
+                const double slope2 = slope - cap;
+                if (!(cap < INFINITY) || slope2 < 0.0) {
+                    D.rec->p = bj;
+                    D.rec->d_p = d;
+                    w_state = 1;
+                } else {
+                    D.flist[nfl] = DualFlip{bj, up ? -u : u};  // (nfl < cnt <= n)
+                    ++nfl;
+                    slope = slope2;
+                    w_key = bk;
+                    w_j = bj;
+                    w_state = 0;
+                }
+            }
+        }
+        __syncthreads();  // (also fences the next round's stores to s_key .. s_s)
+        return w_state;
+    };
+    // round 0: the partials (slot -1: thread 0 looks it up)
+    double bk = INFINITY;
+    int64_t bj = INT64_MAX;
+    for (int g = tid; g < D.price_grid; g += LONG_BLOCK) {
+        const DualPartial v = D.parts[g];
+        if (argmin_better(v.key, v.idx, bk, bj)) {
+            bk = v.key;
+            bj = v.idx;
+        }
+    }
+    int state = decide(bk, bj, -1);
+    if (state == 0) {
+        double lastk = w_key;
+        int64_t lastj = w_j;
+        if (!D.walk_global && cnt <= LONG_SLOTS * LONG_BLOCK) {
+            double ck[LONG_SLOTS];
+            int32_t cj[LONG_SLOTS];
+#pragma unroll
+            for (int t = 0; t < LONG_SLOTS; ++t) {
+                const int s = tid + t * LONG_BLOCK;
+                ck[t] = s < cnt ? D.rkey[s] : INFINITY;
+                cj[t] = s < cnt ? P.nb_list[s] : INT32_MAX;
+            }
+            for (int round = 1; round <= cnt && state == 0; ++round) {
+                bk = INFINITY;
+                bj = INT64_MAX;
+                int32_t bs = -1;
+#pragma unroll
+                for (int t = 0; t < LONG_SLOTS; ++t) {
+                    const double k = ck[t];
+                    const int64_t j = cj[t];
+                    if (k < INFINITY && argmin_better(lastk, lastj, k, j) && argmin_better(k, j, bk, bj)) {
+                        bk = k;
+                        bj = j;
+                        bs = tid + t * LONG_BLOCK;
+                    }
+                }
+                state = decide(bk, bj, bs);
+                lastk = w_key;
+                lastj = w_j;
+            }
+        } else {
+            for (int round = 1; round <= cnt && state == 0; ++round) {
+                bk = INFINITY;
+                bj = INT64_MAX;
+                int32_t bs = -1;
+                for (int s = tid; s < cnt; s += LONG_BLOCK) {
+                    const double k = D.rkey[s];
+                    const int64_t j = P.nb_list[s];
+                    if (k < INFINITY && argmin_better(lastk, lastj, k, j) && argmin_better(k, j, bk, bj)) {
+                        bk = k;
+                        bj = j;
+                        bs = s;
+                    }
+                }
+                state = decide(bk, bj, bs);
+                lastk = w_key;
+                lastj = w_j;
+            }
+        }
+    }
+    if (tid == 0) {
+        if (state == 1) {
+            DualLongRec* r = D.lrec;
+            r->nflip = nfl;
+            if (nfl > 0) {
+                r->flips += nfl;
+                r->passes += 1;
+                if (nfl > r->max_pass) r->max_pass = nfl;
+            }
+        } else {  // every candidate flipped and none enters, or none at all: primal infeasible
+            D.lrec->nflip = 0;
+            st->status = ST_INFEASIBLE;
+        }
+    }
+}
+
+// The flipped columns' move: v = sum over the flip list, in its order, of dx_j
+// A_j, one thread per row (k_box_rhs's form: coalesced in the column-major A, no
+// atomics), P.b -= v; workgroup 0 toggles at_upper.  Returns at once when the
+// pass flipped nothing (or did not run: k_dual_long's exits).
+__global__ __launch_bounds__(BOX_BLOCK) void k_dual_flips(Params P, DualLongArgs D, double* b_eff) {
+    const DevState* st = P.st;
+    if (st->status != ST_RUNNING || st->iter >= st->limit) return;
+    const int nfl = D.lrec->nflip;
+    if (nfl <= 0) return;
+    const int64_t i = (int64_t)blockIdx.x * BOX_BLOCK + threadIdx.x;
+    const int64_t m = P.m, L = P.L;
+    if (i < L) {
+        double acc = 0.0;
+        if (i < m) {
+            for (int f = 0; f < nfl; ++f) {
+                const DualFlip t = D.flist[f];
+                acc = fma(t.dx, P.A[t.j * L + i], acc);
+            }
+            b_eff[i] -= acc;  // (= P.b, as k_box_rhs writes it)
+        }
+        D.v[i] = acc;
+    }
+    if (blockIdx.x == 0)
+        for (int f = threadIdx.x; f < nfl; f += BOX_BLOCK) {
+            const int64_t j = D.flist[f].j;  // (distinct columns)
+            D.at_upper[j] = D.at_upper[j] ? 0 : 1;
+        }
+}
+
+// ---------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------
 namespace {
@@ -475,6 +742,19 @@ hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool globa
         e = se_rho_lds ? set_lds(k_dual_update<true, 1>, vec3) : set_lds(k_dual_update<true, 2>, vec2);
         if (e != hipSuccess) return e;
     }
+    // the long-step instantiations (launched only under SPX_DUAL_RATIO_LONG_STEP with finite bounds)
+    if (cfg->price_lds) {
+        e = set_lds(k_dual_price<true, true, true>, vec2);
+        if (e != hipSuccess) return e;
+    }
+    if (cfg->update_lds) {
+        e = set_lds(k_dual_update<true, 0, true>, vec2);
+        if (e != hipSuccess) return e;
+    }
+    if (cfg->se_update_lds) {
+        e = se_rho_lds ? set_lds(k_dual_update<true, 1, true>, vec3) : set_lds(k_dual_update<true, 2, true>, vec2);
+        if (e != hipSuccess) return e;
+    }
     if (per_cu < 1) per_cu = 1;
     const int64_t cols = P.n - P.m;  // the non-basic count never changes
     const int64_t want = (cols + DUAL_WAVES - 1) / DUAL_WAVES;
@@ -520,6 +800,43 @@ hipError_t launch_dual_update(const Params& P, const DualSeArgs& D, const DualCf
     const DualArgs& D0 = D;
     if (c.update_lds) return launch_timed(k_dual_update<true, 0>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D0);
     return launch_timed(k_dual_update<false, 0>, c.update_grid, 0, s, e0, e1, P, D0);
+}
+
+hipError_t launch_dual_step_long(const Params& P, const DualLongArgs& D, bool se, bool finish_only, hipStream_t s) {
+    const int fin = finish_only ? 1 : 0;
+    if (se) hipLaunchKernelGGL(k_dual_step_se_long, dim3(1), dim3(1024), 0, s, P, D, fin);
+    else hipLaunchKernelGGL(k_dual_step_long, dim3(1), dim3(1024), 0, s, P, D, fin);
+    return hipGetLastError();
+}
+
+hipError_t launch_dual_price_long(const Params& P, const DualLongArgs& D, const DualCfg& c, hipStream_t s,
+                                  hipEvent_t e0, hipEvent_t e1) {
+    if (c.price_lds)
+        return launch_timed(k_dual_price<true, true, true>, c.price_grid, (size_t)P.L * 16, s, e0, e1, P, D);
+    return launch_timed(k_dual_price<false, true, true>, c.price_grid, 0, s, e0, e1, P, D);
+}
+
+hipError_t launch_dual_long(const Params& P, const DualLongArgs& D, hipStream_t s) {
+    hipLaunchKernelGGL(k_dual_long, dim3(1), dim3(LONG_BLOCK), 0, s, P, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_dual_flips(const Params& P, const DualLongArgs& D, double* b_eff, hipStream_t s) {
+    const int grid = (int)((P.L + BOX_BLOCK - 1) / BOX_BLOCK);
+    hipLaunchKernelGGL(k_dual_flips, dim3(grid), dim3(BOX_BLOCK), 0, s, P, D, b_eff);
+    return hipGetLastError();
+}
+
+hipError_t launch_dual_update_long(const Params& P, const DualLongArgs& D, const DualCfg& c, bool se, hipStream_t s,
+                                   hipEvent_t e0, hipEvent_t e1) {
+    if (se) {
+        if (!c.se_update_lds) return launch_timed(k_dual_update<false, 2, true>, c.update_grid, 0, s, e0, e1, P, D);
+        if (c.se_rho_lds)
+            return launch_timed(k_dual_update<true, 1, true>, c.update_grid, (size_t)P.L * 24, s, e0, e1, P, D);
+        return launch_timed(k_dual_update<true, 2, true>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D);
+    }
+    if (c.update_lds) return launch_timed(k_dual_update<true, 0, true>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D);
+    return launch_timed(k_dual_update<false, 0, true>, c.update_grid, 0, s, e0, e1, P, D);
 }
 
 hipError_t launch_dual_norms(const Params& P, const DualSeArgs& D, const DualCfg& c, hipStream_t s) {

@@ -4,6 +4,7 @@
 //   SPX_STEP_ARGS    DualArgs (Dantzig) or DualSeArgs (steepest edge)
 //   SPX_STEP_SE      0 / 1
 //   SPX_STEP_BOX     0 / 1 (1: SPX_STEP_ARGS is DualBoxArgs)
+//   SPX_STEP_LONG    defined and 1 with SPX_STEP_BOX 1: SPX_STEP_ARGS is DualLongArgs
 // Text inclusion, not a template: as a template instantiation (and as a
 // forceinline body shared by two kernels) the Dantzig kernel compiled to a
 // different schedule than the plain function it has always been; included
@@ -20,6 +21,10 @@
 // delta_q from x_b[q] and ub_B[q] (loaded beside alpha_q: no longer chain),
 // offsets the entering value by u_p when p sat at its upper bound and keeps
 // at_upper / ub_B with the basis.
+// LONG (the bound-flipping ratio test): when the pass flipped columns (nflip >
+// 0) the commit works on x_b - fl, fl = B^-1 v loaded with the chunk's other
+// vectors; delta_q comes from x_b[q] - fl_q.  Without a flip fl is not read and
+// every value is the boxed kernel's.
 __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS D, int finish_only) {
     constexpr int BLOCK = 1024, WAVES = BLOCK / 64;
     DevState* st = P.st;
@@ -27,6 +32,9 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
     const int64_t m = P.m, L = P.L;
     __shared__ StepState S;
     __shared__ ArgMinEntry s_red[WAVES];
+#if SPX_STEP_LONG
+    __shared__ int32_t s_nfl;  // the pass's flip count, read with the snapshot
+#endif
     // The kernel is a chain of dependent memory round trips on one CU, so each
     // phase requests everything it needs before its first store: the state and
     // the pass record in one snapshot, the vectors in chunks of CH per thread
@@ -45,6 +53,9 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
         S.q = D.rec->q;
         S.p = D.rec->p;
         S.d_p = D.rec->d_p;
+#if SPX_STEP_LONG
+        s_nfl = D.lrec->nflip;
+#endif
     }
     __syncthreads();
     double* y = S.y_buf ? P.y1 : P.y0;
@@ -55,7 +66,12 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
         const int64_t q = S.q, p = S.p;
         const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
 #if SPX_STEP_BOX
+#if SPX_STEP_LONG
+        const bool flp = s_nfl > 0;
+        const double aq = al[q], xq0 = flp ? P.x_b[q] - D.fl[q] : P.x_b[q], ubq = D.ub_B[q];
+#else
         const double aq = al[q], xq0 = P.x_b[q], ubq = D.ub_B[q];  // (every thread: the same words)
+#endif
         const int32_t sgn = D.rec->s;
         const double xq = sgn > 0 ? xq0 : xq0 - ubq;  // delta_q
         const double u_p = D.ub[p];
@@ -93,6 +109,9 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
 #if SPX_STEP_SE
                 ev[u] = i < m ? D.wex[i] : 0.0;
                 tv[u] = i < m ? D.tau[i] : 0.0;
+#endif
+#if SPX_STEP_LONG
+                if (flp && i < m) xv[u] -= D.fl[i];
 #endif
             }
 #pragma unroll
@@ -140,6 +159,9 @@ __global__ __launch_bounds__(1024) void SPX_STEP_KERNEL(Params P, SPX_STEP_ARGS 
             st->iter = it + 1;
             record_pivot(P, it, p, q);
             D.rec->fresh = 0;
+#if SPX_STEP_LONG
+            D.lrec->nflip = 0;
+#endif
         }
         it += 1;
         qprev = q;
