@@ -563,8 +563,12 @@ int spx_info(spx_ctx* ctx, int64_t* m, int64_t* n, int64_t* ld,
  * the dense B_w (0), [14] k_ftran_bc rows per wave (0: not in use), [15]
  * (after spx_mbox_attach) loop passes exchange through the mailboxes inside
  * k_price and k_ftran_bc (1: the fused exchange; SPX_MBOX_FUSED=0 turns it
- * off) or with a k_exchange launch per pass (0). */
-#define SPX_CONFIG_FIELDS 16
+ * off) or with a k_exchange launch per pass (0), [16] the window's passes
+ * after its first price from the listed rows of A (1: compact pricing, one
+ * rank over the compact operand, Dantzig or Devex; SPX_DENSE_PRICE=1 turns it
+ * off) or stream A (0: also once the list has outgrown the stored rows,
+ * SPX_CPRICE_CAP). */
+#define SPX_CONFIG_FIELDS 17
 int spx_config(spx_ctx* ctx, int32_t out[SPX_CONFIG_FIELDS]);
 
 /* Columns of B^-1 the FTRAN stream reads per row: m, or with the eta window's
@@ -582,9 +586,11 @@ int spx_ftran_cols(spx_ctx* ctx, int32_t* cols);
  * before the next pass when it equals [7]), [7] the window size KW (0 =
  * explicit B^-1), [8] persistent launches whose grid was found not
  * co-resident (another stream or process held CUs; the context then
- * switched to two-kernel passes and made those pivots that way), [9] batch
- * hipGraphs built (captured, instantiated and uploaded; 0 or 1 per context,
- * rebuilt once after spx_mbox_attach). */
+ * switched to two-kernel passes and made those pivots that way), [9] times
+ * the batch hipGraph was built (captured, instantiated and uploaded; 0 or 1
+ * per context, rebuilt once after spx_mbox_attach).  A context that prices
+ * compactly (spx_config [16]) builds the batch twice in that one go, once per
+ * pricing mode, so that a solve crossing into dense pricing builds nothing. */
 #define SPX_DISPATCH_FIELDS 10
 int spx_dispatch_stats(spx_ctx* ctx, int64_t out[SPX_DISPATCH_FIELDS]);
 

@@ -512,7 +512,11 @@ class Context:
         return v.value
 
     def dispatch_stats(self):
-        """Monotone counts of what the loop enqueued (spx_dispatch_stats)."""
+        """Monotone counts of what the loop enqueued (spx_dispatch_stats).
+        ``graph_builds`` counts the times the library stopped to build its
+        batch graph, not the graphs: a context that prices compactly
+        (``config()["compact_price"]``) captures the batch once per pricing
+        mode in that one stop, and reports 1."""
         out = (ctypes.c_int64 * 10)()
         check(self._L.spx_dispatch_stats(self._h, out))
         keys = ("eager_passes", "graph_launches", "graph_passes", "persistent_launches", "persistent_passes",
@@ -521,11 +525,11 @@ class Context:
 
     def config(self):
         """Resolved representation and launch geometry (spx_config)."""
-        out = (ctypes.c_int32 * 16)()
+        out = (ctypes.c_int32 * 17)()
         check(self._L.spx_config(self._h, out))
         keys = ("window", "price_block", "price_grid", "price_lds", "update_block", "update_rows", "update_grid",
                 "graph_batch", "persistent", "loop_block", "tableau", "loop_grid", "defer_tail", "compact_fold",
-                "ftran_rows_per_wave", "mbox_fused")
+                "ftran_rows_per_wave", "mbox_fused", "compact_price")
         cfg = dict(zip(keys, list(out)))
         cfg["dual_pricing"] = self._dual_pricing  # (the library keeps it outside spx_config)
         cfg["dual_ratio"] = self._dual_ratio

@@ -118,6 +118,8 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&x->st_host), sizeof(DevState), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&x->limit_host), sizeof(int64_t), hipHostMallocDefault));
     std::memset(x->st_host, 0, sizeof(DevState));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&x->bcn_host), BC_N_WORDS * sizeof(int32_t), hipHostMallocDefault));
+    std::memset(x->bcn_host, 0, BC_N_WORDS * sizeof(int32_t));
 
     x->m = m;
     x->n = n;
@@ -387,14 +389,16 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
         uc.grid = (int)std::max<int64_t>(1, (P.mloc + 255) / 256);
     }
 
-    SPX_TRY(x->alloc(&P.price_partials, (size_t)pc.grid));
+    // (compact pricing, k_price WM 6, holds several workgroups per CU and
+    // shares these slots: its grid is set with its LDS, cprice_setup)
+    P.price_cap = std::max<int64_t>(pc.grid, 8LL * x->cus);
+    SPX_TRY(x->alloc(&P.price_partials, (size_t)P.price_cap));
     P.upd_cap = uc.grid;
     SPX_TRY(x->alloc(&P.upd_soa, (size_t)(7 * uc.grid)));
     if (!P.row_shard && !P.tab && !(x->opts.flags & SPX_FLAG_COUNTED_TAIL))
         SPX_TRY(x->alloc(&P.upd_tag, (size_t)(UPD_WORDS * uc.grid)));
-    P.price_cap = pc.grid;
     if (!P.tab && !(x->opts.flags & SPX_FLAG_COUNTED_TAIL))
-        SPX_TRY(x->alloc(&P.price_tag, (size_t)(PRICE_WORDS * pc.grid)));
+        SPX_TRY(x->alloc(&P.price_tag, (size_t)(PRICE_WORDS * P.price_cap)));
     // the persistent loop kernel replaces the two-kernel pass where it applies
     if (P.win && !P.tab && G == 1 && !P.row_shard && P.ratio != RATIO_HARRIS && !P.steep &&
         !(x->opts.flags & SPX_FLAG_STAMPS) &&
@@ -511,6 +515,9 @@ int do_reset(spx_ctx* x) {
         HIP_TRY(hipMemsetAsync(x->P.rleft, 0, (size_t)x->L * sizeof(int32_t), x->stream));
         HIP_TRY(hipMemsetAsync(x->P.rmap, 0xFF, (size_t)x->L * sizeof(int32_t), x->stream));
         HIP_TRY(hipMemsetAsync(x->P.bc_n, 0, BC_N_WORDS * sizeof(int32_t), x->stream));
+        // compact pricing: no list, so no lane has a run (k_as_order writes
+        // these only where the list changes: at a fold or a rebuild)
+        if (x->P.as_off) HIP_TRY(hipMemsetAsync(x->P.as_off, 0, 65 * sizeof(int32_t), x->stream));
     }
     SPX_TRY(tab_rebuild(x, true));
     HIP_TRY(hipStreamSynchronize(x->stream));
@@ -518,6 +525,9 @@ int do_reset(spx_ctx* x) {
     x->status = SPX_STATUS_MAX_ITER;
     x->stepped_price = false;
     x->nw = 0;
+    x->dw_ok = false;
+    x->s_list = 0;
+    x->cp_now = x->cp_ok;
     return SPX_OK;
 }
 
@@ -562,7 +572,16 @@ int enqueue_pass(spx_ctx* x, bool timed) {
         if (f0) HIP_TRY(hipEventRecord(f0, x->stream));
         HIP_TRY(launch_fold(x->P, x->P.win, x->cus, x->stream));
         if (f1) HIP_TRY(hipEventRecord(f1, x->stream));
+        x->dw_ok = false;
     }
+    // compact pricing: the first pass after a fold, reset or rebuild is the
+    // dense stream that also stores dw (tau <= 0 there); the window's other
+    // passes price from AS and dw.  Where dw is stale in mid-window (the
+    // stepping API made pivots since the fold) the plain dense pass runs until
+    // the next fold.  Decided from the window position alone, so the same
+    // passes are dense however the calls are chunked or dispatched
+    const bool cp_open = x->cp_now && !x->dw_ok && (fold || x->nw <= 1);
+    const bool cp_pass = x->cp_now && x->dw_ok;
     advance_window(x, fold);
     // steepest edge: after the fold, before pricing (k_se_part skipped when the
     // previous pass's FTRAN left its sums and no fold came between)
@@ -572,7 +591,12 @@ int enqueue_pass(spx_ctx* x, bool timed) {
     Pp.defer_price = x->defer_ok ? 1 : 0;
     Pp.defer_tail = x->defer_tail ? 1 : 0;
     Pp.mbox_fused = (x->mbox_ready && x->mbox_fused) ? 1 : 0;
-    HIP_TRY(launch_price(Pp, x->pcfg, x->stream, p0, p1));
+    if (cp_pass) Pp.price_grid = x->ccfg.grid;  // the FTRAN pass reduces this launch's partials
+    HIP_TRY(launch_price(Pp, cp_pass ? x->ccfg : (cp_open ? x->dcfg : x->pcfg), x->stream, p0, p1));
+    if (cp_open) {
+        HIP_TRY(launch_dw_basic(Pp, x->stream));
+        x->dw_ok = true;
+    }
     if (x->use_comm) {
         if (x->mbox_ready) {
             if (!Pp.mbox_fused) HIP_TRY(launch_exchange(x->P, x->stream));
@@ -594,13 +618,17 @@ int enqueue_pass(spx_ctx* x, bool timed) {
     return SPX_OK;
 }
 
+// (the batch of the current pricing mode, x->cp_now: each mode has its graph)
 int build_graph(spx_ctx* x) {
-    if (x->graph_exec || x->batch <= 0) return SPX_OK;
+    hipGraphExec_t& gexec = x->cp_now ? x->graph_exec_c : x->graph_exec;
+    hipGraph_t& gkeep = x->cp_now ? x->graph_c : x->graph;
+    if (gexec || x->batch <= 0) return SPX_OK;
     if (x->use_comm && !x->comm_ready && !x->mbox_ready)
         return fail(SPX_ERR_STATE, "nranks > 1 but neither spx_attach_comm nor spx_mbox_attach was called");
     HIP_TRY(hipStreamBeginCapture(x->stream, hipStreamCaptureModeThreadLocal));
     int rc = SPX_OK;
     const int nw_keep = x->nw;
+    const bool dw_keep = x->dw_ok;
     if (x->P.win) x->nw = x->P.win;  // a batch starts with a fold (see iterate)
     x->capturing = true;
     x->graph_folds = 0;
@@ -608,14 +636,15 @@ int build_graph(spx_ctx* x) {
     x->capturing = false;
     x->se_chain = false;  // (nothing captured has run)
     x->nw = nw_keep;
+    x->dw_ok = dw_keep;
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(x->stream, &g);
     hipError_t ei = hipSuccess;
-    if (rc == SPX_OK && e == hipSuccess) ei = hipGraphInstantiate(&x->graph_exec, g, nullptr, nullptr, 0);
+    if (rc == SPX_OK && e == hipSuccess) ei = hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0);
     if (x->use_comm && (rc != SPX_OK || e != hipSuccess || ei != hipSuccess)) {
         // RCCL calls that cannot be captured: launch the passes eagerly
         if (g) (void)hipGraphDestroy(g);
-        x->graph_exec = nullptr;
+        gexec = nullptr;
         x->batch = 0;
         x->graph_fallback = true;
         (void)hipGetLastError();
@@ -623,14 +652,32 @@ int build_graph(spx_ctx* x) {
     }
     if (rc != SPX_OK) return rc;
     if (e != hipSuccess) return fail(SPX_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    x->graph = g;
+    gkeep = g;
     if (ei != hipSuccess) return fail(SPX_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ei));
     ++x->n_graph_builds;
     // the first launch of a fresh graph pays its upload (measured 13 ms for a
     // 63-node graph): do it here, not inside somebody's timed loop
-    HIP_TRY(hipGraphUpload(x->graph_exec, x->stream));
+    HIP_TRY(hipGraphUpload(gexec, x->stream));
     HIP_TRY(hipStreamSynchronize(x->stream));
     return SPX_OK;
+}
+
+// both batch graphs of a context that can price compactly (a solve crosses
+// into dense pricing when its list outgrows AS): nothing is captured later,
+// inside somebody's timed region.  One build in spx_dispatch_stats' count:
+// it counts the times the library stopped to build, not the graphs
+int build_graphs(spx_ctx* x) {
+    if (!x->cp_ok) return build_graph(x);
+    const bool keep = x->cp_now;
+    const int64_t built = x->n_graph_builds;
+    int rc = SPX_OK;
+    for (int mode = 1; mode >= 0 && rc == SPX_OK; --mode) {
+        x->cp_now = mode != 0;
+        rc = build_graph(x);
+    }
+    x->cp_now = keep;
+    if (x->n_graph_builds > built) x->n_graph_builds = built + 1;
+    return rc;
 }
 
 // The ticketed pricing tail's coverage (k_price, Params::price_dyn): each
@@ -772,6 +819,8 @@ int iterate_persist(spx_ctx* x, int64_t k) {
     return SPX_OK;
 }
 
+int iterate_passes(spx_ctx* x, int64_t k);
+
 int iterate_raw(spx_ctx* x, int64_t k) {
     if (x->status != SPX_STATUS_MAX_ITER || k <= 0) return SPX_OK;
     if (x->algo == SPX_ALGO_DUAL) return iterate_dual(x, k);
@@ -780,6 +829,35 @@ int iterate_raw(spx_ctx* x, int64_t k) {
         return iterate_persist(x, k);
     }
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_price was called without spx_pivot");
+    if (!x->cp_ok) return iterate_passes(x, k);
+    // Compact pricing needs the list inside AS at every fold of the passes
+    // enqueued here.  The list grows by at most one row per pivot and the host
+    // knows its length as of the last readback (s_list, as of the last fold;
+    // the open window's nw pivots add at most nw rows at the next one), so a
+    // chunk of `room` pivots is safe; a long call is cut into such chunks,
+    // each ending with the readback every call ends with.  With room for
+    // fewer than 16 pivots the rest of the call prices densely, whatever its
+    // length, and so does every later call until the window folds (nw falls
+    // back) or a reset or a rebuild shortens the list: the choice depends on
+    // the list and the window position, never on how long the call is.
+    int64_t left = k;
+    while (left > 0 && x->status == SPX_STATUS_MAX_ITER) {
+        const int64_t room = (int64_t)x->P.as_cap - x->s_list - x->nw;
+        const bool cp = room >= 16;
+        const int64_t chunk = cp ? std::min(left, room) : left;
+        if (cp != x->cp_now) {
+            x->cp_now = cp;
+            x->dw_ok = false;
+        }
+        const int64_t before = x->pivots;
+        SPX_TRY(iterate_passes(x, chunk));
+        left -= chunk;
+        if (x->pivots == before) break;
+    }
+    return SPX_OK;
+}
+
+int iterate_passes(spx_ctx* x, int64_t k) {
     SPX_TRY(set_limit(x, x->pivots + k));
     x->se_chain = false;  // (steepest edge: the fused sums are used within one call only)
     // exactly k passes: whole captured batches, then the remainder eagerly.
@@ -792,8 +870,10 @@ int iterate_raw(spx_ctx* x, int64_t k) {
             for (int64_t i = 0; i < lead; ++i) SPX_TRY(enqueue_pass(x, x->timing));
             left -= lead;
             SPX_TRY(build_graph(x));
+            hipGraphExec_t gexec = x->cp_now ? x->graph_exec_c : x->graph_exec;
             const int64_t reps = left / x->batch;
-            for (int64_t i = 0; i < reps; ++i) HIP_TRY(hipGraphLaunch(x->graph_exec, x->stream));
+            for (int64_t i = 0; i < reps; ++i) HIP_TRY(hipGraphLaunch(gexec, x->stream));
+            if (reps > 0 && x->cp_now) x->dw_ok = true;  // (the batch's last window; the next pass folds)
             x->se_chain = false;
             x->n_graph_launch += reps;
             x->n_graph_pass += reps * x->batch;
@@ -897,6 +977,7 @@ int reinvert_basis(spx_ctx* x, const int64_t* basis) {
     }
     SPX_TRY(tab_rebuild(x, false));
     x->nw = 0;
+    x->dw_ok = false;
     dual_on_reinvert(x);
     return read_state(x);
 }
@@ -1002,10 +1083,72 @@ int set_slack_flags(spx_ctx* x) {
     return SPX_OK;
 }
 
+// Compact pricing (Params::AS, spx_device.h; after set_slack_flags, which
+// decides the compact operand and the deferred tail): one rank, two-kernel
+// window passes over the compact operand, Dantzig and Devex (steepest edge's
+// third dot takes a dense vector).  SPX_DENSE_PRICE=1 keeps the stream.
+// Rows of AS: m / 4 by default, at least 512 and at most 4096 (C3: 1024,
+// twice the 456 its whole solve reaches; a row costs 8 n bytes: 134 MB
+// there), SPX_CPRICE_CAP lowers it (tests).  Measured at C3:
+// 46.8 us per pass at S = 800-876 against 75.8 streaming, so the cap is set by
+// memory, not by where compact stops paying.  No room for AS: dense pricing.
+// Params::AS is set last, once everything beside it exists: the fold's
+// k_as_rows / k_as_order run exactly when compact passes can.
+int cprice_setup(spx_ctx* x) {
+    Params& P = x->P;
+    if (!(P.bc && !P.steep && x->opts.nranks == 1 && !x->use_comm && !x->persist && !P.row_shard &&
+          (x->pcfg.wm == 1 || x->pcfg.wm == 2) && !env_on("SPX_DENSE_PRICE")))
+        return SPX_OK;
+    int64_t cap = std::min<int64_t>(4096, std::max<int64_t>(512, round_up((x->m + 3) / 4, 64)));
+    if (const char* ev = std::getenv("SPX_CPRICE_CAP")) {
+        const int64_t v = std::atoll(ev);
+        if (v >= 1 && v < cap) cap = v;
+    }
+    void* d = nullptr;
+    const size_t bytes = (size_t)(cap * x->n) * sizeof(double);
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return SPX_OK;
+    }
+    x->allocs.push_back(d);
+    HIP_TRY(hipMemsetAsync(d, 0, bytes, x->stream));
+    SPX_TRY(x->alloc(&P.dw, (size_t)x->n));
+    SPX_TRY(x->alloc(&P.as_ord, (size_t)cap));
+    SPX_TRY(x->alloc(&P.as_off, (size_t)65));
+    PriceCfg& cc = x->ccfg;
+    // 256 threads unless the caller chose: a compact pass stages no vector in
+    // LDS, so three such workgroups fit a CU (12 waves against the 8 of one
+    // 512-thread workgroup), and a wave prices one column at a time.  The
+    // deferred tail reduces in either shape
+    cc.block = (x->opts.price_block == 512 || x->opts.price_block == 1024) ? x->pcfg.block : 256;
+    if (x->defer_tail && cc.block == 1024) cc.block = 512;
+    cc.lds_y = false;
+    cc.wm = 6;
+    cc.tk = false;
+    // the pending row's listed entries, their list positions and rows
+    cc.lds_bytes = (size_t)(cc.block / 64) * sizeof(PricePartial) + 16 + (size_t)round_up(cap, 2) * 16;
+    x->dcfg = x->pcfg;
+    x->dcfg.dw = true;
+    int per_cu = 0, per_cu_d = 0;
+    HIP_TRY(price_prepare(cc, &per_cu));
+    HIP_TRY(price_prepare(x->dcfg, &per_cu_d));  // (its LDS attribute)
+    // one wave per column; every workgroup the CUs hold at once, within the
+    // partial slots setup_common allocated
+    const int waves = cc.block / 64;
+    cc.grid = (int)std::max<int64_t>(1, std::min<int64_t>({(x->max_local_cols + waves - 1) / waves,
+                                                           (int64_t)x->cus * std::max(per_cu, 1), P.price_cap}));
+    if (x->opts.price_grid > 0) cc.grid = (int)std::min<int64_t>(x->opts.price_grid, P.price_cap);
+    P.as_ld = cap;
+    P.as_cap = (int32_t)cap;
+    P.AS = static_cast<double*>(d);
+    x->cp_ok = x->cp_now = true;
+    return SPX_OK;
+}
+
 int create_tail(spx_ctx* x) {
     SPX_TRY(do_reset(x));
     if (x->algo == SPX_ALGO_DUAL) return dual_setup(x);  // (a later switch to primal captures its graph on its first batch)
-    if (!x->use_comm && !x->persist) SPX_TRY(build_graph(x));  // capture + upload now (off any timed path)
+    if (!x->use_comm && !x->persist) SPX_TRY(build_graphs(x));  // capture + upload now (off any timed path)
     return SPX_OK;
 }
 
@@ -1057,12 +1200,18 @@ int pass_events(spx_ctx* x, hipEvent_t* p0, hipEvent_t* p1, hipEvent_t* u0, hipE
 
 int read_state(spx_ctx* x) {
     HIP_TRY(hipMemcpyAsync(x->st_host, x->P.st, sizeof(DevState), hipMemcpyDeviceToHost, x->stream));
+    if (x->P.bc_n)
+        HIP_TRY(hipMemcpyAsync(x->bcn_host, x->P.bc_n, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
     HIP_TRY(hipStreamSynchronize(x->stream));
+    if (x->P.bc_n) x->s_list = x->bcn_host[0];
     x->pivots = x->st_host->iter;
     x->status = x->st_host->status;  // ST_RUNNING == SPX_STATUS_MAX_ITER
     x->nw = x->st_host->nw;
     if (x->status == ST_WINDOW_FULL) return fail(SPX_ERR_STATE, "internal error: eta window overflow");
     if (x->status == ST_HANDOFF_TIMEOUT) return fail(SPX_ERR_STATE, "internal error: ratio-test hand-off timed out");
+    if (x->status == ST_CPRICE_STATE)
+        return fail(SPX_ERR_STATE, "internal error: compact pricing without its rows of A or a valid dw (list %d, rows %d)",
+                    x->s_list, x->P.as_cap);
     SPX_TRY(check_tickets(x));
     return SPX_OK;
 }
@@ -1075,6 +1224,7 @@ int flush(spx_ctx* x) {
         HIP_TRY(launch_fold(x->P, 2, x->cus, x->stream));
         HIP_TRY(launch_tab_binv(x->P, x->stream));  // tableau without k_fold: B_w from T_w
         x->nw = std::min(x->nw, 1);
+        x->dw_ok = false;
     }
     HIP_TRY(launch_flush(x->P, x->stream));
     return SPX_OK;
@@ -1119,6 +1269,7 @@ int spx_create(spx_ctx** out, int64_t m, int64_t n, const double* A, const doubl
         if (e != hipSuccess) rc = fail(SPX_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
     }
     if (rc == SPX_OK) rc = set_slack_flags(x);
+    if (rc == SPX_OK) rc = cprice_setup(x);
     if (rc == SPX_OK) rc = create_tail(x);
     if (rc != SPX_OK) {
         std::string keep = g_err;
@@ -1143,6 +1294,7 @@ int spx_create_generated(spx_ctx** out, int64_t m, int64_t n, uint64_t seed, con
         if (e != hipSuccess) rc = fail(SPX_ERR_HIP, "generate failed: %s", hipGetErrorString(e));
     }
     if (rc == SPX_OK) rc = set_slack_flags(x);
+    if (rc == SPX_OK) rc = cprice_setup(x);
     if (rc == SPX_OK) rc = create_tail(x);
     if (rc != SPX_OK) {
         std::string keep = g_err;
@@ -1159,6 +1311,8 @@ void spx_destroy(spx_ctx* x) {
     if (x->stream) (void)hipStreamSynchronize(x->stream);
     if (x->graph_exec) (void)hipGraphExecDestroy(x->graph_exec);
     if (x->graph) (void)hipGraphDestroy(x->graph);
+    if (x->graph_exec_c) (void)hipGraphExecDestroy(x->graph_exec_c);
+    if (x->graph_c) (void)hipGraphDestroy(x->graph_c);
     for (hipEvent_t e : {x->ev_sent, x->ev_recv, x->ev_sent2, x->ev_recv2})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_price) (void)hipEventDestroy(e);
@@ -1171,6 +1325,7 @@ void spx_destroy(spx_ctx* x) {
     for (void* p : x->allocs) (void)hipFree(p);
     if (x->st_host) (void)hipHostFree(x->st_host);
     if (x->limit_host) (void)hipHostFree(x->limit_host);
+    if (x->bcn_host) (void)hipHostFree(x->bcn_host);
     if (x->stream) (void)hipStreamDestroy(x->stream);
     delete x;
 }
@@ -1647,6 +1802,7 @@ int spx_price(spx_ctx* x, int64_t* p, double* min_e, int32_t* optimal) {
     SPX_TRY(set_limit(x, x->pivots + 1));
     const bool fold = fold_due(x);
     if (fold) HIP_TRY(launch_fold(x->P, x->P.win, x->cus, x->stream));
+    if (fold) x->dw_ok = false;
     ++x->n_eager;
     x->n_folds += fold ? 1 : 0;
     HIP_TRY(launch_se_prep(x->P, x->stream));
@@ -1718,7 +1874,7 @@ int spx_prepare(spx_ctx* x) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (x->persist) return SPX_OK;  // one launch per window: nothing to capture
     if (x->algo == SPX_ALGO_DUAL) return SPX_OK;  // dual passes are eager launches
-    return build_graph(x);
+    return build_graphs(x);
 }
 
 int spx_pass_times(spx_ctx* x, double out[3], int64_t* passes) {
@@ -1836,6 +1992,15 @@ int spx_info(spx_ctx* x, int64_t* m, int64_t* n, int64_t* ld, int64_t* local_nb,
         streamed -= (x->P.k_hi - x->P.k_lo) - basic_slacks;
     }
     if (bp) *bp = 8.0 * (double)(x->m + 1) * (double)streamed;
+    if (bp && x->cp_ok && x->cp_now && x->P.win > 2) {
+        // compact pricing: the mean launch of a window -- KW - 2 compact passes
+        // (per priced column its S entries of AS, dw[j], A[q, j], the mean Wt
+        // row and the new Wt entry) and the dense pass that opens it
+        const double kw = (double)x->P.win;
+        const double per_col = 8.0 * ((double)x->s_list + 2.0 + 0.5 * (kw - 1.0) + 1.0);
+        const double compact = per_col * (double)x->st_host->nb_count;
+        *bp = ((kw - 2.0) * compact + *bp) / (kw - 1.0);
+    }
     // update bytes per pivot: B^-1 read + write, or (eta window) the B_w
     // FTRAN stream (its non-unit columns with the compact operand) plus the
     // fold's read + write spread over its KW-1 pivots
@@ -1877,6 +2042,7 @@ int spx_config(spx_ctx* x, int32_t out[SPX_CONFIG_FIELDS]) {
     out[13] = (x->P.bc && x->P.cfold) ? 1 : 0;
     out[14] = (x->P.bc && x->ucfg.rows == 1 && x->ucfg.bc_entry) ? x->ucfg.bc_entry : 0;
     out[15] = (x->mbox_ready && x->mbox_fused) ? 1 : 0;
+    out[16] = (x->cp_ok && x->cp_now) ? 1 : 0;
     return SPX_OK;
 }
 

@@ -129,9 +129,24 @@ struct spx_ctx {
     bool se_chain = false;
     int64_t se_rows = 0;
 
-    // graph replay of `batch` passes
+    // compact pricing (Params::AS).  cp_ok: allocated and applicable; cp_now:
+    // the passes being enqueued price compactly (decided per chunk of an
+    // iterate call from the list length, iterate_raw); dw_ok: dw belongs to
+    // the current y_w (false after every fold, rebuild and readback flush:
+    // the next pass is then the dense one that stores it).  ccfg / dcfg: the
+    // compact launch and the dense launch that stores dw; s_list: bc_n[0] as
+    // of the last readback (bcn_host: its pinned mirror)
+    bool cp_ok = false, cp_now = false, dw_ok = false;
+    spx::PriceCfg ccfg{}, dcfg{};
+    int32_t s_list = 0;
+    int32_t* bcn_host = nullptr;
+
+    // graph replay of `batch` passes (graph_c / graph_exec_c: the batch with
+    // compact pricing; both are captured by spx_prepare)
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec_c = nullptr;
+    hipGraph_t graph_c = nullptr;
     int batch = 0;
 
     // in-process group exchange

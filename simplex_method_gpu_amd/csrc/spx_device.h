@@ -64,7 +64,8 @@ enum : int32_t {
     ST_UNBOUNDED = 2,
     ST_INFEASIBLE = 4,  // dual loop (spx_dual.h): a row with x_b < 0 and no ratio-test candidate
     ST_WINDOW_FULL = 16,
-    ST_HANDOFF_TIMEOUT = 17
+    ST_HANDOFF_TIMEOUT = 17,
+    ST_CPRICE_STATE = 18  // compact pricing (Params::AS) found a list past its rows, or no valid dw
 };
 
 // (value, global index) candidate; the order is value, then smallest index —
@@ -354,6 +355,31 @@ struct Params {
     int32_t* rmap;
     int32_t* rleft;
     int32_t* bc_n;
+    // compact pricing (DESIGN.md §4 "compact pricing"; one rank, P.bc, Dantzig
+    // and Devex).  Row q of B_w is e_q (while column q is unit, rmap[q] < 0)
+    // plus bc[q][0..S) at the listed positions, so
+    //   B_w[q,:] . A_j = (rmap[q] < 0 ? A[q, j] : 0) + sum_{c<S} bc[q][c] AS[c][j]
+    // with AS[c][j] = A[rlist[c], j]: the listed rows of A, an exact copy,
+    // stored by column (column j's entries at AS + j * as_ld, as_ld = as_cap:
+    // a wave prices one column and reads its S entries from one short run);
+    // rows appended where the list is (k_as_rows after k_bc_list).  The sum
+    // runs in the dense stream's order, so it has the stream's bits (k_price
+    // WM 6): as_ord = the list positions sorted by the stream's lane of the
+    // row ((row / 2) mod 64), then by row; as_off[l] = where lane l's run
+    // starts (65 entries; k_as_order after every list change).  y_w . A_j - c_j
+    // is constant inside a window: the window's first pass is the dense stream
+    // (k_price<.., DW>) and stores it in dw[j] (n entries; k_dw_basic adds the
+    // basic columns, which may leave inside the window); the other passes
+    // (k_price WM 6) price from AS, dw and the Wt rows.  bc_n[5] = 1 while dw
+    // belongs to the current y_w (set by the dense pass, cleared by
+    // k_bc_list, i.e. by every fold and rebuild); a compact pass that finds
+    // it 0, or S > as_cap, stops with ST_CPRICE_STATE.  nullptr: dense pricing.
+    double* AS;
+    int64_t as_ld;
+    int32_t as_cap;
+    int32_t pad_as;
+    int32_t* as_ord;
+    int32_t* as_off;
 };
 
 // the compact operand's active buffer (bc_n[2])

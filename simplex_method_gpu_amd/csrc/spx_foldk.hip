@@ -110,6 +110,7 @@ __global__ __launch_bounds__(1024) void k_bc_list(Params P, int min_nw) {
         s_base = P.bc_n[0];
         P.bc_n[3] = P.bc_n[0];
         P.bc_n[4] = P.bc_n[1];
+        P.bc_n[5] = 0;  // compact pricing: y_w is about to change (or B_w was rebuilt): dw is stale
     }
     __syncthreads();
     for (int64_t k0 = 0; k0 < P.m; k0 += 1024) {
@@ -141,6 +142,56 @@ __global__ __launch_bounds__(1024) void k_bc_list(Params P, int min_nw) {
         P.bc_n[1] = s_base > 0 ? ((s_base + 63) / 64) * 64 : 64;
     }
 }
+// Compact pricing (Params::AS): the rows of A the list gained, AS[j][c] =
+// A[rlist[c], j] for c in [bc_n[3], S), right after k_bc_list (same min_nw
+// test, before k_cfold resets the window count).  A rebuild starts from
+// bc_n[0] = 0, so it copies every row.  One thread per (column, new row):
+// the threads of a column read its scattered elements and store one run.
+// Rows past as_cap are not copied (a compact pass stops before reading them).
+__global__ __launch_bounds__(256) void k_as_rows(Params P, int min_nw) {
+    if (min_nw > 0) {
+        const int nw = P.st->nw;
+        if (nw < min_nw || nw < 2) return;
+    }
+    const int S0 = P.bc_n[3];
+    const int S = P.bc_n[0] < P.as_cap ? P.bc_n[0] : P.as_cap;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= P.n) return;
+    for (int c = S0 + (int)(threadIdx.x & 63); c < S; c += 64)
+        P.AS[j * P.as_ld + c] = P.A[j * P.L + P.rlist[c]];
+}
+// ... and the order its sum runs in (spx_device.h): rank of every list
+// position under the key (lane of the dense stream, row), by counting (one
+// workgroup; S^2 / 1024 compares per thread, S <= as_cap <= 4096)
+__global__ __launch_bounds__(1024) void k_as_order(Params P, int min_nw) {
+    __shared__ int s_row[4096];
+    if (min_nw > 0) {
+        const int nw = P.st->nw;
+        if (nw < min_nw || nw < 2) return;
+    }
+    const int S = P.bc_n[0] < P.as_cap ? P.bc_n[0] : P.as_cap;
+    const int tid = threadIdx.x;
+    for (int c = tid; c < S; c += 1024) s_row[c] = P.rlist[c];
+    __syncthreads();
+    auto key = [](int r) { return (int64_t)((r >> 1) & 63) << 32 | (int64_t)r; };
+    for (int c = tid; c < S; c += 1024) {
+        const int64_t kc = key(s_row[c]);
+        int rank = 0;
+        for (int d = 0; d < S; ++d) rank += key(s_row[d]) < kc ? 1 : 0;
+        P.as_ord[rank] = c;  // (rows are distinct: the ranks are a permutation)
+    }
+    if (tid < 65) {
+        int off = 0;
+        for (int d = 0; d < S; ++d) off += ((s_row[d] >> 1) & 63) < tid ? 1 : 0;
+        P.as_off[tid] = off;
+    }
+}
+static void launch_as_rows(const Params& P, int min_nw, hipStream_t s) {
+    if (!P.AS) return;
+    hipLaunchKernelGGL(k_as_rows, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, s, P, min_nw);
+    hipLaunchKernelGGL(k_as_order, dim3(1), dim3(1024), 0, s, P, min_nw);
+}
+
 constexpr int BC_ROWS = 4;  // rows per k_bc_gather workgroup
 __global__ __launch_bounds__(256) void k_bc_gather(Params P) {
     const int S = P.bc_n[0];
@@ -157,6 +208,7 @@ __global__ __launch_bounds__(256) void k_bc_gather(Params P) {
 hipError_t launch_compact(const Params& P, hipStream_t s) {
     if (!P.bc) return hipSuccess;
     hipLaunchKernelGGL(k_bc_list, dim3(1), dim3(1024), 0, s, P, 0);
+    launch_as_rows(P, 0, s);
     hipLaunchKernelGGL(k_bc_gather, dim3((unsigned)((P.m + BC_ROWS - 1) / BC_ROWS)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
@@ -455,6 +507,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_cfold(Params P, int min_nw) {
 // k_cfold over the listed columns only (P.bc, one workgroup per CU)
 hipError_t launch_cfold(const Params& P, int min_nw, int cus, hipStream_t s) {
     hipLaunchKernelGGL(k_bc_list, dim3(1), dim3(1024), 0, s, P, min_nw);
+    launch_as_rows(P, min_nw, s);
     // every column group of the list needs a workgroup (m > 16,384: more
     // groups than CUs)
     const int64_t ngmax = P.L / 64;

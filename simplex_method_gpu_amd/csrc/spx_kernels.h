@@ -48,10 +48,12 @@ struct PriceCfg {
     int block;         // 256 / 512 / 1024 threads
     bool lds_y;        // stage y in LDS (L*8 bytes) or read it from global
     int wm;            // 0 explicit B^-1; eta window: 1 base row in LDS, 2 in global; 3 tableau;
-                       // 4 / 5 = 1 / 2 with steepest edge (B_w^T alpha in LDS / global)
+                       // 4 / 5 = 1 / 2 with steepest edge (B_w^T alpha in LDS / global);
+                       // 6 compact pricing (Params::AS: the listed rows of A, dw, the Wt rows)
     size_t lds_bytes;  // dynamic LDS per workgroup
     int grid;          // workgroups (persistent-style, grid-stride over columns)
     bool tk = false;   // wm 1: the instantiation with the ticketed tail (Params::price_dyn)
+    bool dw = false;   // wm 1 / 2: the instantiation that also stores dw[j] (opens a compact-priced window)
 };
 
 struct UpdateCfg {
@@ -65,6 +67,8 @@ struct UpdateCfg {
 
 hipError_t price_prepare(const PriceCfg& c, int* blocks_per_cu);
 hipError_t launch_price(const Params& P, const PriceCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+// compact pricing: dw for the basic columns, after the dense pass that stored the others
+hipError_t launch_dw_basic(const Params& P, hipStream_t s);
 hipError_t launch_update(const Params& P, const UpdateCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 // a pending deferred ratio-test tail (Params::defer_tail), applied on its own
 hipError_t launch_apply_tail(const Params& P, hipStream_t s);

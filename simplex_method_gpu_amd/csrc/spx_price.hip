@@ -75,11 +75,18 @@ __device__ __forceinline__ int best_wave(const PricePartial* red) {
 // TK: the ticketed tail compiled in for WM 1 (a separate instantiation, so the
 // static C3 pass keeps its code: carrying the disabled ticket branches cost
 // it 0.5 us per pass); WM 2 always carries it
-template <int BLOCK, bool LDS_Y, int WM, bool TK = false>
+// WM 6 = compact pricing (P.AS, spx_device.h): no A stream; a column's base
+// row dot comes from the listed rows of A, y_w . A_j - c_j from dw[j].
+// DW: the dense pass (WM 1 / 2) that opens a compact-priced window: it also
+// stores dw[j] for every column it prices and marks dw valid (its own
+// instantiations, so the plain dense pass keeps its code)
+template <int BLOCK, bool LDS_Y, int WM, bool TK = false, bool DW = false>
 __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
     DevState* st = P.st;
     constexpr int WAVES = BLOCK / 64;
     constexpr bool WIN = WM != 0;
+    constexpr bool CP = WM == 6;
+    static_assert(!DW || WM == 1 || WM == 2, "dw is stored by the dense window passes");
     constexpr bool LDS_R = WM == 1 || WM == 4;
     constexpr bool SE = WM == 4 || WM == 5;
     constexpr bool LDS_V = WM == 4;
@@ -104,6 +111,15 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
     constexpr bool DT = WM != 0 && WM != 3;
     TailRec R{};
     if constexpr (DT) R = *(P.defer_tail ? P.trec : reinterpret_cast<const TailRec*>(P.zeros));
+    // compact pricing: the list's shape, the operand's active buffer and pitch,
+    // and whether dw belongs to this y_w (uniform loads, beside the record's)
+    int cp_S = 0, cp_ld = 64, cp_sel = 0, cp_dw = 0;
+    if constexpr (CP) {
+        cp_S = P.bc_n[0];
+        cp_ld = P.bc_n[1];
+        cp_sel = P.bc_n[2];
+        cp_dw = P.bc_n[5];
+    }
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     constexpr int SW = (int)(sizeof(DevState) / 16);
     u32x4 sw[SW];  // the state as raw words (st_snapshot's loads)
@@ -298,6 +314,22 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
         }
         return;
     }
+    if constexpr (CP || DW) {
+        // compact pricing never prices from a short AS or a stale dw, and dw
+        // is y_w . A_j - c_j only while no earlier pivot of the window rides
+        // on the sum (tau <= 0): the host enqueues neither (a state error)
+        const bool bad = CP ? (cp_S > P.as_cap || cp_dw != 1) : nw > 1;
+        if (bad) {
+            if (wg0 && tid == 0) {
+                if (fresh) apply_deferred_tail(P, st, s_rec, s_tp);
+                st->status = ST_CPRICE_STATE;
+            }
+            return;
+        }
+        if constexpr (DW) {
+            if (wg0 && tid == 0) P.bc_n[5] = 1;  // (read by the next launch)
+        }
+    }
     const bool pend = WIN ? nw > 0 : it > 0;
     const int tau = nw - 1;  // pending pivot of the window
     const int64_t qq = pend ? s_q : 0;
@@ -321,7 +353,7 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
     // so the fill waits for its own loads only, not for the A prefetch.
     static_assert(CH >= 1 && CH <= 8, "the pipelined column loop consumes at most one 8-chunk batch of prefetch");
     const bool deep_hit = DEEP && jdeep >= 0 && jdeep == j0;  // (else the first column goes the usual way)
-    const bool pre = WM != 3 && idx0 < nb && L2 >= CH * 64;
+    const bool pre = WM != 3 && !CP && idx0 < nb && L2 >= CH * 64;
     dbl2 yv[YB], rv[YB], vv[YB];
     double uqrow = 0.0;  // U[q][tid] for Urows (window, workgroup 0)
     if (stage) {
@@ -337,7 +369,7 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
     }
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler would hoist the A loads)
     dbl2 v0[CH];
-    if constexpr (WM != 3) {
+    if constexpr (WM != 3 && !CP) {
         if (!deep_hit) {
             const dbl2* c0 = reinterpret_cast<const dbl2*>(P.A + j0 * L);
 #pragma unroll
@@ -544,6 +576,136 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
             if (argmin_better(key, j, best, bj)) { best = key; bj = j; bw = w; be = e; }
         }
         wave_price_min(best, bj, bw, be);
+    } else if constexpr (CP) {
+        // Compact pricing: one wave per column, as the stream, and the
+        // stream's own sum.  The dense pass gives lane l the elements
+        // 2 k, 2 k + 1 of B_w[q,:] and A_j with k = l (mod 64), an fma chain
+        // per parity in ascending k, then b0 + b1, the window term of lane
+        // s < tau, and the butterfly.  Every element off the list (and off q
+        // while column q is unit) is an exact zero of B_w[q,:], and fma(a, 0,
+        // acc) = acc: so a lane that adds only its listed rows, in ascending
+        // row order (as_ord / as_off, k_as_order: the list sorted by lane,
+        // then row; row q's unit entry put in at its place), holds the dense
+        // lane's b0 and b1 bit for bit, and r_tau . A_j, the Wt entry it
+        // becomes, the Devex weights and through FTRAN every later state are
+        // those of dense pricing.  No grid, block, dispatch or group count
+        // enters that order.  Only e_j is associated anew: dw[j] joins lane
+        // 0's window term before the butterfly (it decides the entering
+        // column and is reported, nothing else).
+        double* cf = reinterpret_cast<double*>(smem + WAVES * sizeof(PricePartial) + 16);
+        const int capp = (P.as_cap + 1) & ~1;
+        int* cpos = reinterpret_cast<int*>(cf + capp);
+        int* crow = cpos + capp;
+        __shared__ int c_off[65];
+        const int Sn = pend ? cp_S : 0;
+        {
+            const double* bq = bc_buf(P, cp_sel) + qq * (int64_t)cp_ld;
+            for (int i = tid; i < Sn; i += BLOCK) {
+                const int c = P.as_ord[i];
+                cpos[i] = c;
+                crow[i] = P.rlist[c];
+                cf[i] = bq[c];
+            }
+            if (tid < 65) c_off[tid] = pend ? P.as_off[tid] : 0;
+        }
+        const bool unitq = pend && P.rmap[qq] < 0 && lane == (int)((qq >> 1) & 63);
+        __syncthreads();
+        // (runs clamped into the entries staged above: offsets that do not
+        // belong to this list -- there is none right after a reset -- can
+        // neither reach unstaged LDS nor, through it, an address outside AS)
+        const int i0 = min(max(c_off[lane], 0), Sn), i1 = min(max(c_off[lane + 1], i0), Sn);
+        const int64_t ald = P.as_ld;
+        // The lane's first KR terms (the same for every column) in registers,
+        // in the order above, the unit entry among them as position -1: a
+        // column's loads then go out together, one round trip.  An unused slot
+        // reads entry 0 against a zero coefficient, and each term goes to both
+        // parities, to the other one with a zero coefficient: fma(a, 0, acc)
+        // = acc.  Longer runs take their rest from LDS, term by term.
+        constexpr int KR = 8;
+        double rc0[KR], rc1[KR];
+        int rp[KR];
+        int iR = i0;
+        bool qrem = unitq;
+#pragma unroll
+        for (int u = 0; u < KR; ++u) {
+            const bool takeq = qrem && (iR >= i1 || crow[iR] > (int)qq);
+            double cv = 0.0;
+            int par = 0;
+            rp[u] = 0;
+            if (takeq) {
+                rp[u] = -1;
+                cv = 1.0;
+                par = (int)(qq & 1);
+                qrem = false;
+            } else if (iR < i1) {
+                rp[u] = cpos[iR];
+                cv = cf[iR];
+                par = crow[iR] & 1;
+                ++iR;
+            }
+            rc0[u] = par ? 0.0 : cv;
+            rc1[u] = par ? cv : 0.0;
+        }
+        // Two columns in flight: a column's operands are requested while the
+        // one before it is summed, and its list entry a column earlier still
+        // (indices clamped into the list: every load is unconditional)
+        double av[KR], wv = 0.0, dv = 0.0, aqj = 0.0;
+        auto request = [&](int64_t jj, double (&xa)[KR], double& xw, double& xd, double& xq) {
+            const double* as = P.AS + jj * ald;
+            const double* aq = P.A + jj * L + qq;
+            xw = (pend && lane < tau) ? P.Wt[jj * KW + lane] : 0.0;
+            xd = lane == 0 ? P.dw[jj] : 0.0;
+#pragma unroll
+            for (int u = 0; u < KR; ++u) xa[u] = *(rp[u] < 0 ? aq : as + rp[u]);
+            xq = qrem ? *aq : 0.0;
+        };
+        const int ilast = nlist > 0 ? nlist - 1 : 0;
+        int64_t jn = nbl(idx0 + stride < nlist ? idx0 + stride : ilast);
+        if (idx0 < nlist) request(j0, av, wv, dv, aqj);
+        int64_t jc = j0;
+        for (int idx = idx0; idx < nlist; idx += stride) {
+            const int64_t j = jc;
+            const double* as = P.AS + j * ald;
+            const int64_t jn2 = nbl(idx + 2 * stride < nlist ? idx + 2 * stride : ilast);
+            double avn[KR], wvn = 0.0, dvn = 0.0, aqn = 0.0;
+            const bool more = idx + stride < nlist;
+            if (more) request(jn, avn, wvn, dvn, aqn);
+            double b0 = 0.0, b1 = 0.0;
+#pragma unroll
+            for (int u = 0; u < KR; ++u) {
+                b0 = fma(av[u], rc0[u], b0);
+                b1 = fma(av[u], rc1[u], b1);
+            }
+            bool qdone = !qrem;
+            auto unit_term = [&]() {
+                if (qq & 1) b1 = fma(aqj, 1.0, b1);
+                else b0 = fma(aqj, 1.0, b0);
+                qdone = true;
+            };
+            for (int i = iR; i < i1; ++i) {
+                const int r = crow[i];
+                if (!qdone && r > (int)qq) unit_term();
+                const double a = as[cpos[i]];
+                if (r & 1) b1 = fma(a, cf[i], b1);
+                else b0 = fma(a, cf[i], b0);
+            }
+            if (!qdone) unit_term();
+            double sa = fma(syl, wv, dv);
+            double wn = fma(uq, wv, b0 + b1);
+            wave_sum2(sa, wn);
+            if (pend && lane == 0) P.Wt[j * KW + tau] = wn;
+            const double e = pend ? fma(syp, wn, sa) : sa;
+            consider(j, e, wn, 0.0);
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < KR; ++u) av[u] = avn[u];
+                wv = wvn;
+                dv = dvn;
+                aqj = aqn;
+            }
+            jc = jn;
+            jn = jn2;
+        }
     } else {
     // The first CH chunks of every column are loaded before the previous
     // column's reduction (and, for the first column, before the LDS fill), so
@@ -783,8 +945,14 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
             }
             if (lane == 0) P.Wt[j * KW + tau] = wn;
             e = fma(syp, wn, sa) - P.c[j];
+            if constexpr (DW) {  // tau = 0: sa is y_w . A_j, the stream's own bits
+                if (lane == 0) P.dw[j] = sa - P.c[j];
+            }
         } else {
             e = wave_sum(a0 + a1) - P.c[j];
+            if constexpr (DW) {
+                if (lane == 0) P.dw[j] = e;
+            }
         }
         consider(j, e, wn, dd);
     }
@@ -794,7 +962,7 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
     // workgroup argmin over waves (lane 0 of each wave holds the wave's best)
     if (lane == 0) red[wave] = PricePartial{best, bj, bw, be};
     __syncthreads();
-    if constexpr (DYN) {
+    if constexpr (DYN || CP) {  // (compact passes hand out no tickets, but keep the counters' turn)
         // the previous pass's tickets (final: it ended at the kernel
         // boundary): every wave draws from its counter until it gets a slot
         // past the list, so a counter with waves ends above the slots it
@@ -1004,26 +1172,26 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
 // ---------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------
-template <int BLOCK, bool LDS_Y, int WM, bool TK = false>
+template <int BLOCK, bool LDS_Y, int WM, bool TK = false, bool DW = false>
 static hipError_t launch_price_t(const Params& P, int grid, size_t lds, hipStream_t s, hipEvent_t e0,
                                  hipEvent_t e1) {
     if (e0 || e1) {
-        hipExtLaunchKernelGGL((k_price<BLOCK, LDS_Y, WM, TK>), dim3(grid), dim3(BLOCK), (uint32_t)lds, s, e0, e1, 0, P);
+        hipExtLaunchKernelGGL((k_price<BLOCK, LDS_Y, WM, TK, DW>), dim3(grid), dim3(BLOCK), (uint32_t)lds, s, e0, e1, 0, P);
     } else {
-        hipLaunchKernelGGL((k_price<BLOCK, LDS_Y, WM, TK>), dim3(grid), dim3(BLOCK), lds, s, P);
+        hipLaunchKernelGGL((k_price<BLOCK, LDS_Y, WM, TK, DW>), dim3(grid), dim3(BLOCK), lds, s, P);
     }
     return hipGetLastError();
 }
 
-template <int BLOCK, bool LDS_Y, int WM, bool TK = false>
+template <int BLOCK, bool LDS_Y, int WM, bool TK = false, bool DW = false>
 static hipError_t prep_price_t(size_t lds, int* blocks_per_cu) {
     hipError_t e = hipSuccess;
     if (lds > 65536) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_price<BLOCK, LDS_Y, WM, TK>),
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_price<BLOCK, LDS_Y, WM, TK, DW>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_price<BLOCK, LDS_Y, WM, TK>, BLOCK, lds);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_price<BLOCK, LDS_Y, WM, TK, DW>, BLOCK, lds);
 }
 
 // (lds_y, wm) variants: (1,0) (0,0) explicit B^-1; (1,1) (1,2) (0,2) eta window
@@ -1033,6 +1201,21 @@ static hipError_t price_dispatch(const PriceCfg& c, const Params* P, hipStream_t
 #define SPX_PV(LY, WM)                                                                  \
     return P ? launch_price_t<BLOCK, LY, WM>(*P, c.grid, c.lds_bytes, s, e0, e1)        \
              : prep_price_t<BLOCK, LY, WM>(c.lds_bytes, blocks_per_cu)
+#define SPX_PVD(LY, WM, TK)                                                                    \
+    return P ? launch_price_t<BLOCK, LY, WM, TK, true>(*P, c.grid, c.lds_bytes, s, e0, e1)     \
+             : prep_price_t<BLOCK, LY, WM, TK, true>(c.lds_bytes, blocks_per_cu)
+    if (c.dw) {  // the dense pass that opens a compact-priced window
+        if (c.wm == 1 && c.lds_y) {
+            if (c.tk) SPX_PVD(true, 1, true);
+            SPX_PVD(true, 1, false);
+        }
+        if (c.wm == 2) {
+            if (c.lds_y) SPX_PVD(true, 2, false);
+            SPX_PVD(false, 2, false);
+        }
+        return hipErrorInvalidValue;
+    }
+    if (c.wm == 6) SPX_PV(false, 6);
     if (c.wm == 0) {
         if (c.lds_y) SPX_PV(true, 0);
         SPX_PV(false, 0);
@@ -1053,7 +1236,46 @@ static hipError_t price_dispatch(const PriceCfg& c, const Params* P, hipStream_t
         SPX_PV(false, 5);
     }
 #undef SPX_PV
+#undef SPX_PVD
     return hipErrorInvalidValue;
+}
+
+// dw for the basic columns (one may leave inside the window and is then
+// priced from dw): after the dense pass that stored the non-basic ones, whose
+// workgroup 0 has applied the pending pivot's bookkeeping, so b_ixs is the
+// basis that pass priced for.  One wave per row; k_reduced_costs' dot (the
+// lane partials and butterfly of the pricing stream), a unit column's single
+// term without its stream
+__global__ __launch_bounds__(256) void k_dw_basic(Params P) {
+    const int lane = threadIdx.x & 63;
+    const int64_t L2 = P.L >> 1;
+    const double* y = P.st->y_buf ? P.y1 : P.y0;
+    const dbl2* y2 = reinterpret_cast<const dbl2*>(y);
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < P.m;
+         i += ((int64_t)gridDim.x * blockDim.x) >> 6) {
+        const int64_t j = P.b_ixs[i];
+        if ((uint64_t)j >= (uint64_t)P.n) continue;
+        double s;
+        if (P.slack_unit && j >= P.ns) {
+            s = y[j - P.ns] - P.c[j];
+        } else {
+            const dbl2* col = reinterpret_cast<const dbl2*>(P.A + j * P.L);
+            double a0 = 0.0, a1 = 0.0;
+            for (int64_t k = lane; k < L2; k += 64) {
+                const dbl2 v = col[k], w = y2[k];
+                a0 = fma(v.x, w.x, a0);
+                a1 = fma(v.y, w.y, a1);
+            }
+            s = wave_sum(a0 + a1) - P.c[j];
+        }
+        if (lane == 0) P.dw[j] = s;
+    }
+}
+
+hipError_t launch_dw_basic(const Params& P, hipStream_t s) {
+    const int64_t want = (P.m + 3) / 4;
+    hipLaunchKernelGGL(k_dw_basic, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, s, P);
+    return hipGetLastError();
 }
 
 hipError_t price_prepare(const PriceCfg& c, int* blocks_per_cu) {
