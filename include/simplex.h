@@ -105,7 +105,7 @@ typedef struct spx_opts {
                              0 = off.  The reference prints nothing of the
                              kind; the parity tests compare it with the
                              oracle's pivot sequence.                        */
-    int32_t algorithm;    /* SPX_ALGO_PRIMAL (default) or SPX_ALGO_DUAL; the field
+    int32_t algorithm;    /* SPX_ALGO_PRIMAL (default), _DUAL or _PRIMAL_BOX; the field
                              was `reserved` (0) before, the layout is unchanged */
 } spx_opts;
 
@@ -144,9 +144,40 @@ typedef struct spx_opts {
  *         finite bound the loop and its kernels are the unbounded ones.  Finite
  *         bounds with SPX_ALGO_PRIMAL are SPX_ERR_STATE; the bound-flipping ratio
  *         test is SPX_DUAL_RATIO_LONG_STEP (below); no non-zero or free lower
- *         bounds. */
+ *         bounds.
+ * PRIMAL_BOX: the primal simplex method with bounded variables 0 <= x_j <= u_j
+ *         (DESIGN.md §7e), for a basis that is primal feasible within its
+ *         bounds; it shares the bounds, placements and effective right-hand
+ *         side with DUAL (spx_set_bounds works under both), so
+ *         spx_set_algorithm hands a basis from one to the other.  Before the
+ *         first pass after spx_create, spx_reset, spx_set_basis,
+ *         spx_set_algorithm, spx_set_bounds, spx_set_rhs or spx_set_cost the
+ *         placements are kept (a column at an upper bound that is now +inf goes
+ *         to lower), x_b is recomputed from them and -feas_tol <= x_b[i] <= u_k +
+ *         feas_tol is checked (k the row's basic column): a violation is
+ *         SPX_ERR_STATE "basis is not primal feasible", naming the row and the
+ *         column; nothing changes and SPX_ALGO_DUAL can repair it.  One pass:
+ *         d_j = y.A_j - c_j over the non-basic columns, candidates sigma_j d_j <
+ *         -eps, p = argmin sigma_j d_j (none: OPTIMUM_FOUND); alpha = B^-1 A_p,
+ *         ahat = sigma_p alpha; row i with ahat_i > piv_tol leaves to its lower
+ *         bound at t_i = max(x_b[i], 0) / ahat_i, row i with ahat_i < -piv_tol and
+ *         a finite u_k to its upper bound at t_i = max(u_k - x_b[i], 0) / -ahat_i;
+ *         q = argmin t_i; first index on every tie.  u_p finite and (no row, or
+ *         u_p <= t_q): a flip, x_b -= u_p ahat and p changes sides; no basis
+ *         change, not a pivot.  No row and u_p = +inf: SPX_STATUS_UNBOUNDED.  Else
+ *         theta = t_q: x_b -= theta ahat, x_b[q] = (u_p at upper, else 0) +
+ *         sigma_p theta, y -= (d_p / alpha_q) rho (rho = row q of B^-1 before the
+ *         pivot), and the leaving column becomes non-basic at exactly the bound
+ *         it left to.  The pivot count, the trace, refactor_every and
+ *         spx_iterate(k) count pivots only.  With every bound +inf this is the
+ *         primal loop's Dantzig rule with SPX_RATIO_GUARDED.  Scope and refusals
+ *         are DUAL's (spx_create: SPX_ERR_ARG naming the combination; spx_price /
+ *         spx_pivot / spx_group_iterate: SPX_ERR_STATE).  No primal phase 1, no
+ *         Devex / steepest edge, no non-zero or free lower bounds.  SPX_ALGO_PRIMAL
+ *         itself still refuses finite bounds. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
+#define SPX_ALGO_PRIMAL_BOX 2
 
 /* Leaving-row rules of the dual loop (SPX_FLAG_DUAL_STEEPEST at spx_create,
  * spx_set_dual_pricing later; opts.pricing is the primal entering rule and
@@ -416,6 +447,20 @@ int spx_get_dual_weights(spx_ctx* ctx, double* w /* m */);
  * replicated B^-1 (SPX_ERR_STATE otherwise). */
 int spx_set_rhs(spx_ctx* ctx, const double* b);
 
+/* New objective c[0..n): uploaded, then c_B and y = c_B B^-1 for the current
+ * basis (through spx_reinvert), status back to running; the pivot count, the
+ * basis, the placements and x_b are kept.  The basis stays primal feasible, so
+ * after an optimal boxed dual solve spx_set_algorithm(SPX_ALGO_PRIMAL_BOX) +
+ * spx_solve re-optimises from it; under SPX_ALGO_DUAL the feasibility check
+ * (boxed: the normalisation) runs again before the next pass.  One rank,
+ * replicated B^-1 (SPX_ERR_STATE otherwise). */
+int spx_set_cost(spx_ctx* ctx, const double* c /* n */);
+
+/* Counters of the bounded primal loop since spx_create or spx_reset: out[0]
+ * flip passes, out[1] pivots whose leaving column went to its upper bound.
+ * Counted on the device by the kernel that commits the pass. */
+int spx_get_primal_flips(spx_ctx* ctx, int64_t out[2]);
+
 /* Upper bounds ub[0..n) of all columns, slacks included (+inf = none, NULL =
  * none at all); lower bounds are 0.  The basis and the pivot count are kept and
  * the status is back to running: a non-basic column at an upper bound that
@@ -423,8 +468,10 @@ int spx_set_rhs(spx_ctx* ctx, const double* b);
  * feasible side and x_b is recomputed, so spx_solve re-optimises from the old
  * basis.  B^-1 is untouched: steepest-edge weights stay valid.  SPX_ERR_ARG for
  * a NaN or negative bound (the message names the column); SPX_ERR_STATE unless
- * one rank, replicated B^-1, SPX_ALGO_DUAL and not between spx_price and
- * spx_pivot, and when a column with e_j < -eps has no upper bound. */
+ * one rank, replicated B^-1, SPX_ALGO_DUAL or SPX_ALGO_PRIMAL_BOX and not
+ * between spx_price and spx_pivot, and (DUAL) when a column with e_j < -eps has
+ * no upper bound.  Under SPX_ALGO_PRIMAL_BOX the placements are kept as they
+ * are (no dual normalisation), and the entry check runs before the next pass. */
 int spx_set_bounds(spx_ctx* ctx, const double* ub /* n, +inf = none */);
 int spx_get_bounds(spx_ctx* ctx, double* ub /* n */);
 

@@ -27,7 +27,7 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "SimplexError", "FLAG_TIMING", "RATIO_REFERENCE", "RATIO_GUARDED", "RATIO_HARRIS",
            "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL",
            "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST",
-           "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP"]
+           "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -50,6 +50,9 @@ PRICING_DANTZIG, PRICING_DEVEX, PRICING_STEEPEST = 0, 1, 2
 # simplex algorithm of iterate / solve (include/simplex.h SPX_ALGO_*): the dual
 # loop starts from a dual feasible basis whose x_b may be negative (b of any sign)
 ALGO_PRIMAL, ALGO_DUAL = 0, 1
+# the primal loop with bounded variables 0 <= x <= upper: a basis primal feasible
+# within its bounds (b >= 0 at the slack basis, or a boxed dual optimum after set_cost)
+ALGO_PRIMAL_BOX = 2
 # leaving-row rules of the dual loop (include/simplex.h SPX_DUAL_PRICING_*)
 DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST = 0, 1
 # ratio tests of the dual loop's boxed passes (include/simplex.h SPX_DUAL_RATIO_*)
@@ -182,7 +185,7 @@ class Context:
         o.pricing = pricing  # PRICING_DANTZIG / PRICING_DEVEX / PRICING_STEEPEST
         o.loop_block = loop_block
         o.trace_cap = trace  # record the first `trace` pivots' (p, q) on the device
-        o.algorithm = algorithm  # ALGO_PRIMAL / ALGO_DUAL
+        o.algorithm = algorithm  # ALGO_PRIMAL / ALGO_DUAL / ALGO_PRIMAL_BOX
         if dual_pricing not in (DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST):
             raise ValueError("dual_pricing must be DUAL_PRICING_DANTZIG or DUAL_PRICING_STEEPEST")
         self._dual_pricing = dual_pricing
@@ -214,7 +217,7 @@ class Context:
             self.m, self.n = m, n
         self._h = h
         self._L = L
-        if upper is not None:  # 0 <= x <= upper: the dual loop only (the library refuses it otherwise)
+        if upper is not None:  # 0 <= x <= upper: ALGO_DUAL or ALGO_PRIMAL_BOX (the library refuses it otherwise)
             try:
                 self.set_bounds(upper)
             except Exception:
@@ -291,9 +294,9 @@ class Context:
         check(self._L.spx_set_basis(self._h, _ptr(bs)))
 
     def set_algorithm(self, algo: int):
-        """Switch between the primal and the dual loop (spx_set_algorithm):
-        basis, B^-1, x_b, y and the pivot count are kept, the status goes back
-        to running."""
+        """Switch between the primal, the dual and the bounded primal loop
+        (spx_set_algorithm): basis, B^-1, x_b, y, the placements and the pivot
+        count are kept, the status goes back to running."""
         check(self._L.spx_set_algorithm(self._h, algo))
 
     def set_dual_pricing(self, rule: int):
@@ -332,11 +335,29 @@ class Context:
             raise ValueError(f"b must have {self.m} entries")
         check(self._L.spx_set_rhs(self._h, _ptr(bv)))
 
+    def set_cost(self, c):
+        """New objective (spx_set_cost): c_B and y = c_B B^-1 for the current
+        basis, which stays primal feasible; the basis, the placements, x_b and
+        the pivot count are kept, status back to running."""
+        cv = np.ascontiguousarray(c, dtype=np.float64)
+        if cv.shape != (self.n,):
+            raise ValueError(f"c must have {self.n} entries")
+        check(self._L.spx_set_cost(self._h, _ptr(cv)))
+
+    def primal_flips(self):
+        """(flip passes, pivots whose leaving column went to its upper bound)
+        of the bounded primal loop since create / reset (spx_get_primal_flips)."""
+        out = (ctypes.c_int64 * 2)()
+        check(self._L.spx_get_primal_flips(self._h, out))
+        return tuple(int(v) for v in out)
+
     def set_bounds(self, upper):
         """Upper bounds of all n columns, slacks included (spx_set_bounds):
         ``inf`` = none, ``None`` = no bounds at all.  The basis is kept, the
         placements are made dual feasible and x_b recomputed, so ``solve()``
-        re-optimises from the old basis.  ALGO_DUAL only."""
+        re-optimises from the old basis.  Under ALGO_PRIMAL_BOX the placements
+        are kept as they are and the loop's entry check runs before the next
+        pass.  ALGO_DUAL and ALGO_PRIMAL_BOX only."""
         if upper is None:
             check(self._L.spx_set_bounds(self._h, None))
             return

@@ -65,6 +65,8 @@ SIGNATURES = {
     "spx_get_dual_weights": (ctypes.c_int, [_p, _p]),
     "spx_set_dual_ratio": (ctypes.c_int, [_p, _i32]),
     "spx_get_dual_flips": (ctypes.c_int, [_p, _p]),
+    "spx_set_cost": (ctypes.c_int, [_p, _p]),
+    "spx_get_primal_flips": (ctypes.c_int, [_p, _p]),
     "spx_group_iterate": (ctypes.c_int, [_p, _i32, _i64, _p, _p]),
     "spx_group_sync": (ctypes.c_int, [_p, _i32]),
     "spx_solve": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _p]),

@@ -33,10 +33,15 @@
 //   --dual-ratio R ratio test of --dual with --bounds: textbook (default) | long (the
 //                  bound-flipping ratio test, SPX_DUAL_RATIO_LONG_STEP; --json
 //                  then carries the flip counts).  --ratio stays the primal rule
-//   --bounds F     upper bounds 0 <= x_j <= u_j of all n columns for --dual
-//                  (spx_set_bounds): F holds n whitespace-separated values, "inf"
-//                  = none; without --dual the library's refusal is printed (exit
-//                  1); not with --mps (its reader turns bounds into rows)
+//   --primal-box   solve with the bounded primal simplex loop (SPX_ALGO_PRIMAL_BOX,
+//                  simplex.h): from the slack basis, which must be primal feasible
+//                  (b >= 0, every bounded slack's u >= b_i); --json then carries
+//                  the flip-pass and to-upper counts.  Not with --dual, --mps,
+//                  --window N > 0 or --tableau (refused by name, exit 1)
+//   --bounds F     upper bounds 0 <= x_j <= u_j of all n columns for --dual or
+//                  --primal-box (spx_set_bounds): F holds n whitespace-separated
+//                  values, "inf" = none; without either the library's refusal is
+//                  printed (exit 1); not with --mps (its reader turns bounds into rows)
 //   --tableau      window tableau (SPX_FLAG_TABLEAU): T_w = B_w A
 //                  kept in HBM, no per-pivot A / B^-1 stream
 //   --mps          the input is an MPS file (mps_io.h): converted to the
@@ -81,7 +86,7 @@ static void print_elapsed_time(const char* msg, double dur) {
 static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
-                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual]"
+                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box]"
                  " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
@@ -101,7 +106,7 @@ int main(int argc, char* argv[]) {
     int ratio = -1, window = 0, pricing = SPX_PRICING_DANTZIG;
     double piv_tol = 1e-9, feas_tol = 1e-9, big_m = 0.0;
     int64_t refactor = 0;
-    bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false;
+    bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false, primal_box = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -136,6 +141,7 @@ int main(int argc, char* argv[]) {
         else if (s == "--mps") mps_in = true;
         else if (s == "--tableau") tableau = true;
         else if (s == "--dual") dual = true;
+        else if (s == "--primal-box") primal_box = true;
         else if (s == "--bounds") { need(1); bounds_path = argv[++a]; }
         else if (s == "--dual-pricing") {
             need(1);
@@ -172,6 +178,13 @@ int main(int argc, char* argv[]) {
     if (!path && !gen) {
         std::cerr << "Please, specify an input file.\n";
         return 1;
+    }
+    if (primal_box) {
+        const char* with = dual ? "--dual" : mps_in ? "--mps" : window > 0 ? "--window N > 0" : tableau ? "--tableau" : nullptr;
+        if (with) {
+            std::cerr << "--primal-box does not combine with " << with << "\n";
+            return 1;
+        }
     }
 
     const TimePoint t_start = Clock::now();
@@ -223,6 +236,7 @@ int main(int argc, char* argv[]) {
     o.pricing = pricing;
     if (tableau) o.flags |= SPX_FLAG_TABLEAU;
     if (dual) o.algorithm = SPX_ALGO_DUAL;
+    if (primal_box) o.algorithm = SPX_ALGO_PRIMAL_BOX;
     if (dual_steepest) o.flags |= SPX_FLAG_DUAL_STEEPEST;
     if (dual_long) o.flags |= SPX_FLAG_DUAL_LONG_STEP;
     spx_ctx* ctx = nullptr;
@@ -274,6 +288,8 @@ int main(int argc, char* argv[]) {
     const TimePoint t_loop_end = Clock::now();
     int64_t flips[3] = {0, 0, 0};
     if (dual) spx_get_dual_flips(ctx, flips);
+    int64_t pflips[2] = {0, 0};
+    if (primal_box) spx_get_primal_flips(ctx, pflips);
     spx_destroy(ctx);
     const TimePoint t_dealloc_end = Clock::now();
 
@@ -357,6 +373,8 @@ int main(int argc, char* argv[]) {
         if (dual)
             std::cout << ", \"dual_ratio\": \"" << (dual_long ? "long" : "textbook") << "\", \"flips\": " << flips[0]
                       << ", \"flip_passes\": " << flips[1] << ", \"max_flips\": " << flips[2];
+        if (primal_box)
+            std::cout << ", \"flip_passes\": " << pflips[0] << ", \"to_upper\": " << pflips[1];
         std::cout << ", \"solve_s\": " << seconds(t_init_end, t_loop_end) << "}\n";
     }
     return 0;

@@ -161,11 +161,13 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
     if (rule == SPX_RATIO_HARRIS && G > 1 && (x->opts.flags & SPX_FLAG_ROW_SHARD))
         return fail(SPX_ERR_ARG, "the Harris ratio test needs replicated B^-1 (no row sharding)");
     if (x->opts.refactor_every < 0) return fail(SPX_ERR_ARG, "refactor_every must be >= 0");
-    if (x->opts.algorithm != SPX_ALGO_PRIMAL && x->opts.algorithm != SPX_ALGO_DUAL)
+    if (x->opts.algorithm != SPX_ALGO_PRIMAL && x->opts.algorithm != SPX_ALGO_DUAL &&
+        x->opts.algorithm != SPX_ALGO_PRIMAL_BOX)
         return fail(SPX_ERR_ARG, "bad algorithm %d", x->opts.algorithm);
-    if (x->opts.algorithm == SPX_ALGO_DUAL) {
+    if (x->opts.algorithm != SPX_ALGO_PRIMAL) {  // the dual loop's scope is the bounded primal loop's
         if (const char* why = dual_conflict(x->opts, x->opts.window > 0 ? x->opts.window : 0))
-            return fail(SPX_ERR_ARG, "the dual simplex loop does not run %s", why);
+            return fail(SPX_ERR_ARG, "the %s does not run %s",
+                        x->opts.algorithm == SPX_ALGO_DUAL ? "dual simplex loop" : "bounded primal simplex loop", why);
         if (!(x->opts.piv_tol >= 0.0) || !(x->opts.feas_tol >= 0.0))
             return fail(SPX_ERR_ARG, "piv_tol and feas_tol must be >= 0");
     }
@@ -209,7 +211,7 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
 
     // B^-1 representation: eta window of KW pivots, or the explicit rank-1 update
     int KW = x->opts.window;
-    if (KW == 0 && x->algo == SPX_ALGO_DUAL) KW = -1;  // the dual loop works on the explicit B^-1
+    if (KW == 0 && x->algo != SPX_ALGO_PRIMAL) KW = -1;  // the dual and the bounded primal loop work on the explicit B^-1
     if (KW == 0) {
         // auto (measured): the window halves the B^-1 stream and
         // costs ~2 % more pricing (its Wt rows): C3 +27 %, C4 +4 %, C5 +33 %
@@ -508,6 +510,7 @@ int do_reset(spx_ctx* x) {
         HIP_TRY(hipMemsetAsync(v, 0, (size_t)x->L * sizeof(double), x->stream));
     SPX_TRY(clear_tickets(x));
     SPX_TRY(dual_on_reset(x));
+    SPX_TRY(pbox_on_reset(x));
     HIP_TRY(launch_reset(x->P, x->stream));
     SPX_TRY(box_sync(x));
     HIP_TRY(launch_se_init(x->P, x->stream));  // steepest edge: gamma_j = 1 + ||A_j||^2
@@ -824,6 +827,7 @@ int iterate_passes(spx_ctx* x, int64_t k);
 int iterate_raw(spx_ctx* x, int64_t k) {
     if (x->status != SPX_STATUS_MAX_ITER || k <= 0) return SPX_OK;
     if (x->algo == SPX_ALGO_DUAL) return iterate_dual(x, k);
+    if (x->algo == SPX_ALGO_PRIMAL_BOX) return iterate_pbox(x, k);
     if (x->persist && !x->stepped_price) {
         SPX_TRY(set_limit(x, x->pivots + k));
         return iterate_persist(x, k);
@@ -1148,6 +1152,7 @@ int cprice_setup(spx_ctx* x) {
 int create_tail(spx_ctx* x) {
     SPX_TRY(do_reset(x));
     if (x->algo == SPX_ALGO_DUAL) return dual_setup(x);  // (a later switch to primal captures its graph on its first batch)
+    if (x->algo == SPX_ALGO_PRIMAL_BOX) return pbox_setup(x);
     if (!x->use_comm && !x->persist) SPX_TRY(build_graphs(x));  // capture + upload now (off any timed path)
     return SPX_OK;
 }
@@ -1503,7 +1508,8 @@ int spx_set_basis(spx_ctx* x, const int64_t* basis) {
 
 int spx_set_algorithm(spx_ctx* x, int32_t algo) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
-    if (algo != SPX_ALGO_PRIMAL && algo != SPX_ALGO_DUAL) return fail(SPX_ERR_ARG, "bad algorithm %d", algo);
+    if (algo != SPX_ALGO_PRIMAL && algo != SPX_ALGO_DUAL && algo != SPX_ALGO_PRIMAL_BOX)
+        return fail(SPX_ERR_ARG, "bad algorithm %d", algo);
     if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_algorithm between spx_price and spx_pivot");
     SPX_TRY(dual_switch_algorithm(x, algo));
@@ -1523,6 +1529,22 @@ int spx_set_rhs(spx_ctx* x, const double* b) {
     HIP_TRY(hipStreamSynchronize(x->stream));
     HIP_TRY(hipMemcpy(dual_rhs_target(x), b, (size_t)x->m * sizeof(double), hipMemcpyHostToDevice));
     SPX_TRY(reinvert_current(x));  // x_b = B^-1 b (and the window / tableau rebuilds)
+    pbox_on_change(x);
+    return set_running(x);
+}
+
+int spx_set_cost(spx_ctx* x, const double* c) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (!c) return fail(SPX_ERR_ARG, "c is NULL");
+    if (x->opts.nranks > 1 || x->P.row_shard)
+        return fail(SPX_ERR_STATE, "spx_set_cost needs one rank and replicated B^-1 (nranks %d%s)", x->opts.nranks,
+                    x->P.row_shard ? ", row-sharded" : "");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_cost between spx_price and spx_pivot");
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(x->c, c, (size_t)x->n * sizeof(double), hipMemcpyHostToDevice));
+    SPX_TRY(reinvert_current(x));  // c_B and y = c_B B^-1 (and the window / tableau rebuilds)
+    dual_on_new_basis(x);  // the reduced costs changed: nothing checked
     return set_running(x);
 }
 
@@ -1544,6 +1566,8 @@ int spx_group_iterate(spx_ctx** cs, int32_t G, int64_t k, int32_t* status, int64
         if (x->comm_ready) return fail(SPX_ERR_STATE, "group contexts must not have a communicator");
         if (x->algo == SPX_ALGO_DUAL)
             return fail(SPX_ERR_STATE, "spx_group_iterate runs the primal loop only (context %d runs SPX_ALGO_DUAL)", g);
+        if (x->algo == SPX_ALGO_PRIMAL_BOX)
+            return fail(SPX_ERR_STATE, "spx_group_iterate runs the primal loop only (context %d runs SPX_ALGO_PRIMAL_BOX)", g);
         if (x->m != cs[0]->m || x->n != cs[0]->n) return fail(SPX_ERR_ARG, "group shape mismatch");
         if (x->status != cs[0]->status || x->pivots != cs[0]->pivots) return fail(SPX_ERR_STATE, "group out of step");
         if (x->P.row_shard != cs[0]->P.row_shard || x->P.win != cs[0]->P.win)
@@ -1798,6 +1822,8 @@ int spx_price(spx_ctx* x, int64_t* p, double* min_e, int32_t* optimal) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (x->algo == SPX_ALGO_DUAL)
         return fail(SPX_ERR_STATE, "spx_price / spx_pivot step the primal loop only (the context runs SPX_ALGO_DUAL)");
+    if (x->algo == SPX_ALGO_PRIMAL_BOX)
+        return fail(SPX_ERR_STATE, "spx_price / spx_pivot step the primal loop only (the context runs SPX_ALGO_PRIMAL_BOX)");
     if (x->status != SPX_STATUS_MAX_ITER) return fail(SPX_ERR_STATE, "solve already terminated");
     SPX_TRY(set_limit(x, x->pivots + 1));
     const bool fold = fold_due(x);
@@ -1845,6 +1871,8 @@ int spx_pivot(spx_ctx* x, int64_t* q, int32_t* status) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (x->algo == SPX_ALGO_DUAL)
         return fail(SPX_ERR_STATE, "spx_price / spx_pivot step the primal loop only (the context runs SPX_ALGO_DUAL)");
+    if (x->algo == SPX_ALGO_PRIMAL_BOX)
+        return fail(SPX_ERR_STATE, "spx_price / spx_pivot step the primal loop only (the context runs SPX_ALGO_PRIMAL_BOX)");
     if (!x->stepped_price) return fail(SPX_ERR_STATE, "spx_pivot needs a preceding spx_price");
     x->stepped_price = false;
     HIP_TRY(launch_update(x->P, x->ucfg, x->stream, nullptr, nullptr));
@@ -1873,7 +1901,7 @@ int spx_dispatch_stats(spx_ctx* x, int64_t out[SPX_DISPATCH_FIELDS]) {
 int spx_prepare(spx_ctx* x) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (x->persist) return SPX_OK;  // one launch per window: nothing to capture
-    if (x->algo == SPX_ALGO_DUAL) return SPX_OK;  // dual passes are eager launches
+    if (x->algo != SPX_ALGO_PRIMAL) return SPX_OK;  // dual and bounded primal passes are eager launches
     return build_graphs(x);
 }
 

@@ -233,6 +233,44 @@ int box_sync(spx_ctx* x) {
     return SPX_OK;
 }
 
+int box_buffers(spx_ctx* x) {
+    DualState& d = x->dual;
+    if (d.args.ub) return SPX_OK;
+    const size_t n = (size_t)x->n, L = (size_t)x->L;
+    double* d_ub = nullptr;
+    SPX_TRY(x->alloc(&d_ub, n));
+    d.args.ub = d_ub;
+    SPX_TRY(x->alloc(&d.args.ub_B, L));
+    SPX_TRY(x->alloc(&d.args.at_upper, n));
+    SPX_TRY(x->alloc(&d.b_user, L));
+    const std::vector<double> inf(std::max(n, L), INFINITY);
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(d_ub, inf.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.args.ub_B, inf.data(), L * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.b_user, x->b, L * sizeof(double), hipMemcpyDeviceToDevice));
+    return SPX_OK;
+}
+
+int box_replace_xb(spx_ctx* x) {
+    DualState& d = x->dual;
+    if (d.boxed) {
+        const size_t n = (size_t)x->n;
+        std::vector<int8_t> up(n);
+        bool changed = false;
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        HIP_TRY(hipMemcpy(up.data(), d.args.at_upper, n, hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < n; ++j)
+            if (up[j] && !std::isfinite(d.ub[j])) {
+                up[j] = 0;
+                changed = true;
+            }
+        if (changed) HIP_TRY(hipMemcpy(d.args.at_upper, up.data(), n, hipMemcpyHostToDevice));
+    }
+    SPX_TRY(box_sync(x));
+    HIP_TRY(launch_box_xb(x->P, d.cfg, x->stream));
+    return SPX_OK;
+}
+
 // k dual passes, eager launches, one host synchronisation at the end.  Every
 // kernel returns at once when the device status is not running or the limit is
 // reached; the closing k_dual_step only commits the last pass's pivot.
@@ -272,7 +310,10 @@ int dual_on_reset(spx_ctx* x) {
 
 void dual_on_reinvert(spx_ctx* x) { weights_lost(x); }
 
-void dual_on_new_basis(spx_ctx* x) { feasibility_unknown(x); }
+void dual_on_new_basis(spx_ctx* x) {
+    feasibility_unknown(x);
+    pbox_on_change(x);
+}
 
 // (rows m..L-1 stay 0; boxed: the caller's b, reinvert_basis forms b_eff from it)
 double* dual_rhs_target(spx_ctx* x) { return x->dual.boxed ? x->dual.b_user : x->b; }
@@ -280,11 +321,16 @@ double* dual_rhs_target(spx_ctx* x) { return x->dual.boxed ? x->dual.b_user : x-
 int dual_switch_algorithm(spx_ctx* x, int32_t algo) {
     if (algo == SPX_ALGO_PRIMAL && x->dual.boxed)
         return fail(SPX_ERR_STATE, "the primal loop does not run with finite upper bounds (spx_set_bounds): bounded "
-                    "variables are the dual simplex loop's; remove the bounds first");
-    if (algo == SPX_ALGO_DUAL) {
+                    "variables are the dual simplex loop's and the bounded primal loop's (SPX_ALGO_PRIMAL_BOX); remove "
+                    "the bounds first");
+    if (algo == SPX_ALGO_DUAL || algo == SPX_ALGO_PRIMAL_BOX) {
         if (const char* why = dual_conflict(x->opts, x->P.win))
-            return fail(SPX_ERR_STATE, "the dual simplex loop does not run %s", why);
+            return fail(SPX_ERR_STATE, "the %s does not run %s",
+                        algo == SPX_ALGO_DUAL ? "dual simplex loop" : "bounded primal simplex loop", why);
+        if (algo == SPX_ALGO_PRIMAL_BOX && (!(x->opts.piv_tol >= 0.0) || !(x->opts.feas_tol >= 0.0)))
+            return fail(SPX_ERR_STATE, "piv_tol and feas_tol must be >= 0");
         SPX_TRY(dual_setup(x));
+        if (algo == SPX_ALGO_PRIMAL_BOX) SPX_TRY(pbox_setup(x));
         // the primal loop's pending y / x_b updates applied; its pending rank-1
         // update of B^-1 is the form the dual kernels continue from
         SPX_TRY(flush(x));
@@ -295,6 +341,7 @@ int dual_switch_algorithm(spx_ctx* x, int32_t algo) {
     }
     feasibility_unknown(x);
     weights_lost(x);  // (primal passes keep no dual weights)
+    pbox_on_change(x);
     return SPX_OK;
 }
 
@@ -374,14 +421,16 @@ int spx_set_bounds(spx_ctx* x, const double* ub) {
     if (x->opts.nranks > 1 || x->P.row_shard)
         return fail(SPX_ERR_STATE, "spx_set_bounds needs one rank and replicated B^-1 (nranks %d%s)", x->opts.nranks,
                     x->P.row_shard ? ", row-sharded" : "");
-    if (x->algo != SPX_ALGO_DUAL)
-        return fail(SPX_ERR_STATE, "upper bounds need the dual simplex loop (SPX_ALGO_DUAL): the primal loop does not "
-                    "run bounded variables");
+    const bool pbox = x->algo == SPX_ALGO_PRIMAL_BOX;  // placements kept, no normalisation: its entry check follows
+    if (x->algo != SPX_ALGO_DUAL && !pbox)
+        return fail(SPX_ERR_STATE, "upper bounds need the dual simplex loop (SPX_ALGO_DUAL) or the bounded primal loop "
+                    "(SPX_ALGO_PRIMAL_BOX): the primal loop does not run bounded variables");
     if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_bounds between spx_price and spx_pivot");
     SPX_TRY(dual_setup(x));
     DualState& d = x->dual;
-    {  // refused before anything changes: a column that would have no dual feasible side
+    pbox_on_change(x);
+    if (!pbox) {  // refused before anything changes: a column that would have no dual feasible side
         std::vector<double> e;
         std::vector<int32_t> pos;
         SPX_TRY(fetch_reduced_costs(x, e, pos));
@@ -392,14 +441,7 @@ int spx_set_bounds(spx_ctx* x, const double* ub) {
         d.ub.assign(n, INFINITY);
         return set_running(x);
     }
-    if (!d.args.ub) {
-        double* d_ub = nullptr;
-        SPX_TRY(x->alloc(&d_ub, n));
-        d.args.ub = d_ub;
-        SPX_TRY(x->alloc(&d.args.ub_B, (size_t)x->L));
-        SPX_TRY(x->alloc(&d.args.at_upper, n));
-        SPX_TRY(x->alloc(&d.b_user, (size_t)x->L));
-    }
+    SPX_TRY(box_buffers(x));
     HIP_TRY(hipStreamSynchronize(x->stream));
     if (!d.boxed) {  // P.b is still the caller's b, every column at lower
         HIP_TRY(hipMemcpy(d.b_user, x->b, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice));
@@ -417,7 +459,7 @@ int spx_set_bounds(spx_ctx* x, const double* ub) {
     d.boxed = true;  // (the normalisation and b_eff below run on the boxed state either way)
     feasibility_unknown(x);
     SPX_TRY(set_running(x));
-    const int rc = box_normalise(x, true);
+    const int rc = pbox ? box_recompute_xb(x) : box_normalise(x, true);
     if (!finite && rc == SPX_OK) {  // no bound left: P.b is b again (no column at upper), the plain kernels run
         HIP_TRY(hipStreamSynchronize(x->stream));
         d.boxed = false;

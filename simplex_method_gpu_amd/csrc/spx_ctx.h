@@ -1,5 +1,5 @@
 // spx_ctx.h — what the host translation units behind include/simplex.h share
-// (spx_api.cpp, spx_api_dual.cpp): the context, the error plumbing and the few
+// (spx_api.cpp, spx_api_dual.cpp, spx_api_pbox.cpp): the context, the error plumbing and the few
 // helpers one unit calls in the other.  Internal: not installed, not part of
 // the ABI.
 #pragma once
@@ -15,6 +15,7 @@
 #include "spx_dual.h"
 #include "spx_kernels.h"
 #include "spx_loop.h"
+#include "spx_pbox.h"
 #include "spx_reinv.h"
 
 namespace spx_host {
@@ -81,6 +82,23 @@ struct DualState {
     bool boxed = false;
     std::vector<double> ub;
     double* b_user = nullptr;  // L
+};
+
+// The bounded primal loop's host state (spx_pbox.h; everything that reads or
+// writes it is in spx_api_pbox.cpp).  The bounds, placements and the caller's
+// right-hand side are DualState's (args.ub / ub_B / at_upper, b_user, ub,
+// boxed): PboxArgs points at the same buffers.  Invariants:
+//  - args.rec != nullptr  <=>  pbox_setup ran: parts, rparts, rec and cfg are
+//    set, and so are the dual loop's buffers (dual_setup) and the boxed ones
+//    (box_buffers: with no finite bound ub and ub_B are all +inf, at_upper all 0).
+//  - checked: since the basis, the bounds, b, c or the algorithm were last set
+//    from outside, the entry check passed (x_b recomputed from the placements
+//    and within its bounds) and rbuf holds the pending pivot's row.
+//  - the counters live in args.rec (all 0 while it is not allocated).
+struct PboxState {
+    spx::PboxArgs args{};
+    spx::PboxCfg cfg{};
+    bool checked = false;
 };
 
 struct spx_ctx {
@@ -198,6 +216,7 @@ struct spx_ctx {
 
     int32_t algo = SPX_ALGO_PRIMAL;  // the loop spx_iterate runs
     DualState dual;                  // the dual one's state (spx_api_dual.cpp)
+    PboxState pbox;                  // the bounded primal one's (spx_api_pbox.cpp)
 
     template <typename T>
     int alloc(T** p, size_t count, unsigned ext_flags = ~0u) {
@@ -248,5 +267,17 @@ double* dual_rhs_target(spx_ctx* x);  // where spx_set_rhs writes the caller's b
 int dual_switch_algorithm(spx_ctx* x, int32_t algo);
 // boxed: zu = sum of c_j u_j over the non-basic columns at upper; else 0
 int dual_objective_offset(spx_ctx* x, double* zu);
+// the boxed buffers (ub, ub_B, at_upper, b_user), on first use: no bound, every
+// column at lower, b_user = Params::b
+int box_buffers(spx_ctx* x);
+// boxed: a column at an upper bound that no longer exists goes to lower; then
+// Params::b from the placements and x_b = B^-1 Params::b (B^-1 untouched)
+int box_replace_xb(spx_ctx* x);
+
+// spx_api_pbox.cpp: all the rest of the runtime knows of the bounded primal loop
+int pbox_setup(spx_ctx* x);  // buffers and launch geometry, on first use
+int iterate_pbox(spx_ctx* x, int64_t k);
+int pbox_on_reset(spx_ctx* x);     // do_reset: counters cleared, nothing checked
+void pbox_on_change(spx_ctx* x);   // the basis, the bounds, b, c or the algorithm were set: nothing checked
 
 }  // namespace spx_host

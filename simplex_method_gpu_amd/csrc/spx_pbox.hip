@@ -1,0 +1,519 @@
+// spx_pbox.hip — gfx950 kernels of the bounded primal simplex loop (spx_pbox.h).
+#include "spx_pbox.h"
+
+#include <hip/hip_ext.h>
+
+#include "spx_common.h"
+
+namespace spx {
+
+namespace {
+
+// the workgroup's merge of its waves' pricing candidates, with selects on scalars
+template <int WAVES>
+__device__ __forceinline__ PboxPartial merge_price(const PboxPartial* red) {
+    double key = red[0].key, d = red[0].d;
+    int64_t idx = red[0].idx;
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) {
+        const double k2 = red[w].key, d2 = red[w].d;
+        const int64_t j2 = red[w].idx;
+        const bool t = argmin_better(k2, j2, key, idx);
+        key = t ? k2 : key;
+        idx = t ? j2 : idx;
+        d = t ? d2 : d;
+    }
+    return PboxPartial{key, idx, d, 0.0};
+}
+
+// (value, index) argmin over the wave; every lane ends with the result (xor
+// butterfly, argmin_better's order)
+__device__ __forceinline__ void wave_argmin(double& v, int64_t& j) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double v2 = __shfl_xor(v, off, 64);
+        const int64_t j2 = __shfl_xor(j, off, 64);
+        const bool t = argmin_better(v2, j2, v, j);
+        v = t ? v2 : v;
+        j = t ? j2 : j;
+    }
+}
+
+struct PboxSnap {  // the loop state, read once per workgroup by thread 0
+    int64_t it, limit, qprev, p;
+    double aqprev, d_p;
+    int32_t status, y_buf, fresh, cnt;
+};
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// Pricing (the hot kernel): one dot per streamed non-basic column
+// ---------------------------------------------------------------------------
+// k_dual_price's stream with one operand: one wave per column, grid-stride over
+// nb_list.  A column is L/2 dbl2 in chunks of 64 lanes; U chunks are in flight
+// per wave while the previous U are multiplied with y (double-buffered
+// registers), non-temporal as k_price's A stream.  Per lane the chunks are
+// accumulated in ascending order into two partial sums, then one butterfly: a
+// column's d_j does not depend on the grid or on which wave prices it.  sigma_j
+// is one wave-uniform flag read per column, ahead of its stream.
+template <bool LDS>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_price(Params P, PboxArgs D) {
+    constexpr int WAVES = PBOX_WAVES, U = 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    const DevState* st = P.st;
+    const int32_t status = st->status;
+    const int32_t cnt = st->nb_count;
+    const int32_t y_buf = st->y_buf;
+    const int64_t iter = st->iter, limit = st->limit;
+    if (status != ST_RUNNING || iter >= limit) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);  // chunks of 64 dbl2 (L is a multiple of 128)
+    const dbl2* y_g = reinterpret_cast<const dbl2*>(y_buf ? P.y1 : P.y0);
+    if constexpr (LDS) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) d[k] = y_g[k];
+        __syncthreads();
+    }
+    const dbl2* yv = LDS ? reinterpret_cast<const dbl2*>(dsm) : y_g;
+    const double* ys = reinterpret_cast<const double*>(yv);
+
+    double bkey = INFINITY, bd = 0.0;
+    int64_t bidx = INT64_MAX;
+    const int nwv = (int)gridDim.x * WAVES;
+    for (int s = (int)blockIdx.x * WAVES + wave; s < cnt; s += nwv) {
+        const int64_t j = P.nb_list[s];
+        const int up = D.at_upper[j];
+        double d;
+        if (P.slack_unit && j >= P.ns) {  // A_j = e_k: no stream
+            d = ys[j - P.ns] - P.c[j];
+        } else {
+            const dbl2* col = reinterpret_cast<const dbl2*>(P.A + j * L) + lane;
+            dbl2 cur[U], nxt[U];
+#pragma unroll
+            for (int t = 0; t < U; ++t) cur[t] = t < nch ? ld2<SPX_NT_A>(col + 64 * t) : dbl2{0.0, 0.0};
+            double d0 = 0.0, d1 = 0.0;
+            for (int c0 = 0; c0 < nch; c0 += U) {
+#pragma unroll
+                for (int t = 0; t < U; ++t)
+                    nxt[t] = c0 + U + t < nch ? ld2<SPX_NT_A>(col + 64 * (c0 + U + t)) : dbl2{0.0, 0.0};
+#pragma unroll
+                for (int t = 0; t < U; ++t) {
+                    if (c0 + t < nch) {
+                        const dbl2 w = yv[64 * (c0 + t) + lane];
+                        d0 = fma(cur[t].x, w.x, d0);
+                        d1 = fma(cur[t].y, w.y, d1);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < U; ++t) cur[t] = nxt[t];
+            }
+            d = wave_sum(d0 + d1) - P.c[j];
+        }
+        const double key = up ? -d : d;  // sigma_j d_j (a sign flip: exact)
+        if (key < -P.eps && argmin_better(key, j, bkey, bidx)) {
+            bkey = key;
+            bidx = j;
+            bd = d;
+        }
+    }
+    if (lane == 0) s_red[wave] = PboxPartial{bkey, bidx, bd, 0.0};
+    __syncthreads();
+    if (tid == 0) D.parts[blockIdx.x] = merge_price<WAVES>(s_red);  // read after the kernel boundary (k_pbox_update)
+}
+
+// ---------------------------------------------------------------------------
+// Entering column, FTRAN fused with the pending rank-1 update, ratio entries
+// ---------------------------------------------------------------------------
+// One row per wave, k_dual_update's stream.  Row i of S is read once, becomes
+// S[i] + E_i r' (the pending pivot; r' from rbuf), is written back in place and
+// dotted with A_p: alpha_i into alpha[(it + 1) & 1].  After the launch S is the
+// true B^-1.  x_b[i] and ub_B[i] are requested ahead of the stream; with ahat_i
+// = sigma_p alpha_i the row's ratio-test entry is max(x_b, 0) / ahat_i (ahat_i >
+// piv_tol: to its lower bound) or max(ub_B - x_b, 0) / -ahat_i (ahat_i <
+// -piv_tol, finite ub_B: to its upper bound), keyed (t, 2 i + side) so that the
+// first row wins ties through every reduction.
+template <bool XL>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_update(Params P, PboxArgs D) {
+    constexpr int WAVES = PBOX_WAVES, U = 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    __shared__ ArgMinEntry s_rat[WAVES];
+    __shared__ PboxSnap Sv;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // one reader per workgroup: workgroup 0 may store ST_OPTIMAL below while
+    // other workgroups start, and every wave of a workgroup must take the same exit
+    if (tid == 0) {
+        Sv.status = st->status;
+        Sv.it = st->iter;
+        Sv.limit = st->limit;
+        Sv.qprev = st->q;
+        Sv.aqprev = st->aq;
+    }
+    __syncthreads();
+    const int64_t it = Sv.it, qp = Sv.qprev;
+    const double aqp = Sv.aqprev;
+    if (Sv.status != ST_RUNNING || it >= Sv.limit) return;
+
+    // pricing's grid step: every workgroup merges the same partials
+    double wk = INFINITY, wd = 0.0;
+    int64_t wj = INT64_MAX;
+    for (int g = tid; g < D.price_grid; g += PBOX_BLOCK) {
+        const PboxPartial v = D.parts[g];
+        if (argmin_better(v.key, v.idx, wk, wj)) {
+            wk = v.key;
+            wj = v.idx;
+            wd = v.d;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double k2 = __shfl_xor(wk, off, 64);
+        const int64_t j2 = __shfl_xor(wj, off, 64);
+        const double d2 = __shfl_xor(wd, off, 64);
+        const bool t = argmin_better(k2, j2, wk, wj);
+        wk = t ? k2 : wk;
+        wj = t ? j2 : wj;
+        wd = t ? d2 : wd;
+    }
+    if (lane == 0) s_red[wave] = PboxPartial{wk, wj, wd, 0.0};
+    __syncthreads();
+    const PboxPartial t = merge_price<WAVES>(s_red);
+    if (t.idx == INT64_MAX) {  // no sigma_j d_j < -eps: optimum
+        if (blockIdx.x == 0 && tid == 0) st->status = ST_OPTIMAL;
+        return;
+    }
+    const int64_t p = t.idx;
+    if (blockIdx.x == 0 && tid == 0) {
+        D.rec->p = p;
+        D.rec->d_p = t.d;
+        D.rec->fresh = 1;
+    }
+
+    const int64_t m = P.m, L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const bool pend = it > 0 && qp >= 0;
+    const dbl2* rp = reinterpret_cast<const dbl2*>(pend ? P.rbuf : P.zeros);
+    const dbl2* ap = reinterpret_cast<const dbl2*>(P.A + p * L);
+    if constexpr (XL) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) {
+            d[k] = rp[k];
+            d[L2 + k] = ap[k];
+        }
+        __syncthreads();
+    }
+    const dbl2* xr = XL ? reinterpret_cast<const dbl2*>(dsm) : rp;
+    const dbl2* xa = XL ? reinterpret_cast<const dbl2*>(dsm) + L2 : ap;
+
+    const int64_t i = (int64_t)blockIdx.x * WAVES + wave;
+    double rt = INFINITY;
+    int64_t ri = INT64_MAX;
+    if (i < m) {  // (wave-uniform; the barrier below is outside)
+        const double sg = D.at_upper[p] ? -1.0 : 1.0;
+        const double xi = P.x_b[i], ubi = D.ub_B[i];
+        const double* a_prev = (it & 1) ? P.alpha1 : P.alpha0;
+        double* a_new = (it & 1) ? P.alpha0 : P.alpha1;
+        const double ei = pend ? eta_entry(a_prev[i], i, qp, aqp) : 0.0;
+        dbl2* row = reinterpret_cast<dbl2*>(P.B0 + i * L) + lane;
+        dbl2 cur[U], nxt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = u < nch ? ld2<SPX_NT_BLOAD>(row + 64 * u) : dbl2{0.0, 0.0};
+        double acc0 = 0.0, acc1 = 0.0;
+        for (int c0 = 0; c0 < nch; c0 += U) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                nxt[u] = c0 + U + u < nch ? ld2<SPX_NT_BLOAD>(row + 64 * (c0 + U + u)) : dbl2{0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (c0 + u < nch) {
+                    const int k = 64 * (c0 + u) + lane;
+                    const dbl2 r = xr[k], a = xa[k];
+                    dbl2 nv;
+                    nv.x = fma(ei, r.x, cur[u].x);
+                    nv.y = fma(ei, r.y, cur[u].y);
+                    st2<SPX_NT_BSTORE>(nv, row + 64 * (c0 + u));
+                    acc0 = fma(nv.x, a.x, acc0);
+                    acc1 = fma(nv.y, a.y, acc1);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        }
+        const double alpha = wave_sum(acc0 + acc1);
+        if (lane == 0) a_new[i] = alpha;
+        const double ah = sg * alpha;  // (a sign flip: exact)
+        if (ah > D.piv_tol) {
+            rt = (xi > 0.0 ? xi : 0.0) / ah;
+            ri = 2 * i;
+        } else if (ah < -D.piv_tol && ubi < INFINITY) {
+            const double gap = ubi - xi;
+            rt = (gap > 0.0 ? gap : 0.0) / (-ah);
+            ri = 2 * i + 1;
+        }
+    }
+    if (lane == 0) s_rat[wave] = ArgMinEntry{rt, ri};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry b = s_rat[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            const ArgMinEntry v = s_rat[w];
+            const bool tk = argmin_better(v.val, v.idx, b.val, b.idx);
+            b.val = tk ? v.val : b.val;
+            b.idx = tk ? v.idx : b.idx;
+        }
+        D.rparts[blockIdx.x] = b;  // read after the kernel boundary (k_pbox_step)
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Ratio-test merge, decision and commit (one workgroup)
+// ---------------------------------------------------------------------------
+// alpha = B^-1 A_p is in alpha[(it + 1) & 1] and S is the true B^-1
+// (k_pbox_update).  A pivot makes (q, alpha_q, alpha[(it + 1) & 1]) the pending
+// one with iter = it + 1 and stages rho = S[q] into rbuf while y takes it.  A
+// flip or an unbounded column leaves iter alone and nothing pending: st->q = 0,
+// st->aq = 1, alpha[it & 1] = e_0 (a reinversion's state: every eta entry 0).
+__global__ __launch_bounds__(1024) void k_pbox_step(Params P, PboxArgs D) {
+    constexpr int BLOCK = 1024, WAVES = BLOCK / 64, CH = 4;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t m = P.m, L = P.L;
+    __shared__ PboxSnap S;
+    __shared__ ArgMinEntry s_red[WAVES];
+    __shared__ ArgMinEntry s_win;
+    __shared__ double s_up;   // u_p
+    __shared__ int32_t s_at;  // at_upper[p], read once: the commit's thread 0 / bookkeeping lane rewrites it
+    if (tid == 0) {
+        S.it = st->iter;
+        S.limit = st->limit;
+        S.status = st->status;
+        S.y_buf = st->y_buf;
+        S.cnt = st->nb_count;
+        S.fresh = D.rec->fresh;
+        S.p = D.rec->p;
+        S.d_p = D.rec->d_p;
+    }
+    __syncthreads();
+    const int64_t it = S.it;
+    if (S.status != ST_RUNNING || it >= S.limit || !S.fresh) return;
+
+    // the ratio test's grid step
+    double bv = INFINITY;
+    int64_t bi = INT64_MAX;
+    for (int g = tid; g < D.update_grid; g += BLOCK) {
+        const ArgMinEntry v = D.rparts[g];
+        if (argmin_better(v.val, v.idx, bv, bi)) {
+            bv = v.val;
+            bi = v.idx;
+        }
+    }
+    wave_argmin(bv, bi);
+    if (lane == 0) s_red[wave] = ArgMinEntry{bv, bi};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry t = s_red[0];
+        for (int w = 1; w < WAVES; ++w)
+            if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
+        s_win = t;
+        s_up = D.ub[S.p];
+        s_at = D.at_upper[S.p];
+    }
+    __syncthreads();
+    const double tq = s_win.val;
+    const bool none = s_win.idx == INT64_MAX;
+    const int64_t q = none ? 0 : (s_win.idx >> 1);
+    const int side = none ? 0 : (int)(s_win.idx & 1);  // 1: the row leaves to its upper bound
+    const int64_t p = S.p;
+    const double u_p = s_up;
+    const int up_p = s_at;
+    const double sg = up_p ? -1.0 : 1.0;
+    const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
+    double* a_cur = (it & 1) ? P.alpha1 : P.alpha0;
+    const bool flip = u_p < INFINITY && (none || u_p <= tq);
+
+    if (flip || none) {
+        // no pivot: S has the pending pivot applied and iter stays, so nothing is pending
+        if (flip) {
+            const double dx = up_p ? -u_p : u_p;  // the column's move
+            const double* Ap = P.A + p * L;
+            for (int64_t i = tid; i < m; i += BLOCK) {
+                P.x_b[i] = fma(-u_p, sg * al[i], P.x_b[i]);
+                D.b_eff[i] = fma(-dx, Ap[i], D.b_eff[i]);
+            }
+        }
+        for (int64_t i = tid; i < L; i += BLOCK) a_cur[i] = (i == 0) ? 1.0 : 0.0;
+        if (tid == 0) {
+            if (flip) {
+                D.at_upper[p] = up_p ? 0 : 1;
+                D.rec->flips += 1;
+            } else {
+                st->status = ST_UNBOUNDED;
+            }
+            st->q = 0;
+            st->aq = 1.0;
+            st->p = p;
+            st->min_e = S.d_p;
+            D.rec->fresh = 0;
+        }
+        return;
+    }
+
+    // pivot it
+    double* y = S.y_buf ? P.y1 : P.y0;
+    const double aq = al[q];
+    const double theta = tq, sy = -(S.d_p / aq);
+    const double x_off = up_p ? u_p : 0.0;  // where the entering column starts from
+    const bool book = tid == BLOCK - 64;    // the last wave's lane 0
+    int64_t leave = -1;
+    double c_p = 0.0;
+    int kp = -1, last = -1;
+    if (book) {
+        leave = P.b_ixs[q];
+        c_p = P.c[p];
+        kp = P.nb_pos[p];
+        last = P.nb_list[S.cnt - 1];
+    }
+    const double* Sq = P.B0 + q * L;  // rho: row q of B^-1 before this pivot
+    for (int64_t i0 = tid; i0 < L; i0 += (int64_t)CH * BLOCK) {
+        double xv[CH], av[CH], yv[CH], rv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            xv[u] = i < m ? P.x_b[i] : 0.0;
+            av[u] = i < m ? al[i] : 0.0;
+            yv[u] = i < L ? y[i] : 0.0;
+            rv[u] = i < L ? Sq[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            if (i < m) P.x_b[i] = (i == q) ? x_off + sg * theta : fma(-theta, sg * av[u], xv[u]);
+            if (i < L) {
+                y[i] = fma(sy, rv[u], yv[u]);
+                P.rbuf[i] = rv[u];  // the pending pivot's row, before the next update overwrites it
+            }
+        }
+    }
+    if (book) {
+        P.c_B[q] = c_p;
+        P.b_ixs[q] = p;
+        D.ub_B[q] = u_p;
+        D.at_upper[p] = 0;
+        D.at_upper[leave] = (int8_t)side;
+        // nb_list / nb_pos as pivot_bookkeeping keeps them: swap-remove p, append the leaving column
+        int cnt = S.cnt;
+        P.nb_list[kp] = last;
+        P.nb_pos[last] = kp;
+        P.nb_pos[p] = -1;
+        --cnt;
+        P.nb_list[cnt] = (int32_t)leave;
+        P.nb_pos[leave] = cnt;
+        ++cnt;
+        st->nb_count = cnt;
+        st->aq = aq;
+        st->s_y = sy;
+        st->y_applied = it + 1;  // y and x_b are current: only B^-1 stays pending
+        st->xb_applied = it + 1;
+        st->p = p;
+        st->q = q;
+        st->min_e = S.d_p;
+        st->iter = it + 1;
+        record_pivot(P, it, p, q);
+        D.rec->fresh = 0;
+        if (side) D.rec->to_upper += 1;
+    }
+}
+
+// rbuf = row st->q of S where a pivot is pending (one workgroup)
+__global__ __launch_bounds__(1024) void k_pbox_stage(Params P) {
+    const DevState* st = P.st;
+    const int64_t it = st->iter, q = st->q;
+    if (it <= 0 || q < 0 || q >= P.m) return;
+    const double* Sq = P.B0 + q * P.L;
+    for (int64_t k = threadIdx.x; k < P.L; k += 1024) P.rbuf[k] = Sq[k];
+}
+
+// ---------------------------------------------------------------------------
+// Host-side launchers
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr size_t PBOX_LDS_CAP = 150 * 1024;
+
+template <typename K>
+hipError_t set_lds(K kernel, size_t lds) {
+    if (lds <= 65536) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds);
+}
+
+template <typename K>
+hipError_t launch_timed(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const Params& P,
+                        const PboxArgs& D) {
+    if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), (uint32_t)lds, s, e0, e1, 0, P, D);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), lds, s, P, D);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t pbox_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, PboxCfg* cfg) {
+    const size_t vec1 = (size_t)P.L * 8;   // y
+    const size_t vec2 = (size_t)P.L * 16;  // the pending row and A_p
+    cfg->price_lds = !global_y && vec1 <= PBOX_LDS_CAP;
+    cfg->update_lds = vec2 <= PBOX_LDS_CAP;
+    hipError_t e = hipSuccess;
+    int per_cu = 0;
+    if (cfg->price_lds) {
+        e = set_lds(k_pbox_price<true>, vec1);
+        if (e == hipSuccess)
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pbox_price<true>, PBOX_BLOCK, vec1);
+    } else {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pbox_price<false>, PBOX_BLOCK, 0);
+    }
+    if (e != hipSuccess) return e;
+    if (cfg->update_lds) {
+        e = set_lds(k_pbox_update<true>, vec2);
+        if (e != hipSuccess) return e;
+    }
+    if (per_cu < 1) per_cu = 1;
+    const int64_t cols = P.n - P.m;  // the non-basic count never changes
+    const int64_t want = (cols + PBOX_WAVES - 1) / PBOX_WAVES;
+    const int64_t cap = (int64_t)cus * per_cu;
+    int64_t g = want < cap ? want : cap;
+    if (g < 1) g = 1;
+    cfg->price_grid = price_grid_opt > 0 ? price_grid_opt : (int)g;
+    cfg->update_grid = (int)((P.m + PBOX_WAVES - 1) / PBOX_WAVES);
+    return hipSuccess;
+}
+
+hipError_t launch_pbox_price(const Params& P, const PboxArgs& D, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
+                             hipEvent_t e1) {
+    if (c.price_lds) return launch_timed(k_pbox_price<true>, c.price_grid, (size_t)P.L * 8, s, e0, e1, P, D);
+    return launch_timed(k_pbox_price<false>, c.price_grid, 0, s, e0, e1, P, D);
+}
+
+hipError_t launch_pbox_update(const Params& P, const PboxArgs& D, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
+                              hipEvent_t e1) {
+    if (c.update_lds) return launch_timed(k_pbox_update<true>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D);
+    return launch_timed(k_pbox_update<false>, c.update_grid, 0, s, e0, e1, P, D);
+}
+
+hipError_t launch_pbox_step(const Params& P, const PboxArgs& D, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_step, dim3(1), dim3(1024), 0, s, P, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_stage(const Params& P, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_stage, dim3(1), dim3(1024), 0, s, P);
+    return hipGetLastError();
+}
+
+}  // namespace spx

@@ -1,0 +1,225 @@
+"""Bounded primal simplex loop (SPX_ALGO_PRIMAL_BOX) at C3's
+shape against the dual and the primal explicit pass.
+
+Every side runs in a child process of its own on device 0, in this order, so the
+first and the last record show the drift of the box:
+  primal        the headline LP (seeded generator), window=-1: k_price / k_update
+  dual          the covering LP of tests/dual_ref.py, SPX_ALGO_DUAL (Dantzig):
+                k_dual_price / k_dual_update
+  pbox          the bounded LP of tests/primal_box_ref.py boxed_primal(m, n, seed),
+                SPX_ALGO_PRIMAL_BOX: k_pbox_price / k_pbox_update
+  primal_again
+Per side: it/s over --k timed pivots of an untimed context after --warm pivots,
+and from a timing context (SPX_FLAG_TIMING) the mean kernel times of the same
+passes, the pricing kernel's algorithmic bandwidth 8 (m + 1) x streamed
+non-basic columns / time against 8 TB/s, and rest_us = what a pass takes beyond
+its two big kernels (the one-workgroup kernel and the launch gaps).  The pbox
+record also carries the flip passes and to-upper pivots of the timed block.
+
+--solve times whole bounded solves to the optimum at every --solve-shape
+(pivots, seconds, flip counts), each checked by the CPU certificate recomputed
+from the returned basis and placements (tests/dual_box_ref.py certificate).
+--rows adds, per solve shape, the same LP with every finite bound written as a
+row (x_j + s = u_j; a bounded slack u_k becomes the row a_k.x >= b_k - u_k,
+negated) on the primal loop with its default eta window.
+
+    python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
+                               [--out profiles/pbox_c3.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))
+
+PEAK = 8.0e12  # MI355X HBM bytes/s the fractions are quoted against
+
+
+def measure(make_ctx, k, warm, flips=False):
+    """it/s from an untimed context, kernel means from a timing one."""
+    with make_ctx(False) as ctx:
+        ctx.iterate(warm)
+        _, p0 = ctx.iterate(0)
+        t0 = time.perf_counter()
+        st, p1 = ctx.iterate(k)
+        dt = time.perf_counter() - t0
+    with make_ctx(True) as ctx:
+        ctx.iterate(warm)
+        ctx.kernel_times()
+        b0 = ctx.info()
+        f0 = ctx.primal_flips() if flips else None
+        ctx.iterate(k)
+        kt = ctx.kernel_times()
+        b1 = ctx.info()
+        f1 = ctx.primal_flips() if flips else None
+    price_us = 1e3 * kt["price_ms"] / max(kt["price_launches"], 1)
+    update_us = 1e3 * kt["update_ms"] / max(kt["update_launches"], 1)
+    bytes_price = 0.5 * (b0["bytes_price"] + b1["bytes_price"])
+    res = {"pivots": p1 - p0, "status": int(st), "it_per_s": round((p1 - p0) / dt, 1),
+           "price_us": round(price_us, 2), "update_us": round(update_us, 2),
+           "rest_us": round(1e6 * dt / max(p1 - p0, 1) - price_us - update_us, 2),
+           "timed_passes": kt["price_launches"], "bytes_price": bytes_price, "bytes_update": b1["bytes_update"],
+           "price_TBps": round(bytes_price / (price_us * 1e-6) / 1e12, 3),
+           "price_frac_of_8TBps": round(bytes_price / (price_us * 1e-6) / PEAK, 3),
+           "update_TBps": round(b1["bytes_update"] / (update_us * 1e-6) / 1e12, 3)}
+    if flips:
+        res["flip_passes"], res["to_upper"] = f1[0] - f0[0], f1[1] - f0[1]
+    return res
+
+
+def run_primal(a):
+    import simplex_method_gpu_amd as spx
+
+    return measure(lambda timing: spx.Context(m=a.m, n=a.n, seed=0, device=0, window=-1, timing=timing), a.k, a.warm)
+
+
+def run_dual(a):
+    import numpy as np
+
+    import dual_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c = dual_ref.covering(a.m, a.n, a.seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    return measure(lambda timing: spx.Context(A_cols, b, c, device=0, window=-1, algorithm=spx.ALGO_DUAL,
+                                              timing=timing), a.k, a.warm)
+
+
+def run_pbox(a):
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = primal_box_ref.boxed_primal(a.m, a.n, a.seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    return measure(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                                              timing=timing), a.k, a.warm, flips=True)
+
+
+def bounds_as_rows(A, b, c, u):
+    """The bounded LP with every finite bound as a row of its own (b stays >= 0
+    where the slack basis is feasible for the bounded LP)."""
+    import numpy as np
+
+    m, n = A.shape
+    ns = n - m
+    rows, rhs = [], []
+    for j in np.flatnonzero(np.isfinite(u[:ns])):  # x_j <= u_j
+        r = np.zeros(ns)
+        r[j] = 1.0
+        rows.append(r)
+        rhs.append(u[j])
+    for k in np.flatnonzero(np.isfinite(u[ns:])):  # s_k <= u_k: -a_k.x <= u_k - b_k
+        rows.append(-A[k, :ns])
+        rhs.append(u[ns + k] - b[k])
+    G = np.vstack([A[:, :ns]] + [np.asarray(rows)]) if rows else A[:, :ns]
+    h = np.concatenate([b, np.asarray(rhs)])
+    m2 = G.shape[0]
+    A2 = np.hstack([G, np.eye(m2)])
+    return A2, h, np.concatenate([c[:ns], np.zeros(m2)])
+
+
+def run_solve(a):
+    """Whole solves to the optimum: the first after a warm-up of the same context."""
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    out = []
+    for (m, n, seed) in [tuple(s) for s in a.solve_shape]:
+        A, b, c, u = primal_box_ref.boxed_primal(m, n, seed)
+        with spx.Context(np.ascontiguousarray(A.T), b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                         refactor_every=a.refactor) as ctx:
+            ctx.iterate(20)  # (first-launch costs)
+            ctx.reset()
+            t0 = time.perf_counter()
+            r = ctx.solve()
+            dt = time.perf_counter() - t0
+            x, up = ctx.primal()
+            fl = ctx.primal_flips()
+        rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "status": int(r.status),
+               "pivots": r.pivots, "z": r.z, "seconds": round(dt, 4), "it_per_s": round(r.pivots / dt, 1),
+               "flip_passes": fl[0], "to_upper": fl[1], "at_upper": int(up.sum())}
+        if int(r.status) == 1:
+            viol, dviol, zc = primal_box_ref.certificate(A, b, c, u, r.b_ixs, up)
+            rec.update({"cert_bound_violation": viol, "cert_dual_violation": dviol,
+                        "cert_z_rel": abs(zc - r.z) / abs(zc), "cert_ok": bool(viol <= 1e-9 and dviol <= 1e-7)})
+        if a.rows:
+            A2, b2, c2 = bounds_as_rows(A, b, c, u)
+            m2, n2 = A2.shape
+            with spx.Context(np.ascontiguousarray(A2.T), b2, c2, device=0, ratio_test=spx.RATIO_GUARDED,
+                             refactor_every=a.refactor) as ctx:
+                ctx.iterate(20)
+                ctx.reset()
+                t0 = time.perf_counter()
+                r2 = ctx.solve()
+                dt2 = time.perf_counter() - t0
+            rec["rows"] = {"m": m2, "n": n2, "status": int(r2.status), "pivots": r2.pivots, "z": r2.z,
+                           "seconds": round(dt2, 4), "z_rel_to_bounded": abs(r2.z - r.z) / abs(r.z)}
+        out.append(rec)
+    return out
+
+
+def child(a, role):
+    cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--m", str(a.m), "--n", str(a.n),
+           "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--refactor", str(a.refactor)]
+    if a.rows:
+        cmd.append("--rows")
+    for shape in a.solve_shape:
+        cmd += ["--solve-shape"] + [str(v) for v in shape]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    if out.returncode != 0:
+        sys.stderr.write(out.stdout + out.stderr)
+        raise SystemExit(f"{role} run failed ({out.returncode})")
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--m", type=int, default=4096)
+    ap.add_argument("--n", type=int, default=16384)
+    ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--k", type=int, default=1000)
+    ap.add_argument("--warm", type=int, default=200)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--solve", action="store_true")
+    ap.add_argument("--solve-shape", type=int, nargs=3, action="append", default=[], metavar=("M", "N", "SEED"))
+    ap.add_argument("--rows", action="store_true", help="with --solve: the bounds as rows on the windowed primal loop too")
+    ap.add_argument("--refactor", type=int, default=500)
+    ap.add_argument("--role", default=None, choices=[None, "primal", "dual", "pbox", "solve"])
+    a = ap.parse_args()
+    if a.role:  # a child: one side, one JSON line
+        run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve}[a.role]
+        print(json.dumps(run(a)), flush=True)
+        return
+    if a.k < 252:
+        ap.error("--k: at least 252 timed pivots")
+    res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "seed": a.seed}
+    for key, role in (("primal", "primal"), ("dual", "dual"), ("pbox", "pbox"), ("pbox_again", "pbox"),
+                      ("dual_again", "dual"), ("primal_again", "primal")):
+        res[key] = child(a, role)
+        sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+        sys.stderr.flush()
+    pb = res["pbox"]
+    for base in ("dual", "primal"):
+        q = res[base]
+        res[f"pbox_over_{base}"] = {k: round(pb[k] / q[k], 3) for k in ("price_us", "update_us", "rest_us", "it_per_s")}
+    if a.solve and a.solve_shape:
+        res["solve"] = child(a, "solve")
+    print(json.dumps(res), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
