@@ -47,10 +47,16 @@ extern "C" {
 #define SPX_STATUS_MAX_ITER       0
 #define SPX_STATUS_OPTIMUM_FOUND  1
 #define SPX_STATUS_UNBOUNDED      2
-#define SPX_STATUS_THETA_OVERFLOW 3 /* kept for ABI parity; unreachable since v2 */
-#define SPX_STATUS_INFEASIBLE     4 /* dual loop only: a basic variable is negative
-                                       and its row has no dual ratio-test candidate,
-                                       so no x >= 0 satisfies the constraints       */
+#define SPX_STATUS_THETA_OVERFLOW 3 /* the reference's status, unreachable there since
+                                       v2; here: a numerical breakdown of the bounded
+                                       primal loop's phase 1 (no blocking row and no
+                                       bound on the entering column, which exact
+                                       arithmetic excludes)                          */
+#define SPX_STATUS_INFEASIBLE     4 /* dual loop: a basic variable is negative and its
+                                       row has no dual ratio-test candidate; bounded
+                                       primal loop, phase 1: no column lowers the sum
+                                       of bound violations.  Either way no 0 <= x <= u
+                                       satisfies the constraints                     */
 
 #define SPX_OK             0
 #define SPX_ERR_ARG       -1  /* bad argument (m > n, m <= 0, NULL, ...)     */
@@ -172,9 +178,31 @@ typedef struct spx_opts {
  *         spx_iterate(k) count pivots only.  With every bound +inf this is the
  *         primal loop's Dantzig rule with SPX_RATIO_GUARDED.  Scope and refusals
  *         are DUAL's (spx_create: SPX_ERR_ARG naming the combination; spx_price /
- *         spx_pivot / spx_group_iterate: SPX_ERR_STATE).  No primal phase 1, no
- *         Devex / steepest edge, no non-zero or free lower bounds.  SPX_ALGO_PRIMAL
- *         itself still refuses finite bounds. */
+ *         spx_pivot / spx_group_iterate: SPX_ERR_STATE).  No Devex / steepest
+ *         edge, no non-zero or free lower bounds.  SPX_ALGO_PRIMAL itself still
+ *         refuses finite bounds.
+ *         Phase 1 (opt-in: SPX_FLAG_PRIMAL_PHASE1, spx_set_primal_phase1;
+ *         DESIGN.md §7f).  With it the entry check refuses nothing: row i is
+ *         *below* when x_b[i] < -feas_tol, *above* when x_b[i] > u_k + feas_tol,
+ *         feasible otherwise; ninf counts the below and above rows, and a pass
+ *         that starts with ninf > 0 is a phase-1 pass: w_i = +1 (below), -1
+ *         (above), 0 (feasible), y1 = w.B^-1, d_j = y1.A_j with no cost term,
+ *         the same entering rule (none: SPX_STATUS_INFEASIBLE).  Ratio test:
+ *         feasible rows block as above; a below row blocks only when ahat_i <
+ *         -piv_tol, at t_i = x_b[i] / ahat_i, and leaves to its lower bound; an
+ *         above row only when ahat_i > piv_tol, at t_i = (x_b[i] - u_k) / ahat_i,
+ *         and leaves to its upper bound; an infeasible row moving away from its
+ *         bound does not block.  Flips and pivots are as above, except that y is
+ *         not updated; no row and u_p = +inf is SPX_STATUS_THETA_OVERFLOW (a
+ *         numerical breakdown).  The rows are classified again after every
+ *         phase-1 pass and after every reinversion; no feasible row becomes
+ *         infeasible, so ninf never grows.  The first pass that starts with ninf
+ *         == 0 recomputes y = c_B.B^-1 once and is an ordinary pass; so does every
+ *         readback of y and every spx_set_algorithm in between.  Pivots, the
+ *         trace, refactor_every, spx_iterate(k) and spx_get_primal_flips count
+ *         both phases.  With phase 1 on and a feasible entry the loop launches
+ *         exactly the passes it launches without.  Still out: a long-step phase
+ *         1, phase 1 under SPX_ALGO_PRIMAL. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
 #define SPX_ALGO_PRIMAL_BOX 2
@@ -324,6 +352,11 @@ typedef struct spx_opts {
                                        accepted and inert while the context runs the
                                        primal loop or has no finite bound          */
 
+#define SPX_FLAG_PRIMAL_PHASE1 8192 /* the bounded primal loop (SPX_ALGO_PRIMAL_BOX)
+                                       starts with its phase 1 enabled (default off:
+                                       a basis out of its bounds is refused); accepted
+                                       and inert under the other algorithms         */
+
 void spx_default_opts(spx_opts* opts);
 
 /* Allocate device state, upload A (column-major, ld = m), b, c and set the
@@ -461,6 +494,18 @@ int spx_set_cost(spx_ctx* ctx, const double* c /* n */);
  * Counted on the device by the kernel that commits the pass. */
 int spx_get_primal_flips(spx_ctx* ctx, int64_t out[2]);
 
+/* Phase 1 of the bounded primal loop on (non-zero) or off, between any two
+ * calls and under any algorithm (it takes effect when the context runs
+ * SPX_ALGO_PRIMAL_BOX).  The entry check runs again before the next pass. */
+int spx_set_primal_phase1(spx_ctx* ctx, int32_t on);
+
+/* Phase-1 counters of the bounded primal loop, kept on the device by the kernel
+ * that commits the pass: out[0] phase-1 passes since spx_create or spx_reset
+ * (flip passes included), out[1] phase-1 pivots, out[2] rows out of their
+ * bounds at the last entry check, out[3] rows out of their bounds now (as of
+ * the last classification). */
+int spx_get_primal_phase1(spx_ctx* ctx, int64_t out[4]);
+
 /* Upper bounds ub[0..n) of all columns, slacks included (+inf = none, NULL =
  * none at all); lower bounds are 0.  The basis and the pivot count are kept and
  * the status is back to running: a non-basic column at an upper bound that
@@ -530,6 +575,12 @@ int spx_get_weights(spx_ctx* ctx, double* w);
  * Dual loop: the dual ratio-test kernel and the FTRAN + update kernel. */
 int spx_kernel_times(spx_ctx* ctx, double* price_ms, int64_t* price_launches,
                      double* update_ms, int64_t* update_launches);
+
+/* With SPX_FLAG_TIMING, bounded primal loop with phase 1 on: total device
+ * milliseconds and count of the v.B^-1 step (k_pbox_vtb and its reduction) of
+ * the four-step passes since the last call (resets); a step that found nothing
+ * to do (phase 2, y current) is counted with its near-zero time. */
+int spx_pbox_vtb_times(spx_ctx* ctx, double* ms, int64_t* launches);
 
 /* With SPX_FLAG_TIMING: device milliseconds summed since the last call (resets)
  * of out[0] the pricing kernel, out[1] pricing + the cross-rank MINLOC

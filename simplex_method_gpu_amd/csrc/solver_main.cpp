@@ -38,6 +38,11 @@
 //                  (b >= 0, every bounded slack's u >= b_i); --json then carries
 //                  the flip-pass and to-upper counts.  Not with --dual, --mps,
 //                  --window N > 0 or --tableau (refused by name, exit 1)
+//   --phase1       with --primal-box only (refused by name otherwise, exit 1): the
+//                  loop's phase 1 (SPX_FLAG_PRIMAL_PHASE1), so the slack basis may
+//                  be out of its bounds (b of any sign, any slack bounds); an
+//                  infeasible LP ends with "Problem infeasible."; --json then
+//                  also carries the phase-1 pass and pivot counts
 //   --bounds F     upper bounds 0 <= x_j <= u_j of all n columns for --dual or
 //                  --primal-box (spx_set_bounds): F holds n whitespace-separated
 //                  values, "inf" = none; without either the library's refusal is
@@ -86,7 +91,7 @@ static void print_elapsed_time(const char* msg, double dur) {
 static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
-                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box]"
+                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1]]"
                  " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
@@ -106,7 +111,7 @@ int main(int argc, char* argv[]) {
     int ratio = -1, window = 0, pricing = SPX_PRICING_DANTZIG;
     double piv_tol = 1e-9, feas_tol = 1e-9, big_m = 0.0;
     int64_t refactor = 0;
-    bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false, primal_box = false;
+    bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false, primal_box = false, phase1 = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -142,6 +147,7 @@ int main(int argc, char* argv[]) {
         else if (s == "--tableau") tableau = true;
         else if (s == "--dual") dual = true;
         else if (s == "--primal-box") primal_box = true;
+        else if (s == "--phase1") phase1 = true;
         else if (s == "--bounds") { need(1); bounds_path = argv[++a]; }
         else if (s == "--dual-pricing") {
             need(1);
@@ -177,6 +183,10 @@ int main(int argc, char* argv[]) {
     }
     if (!path && !gen) {
         std::cerr << "Please, specify an input file.\n";
+        return 1;
+    }
+    if (phase1 && !primal_box) {
+        std::cerr << "--phase1 needs --primal-box: it is the bounded primal loop's phase 1\n";
         return 1;
     }
     if (primal_box) {
@@ -239,6 +249,7 @@ int main(int argc, char* argv[]) {
     if (primal_box) o.algorithm = SPX_ALGO_PRIMAL_BOX;
     if (dual_steepest) o.flags |= SPX_FLAG_DUAL_STEEPEST;
     if (dual_long) o.flags |= SPX_FLAG_DUAL_LONG_STEP;
+    if (phase1) o.flags |= SPX_FLAG_PRIMAL_PHASE1;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)
@@ -290,6 +301,8 @@ int main(int argc, char* argv[]) {
     if (dual) spx_get_dual_flips(ctx, flips);
     int64_t pflips[2] = {0, 0};
     if (primal_box) spx_get_primal_flips(ctx, pflips);
+    int64_t ph1[4] = {0, 0, 0, 0};
+    if (phase1) spx_get_primal_phase1(ctx, ph1);
     spx_destroy(ctx);
     const TimePoint t_dealloc_end = Clock::now();
 
@@ -375,6 +388,9 @@ int main(int argc, char* argv[]) {
                       << ", \"flip_passes\": " << flips[1] << ", \"max_flips\": " << flips[2];
         if (primal_box)
             std::cout << ", \"flip_passes\": " << pflips[0] << ", \"to_upper\": " << pflips[1];
+        if (phase1)
+            std::cout << ", \"phase1_passes\": " << ph1[0] << ", \"phase1_pivots\": " << ph1[1]
+                      << ", \"phase1_rows\": " << ph1[2];
         std::cout << ", \"solve_s\": " << seconds(t_init_end, t_loop_end) << "}\n";
     }
     return 0;

@@ -173,6 +173,7 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
     }
     x->algo = x->opts.algorithm;
     dual_on_create(x);
+    pbox_on_create(x);
     P.ratio = rule;
     P.piv_tol = rule == SPX_RATIO_REFERENCE ? 0.0 : x->opts.piv_tol;
     P.feas_tol = rule == SPX_RATIO_HARRIS ? x->opts.feas_tol : 0.0;
@@ -983,6 +984,7 @@ int reinvert_basis(spx_ctx* x, const int64_t* basis) {
     x->nw = 0;
     x->dw_ok = false;
     dual_on_reinvert(x);
+    SPX_TRY(pbox_on_reinvert(x));
     return read_state(x);
 }
 
@@ -1225,6 +1227,7 @@ int read_state(spx_ctx* x) {
 // vectors in HBM are current.  Not valid between spx_price and spx_pivot.
 int flush(spx_ctx* x) {
     if (x->stepped_price) return fail(SPX_ERR_STATE, "state readback between spx_price and spx_pivot");
+    SPX_TRY(pbox_fresh_y(x));  // bounded primal phase 1 does not maintain y
     if (x->P.win) {  // fold every complete pivot: the explicit form the readback kernels expect
         HIP_TRY(launch_fold(x->P, 2, x->cus, x->stream));
         HIP_TRY(launch_tab_binv(x->P, x->stream));  // tableau without k_fold: B_w from T_w
@@ -1325,6 +1328,7 @@ void spx_destroy(spx_ctx* x) {
     for (hipEvent_t e : x->ev_xend) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_loop) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_fold) (void)hipEventDestroy(e);
+    for (hipEvent_t e : x->pbox.ev_vtb) (void)hipEventDestroy(e);
     if (x->comm) (void)ncclCommDestroy(x->comm);
     for (void* p : x->mbox_opened) (void)hipIpcCloseMemHandle(p);
     for (void* p : x->allocs) (void)hipFree(p);

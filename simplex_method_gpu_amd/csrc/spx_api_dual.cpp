@@ -323,6 +323,9 @@ int dual_switch_algorithm(spx_ctx* x, int32_t algo) {
         return fail(SPX_ERR_STATE, "the primal loop does not run with finite upper bounds (spx_set_bounds): bounded "
                     "variables are the dual simplex loop's and the bounded primal loop's (SPX_ALGO_PRIMAL_BOX); remove "
                     "the bounds first");
+    // the bounded primal loop's phase 1 does not maintain y: whichever loop takes the
+    // basis gets y = c_B B^-1 (the primal loop would go on updating a stale y)
+    SPX_TRY(pbox_fresh_y(x));
     if (algo == SPX_ALGO_DUAL || algo == SPX_ALGO_PRIMAL_BOX) {
         if (const char* why = dual_conflict(x->opts, x->P.win))
             return fail(SPX_ERR_STATE, "the %s does not run %s",

@@ -17,10 +17,31 @@ namespace {
 // b, c or the algorithm from outside: placements kept (a column at an upper
 // bound that no longer exists goes to lower), x_b recomputed from them, and
 // -feas_tol <= x_b[i] <= ub_B[i] + feas_tol on the host.  No normalisation by
-// reduced-cost sign: that is the dual loop's.
+// reduced-cost sign: that is the dual loop's.  With phase 1 on
+// nothing is refused: k_pbox_classify writes w, ninf and ninf0, and the passes
+// are the four-step ones while rows are out of their bounds.
+int read_phase(spx_ctx* x) {
+    PboxPhase ph;
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(&ph, x->pbox.p1.ph, sizeof ph, hipMemcpyDeviceToHost));
+    x->pbox.ninf = ph.ninf;
+    x->pbox.y_stale = ph.y_stale;
+    if (!ph.y_stale && ph.ninf == 0) x->pbox.y_dirty = false;
+    return SPX_OK;
+}
+
 int pbox_check_entry(spx_ctx* x) {
     const size_t m = (size_t)x->m;
+    SPX_TRY(pbox_fresh_y(x));  // (a phase 1 that was switched off mid-way: the plain passes need y)
     SPX_TRY(box_replace_xb(x));
+    if (x->pbox.phase1) {
+        // phase 1: a row out of its bounds is not an error; the device classifies and the passes start there
+        HIP_TRY(launch_pbox_classify(x->P, x->pbox.args, x->pbox.p1, true, x->stream));
+        HIP_TRY(launch_pbox_stage(x->P, x->stream));
+        SPX_TRY(read_phase(x));
+        x->pbox.checked = true;
+        return SPX_OK;
+    }
     std::vector<double> xb(m), ubB(m);
     std::vector<int64_t> bix(m);
     HIP_TRY(hipStreamSynchronize(x->stream));
@@ -57,6 +78,13 @@ int pbox_setup(spx_ctx* x) {
     s.args.price_grid = s.cfg.price_grid;
     s.args.update_grid = s.cfg.update_grid;
     s.args.piv_tol = x->opts.piv_tol;
+    s.p1.vtb_blocks = s.cfg.vtb_blocks;
+    s.p1.force = 0;
+    s.p1.feas_tol = x->opts.feas_tol;
+    SPX_TRY(x->alloc(&s.p1.w, (size_t)x->L));
+    SPX_TRY(x->alloc(&s.p1.yp, (size_t)x->L));
+    SPX_TRY(x->alloc(&s.p1.vparts, (size_t)s.cfg.vtb_blocks * (size_t)x->L));
+    SPX_TRY(x->alloc(&s.p1.ph, 1));
     SPX_TRY(x->alloc(&s.args.rec, 1));
     return SPX_OK;
 }
@@ -65,10 +93,14 @@ int pbox_setup(spx_ctx* x) {
 // pivot or a flip; the host enqueues as many passes as pivots are missing,
 // synchronises once, and goes round again for the flips' share.  Every kernel
 // returns at once when the device status is not running or the limit is reached.
+// Phase 1: while the host last saw ninf > 0 or y stale a pass is the four-step
+// one (k_pbox_vtb first, then the kernels that read the phase from the device),
+// which runs on through the switch inside a round; the readback that shows
+// ninf == 0 and y current brings the three-launch pass back.
 int iterate_pbox(spx_ctx* x, int64_t k) {
     SPX_TRY(pbox_setup(x));
     if (!x->pbox.checked) SPX_TRY(pbox_check_entry(x));
-    const PboxState& s = x->pbox;
+    PboxState& s = x->pbox;
     const int64_t target = x->pivots + k;
     SPX_TRY(set_limit(x, target));
     while (x->status == SPX_STATUS_MAX_ITER && x->pivots < target) {
@@ -76,6 +108,27 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
         for (int64_t i = 0; i < round; ++i) {
             hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
             if (x->timing) SPX_TRY(pass_events(x, &p0, &p1, &u0, &u1));
+            if (s.phase1 && (s.ninf > 0 || s.y_stale)) {
+                s.y_dirty = true;
+                hipEvent_t v0 = nullptr, v1 = nullptr;
+                if (x->timing) {
+                    while (s.ev_vtb.size() < 2 * (s.n_vtb + 1)) {
+                        hipEvent_t e;
+                        HIP_TRY(hipEventCreate(&e));
+                        s.ev_vtb.push_back(e);
+                    }
+                    v0 = s.ev_vtb[2 * s.n_vtb];
+                    v1 = s.ev_vtb[2 * s.n_vtb + 1];
+                    ++s.n_vtb;
+                }
+                HIP_TRY(launch_pbox_vtb(x->P, s.p1, s.cfg, x->stream, v0, v1));
+                HIP_TRY(launch_pbox_price1(x->P, s.args, s.p1, s.cfg, x->stream, p0, p1));
+                if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
+                HIP_TRY(launch_pbox_update1(x->P, s.args, s.p1, s.cfg, x->stream, u0, u1));
+                HIP_TRY(launch_pbox_step1(x->P, s.args, s.p1, x->stream));
+                ++x->n_eager;
+                continue;
+            }
             HIP_TRY(launch_pbox_price(x->P, s.args, s.cfg, x->stream, p0, p1));
             if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
             HIP_TRY(launch_pbox_update(x->P, s.args, s.cfg, x->stream, u0, u1));
@@ -83,17 +136,54 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
             ++x->n_eager;
         }
         SPX_TRY(read_state(x));
+        if (s.phase1) SPX_TRY(read_phase(x));
     }
     return SPX_OK;
 }
 
 int pbox_on_reset(spx_ctx* x) {
-    if (x->pbox.args.rec) HIP_TRY(hipMemsetAsync(x->pbox.args.rec, 0, sizeof(PboxRec), x->stream));
+    if (x->pbox.args.rec) {
+        HIP_TRY(hipMemsetAsync(x->pbox.args.rec, 0, sizeof(PboxRec), x->stream));
+        HIP_TRY(hipMemsetAsync(x->pbox.p1.ph, 0, sizeof(PboxPhase), x->stream));  // (launch_reset rebuilds y)
+    }
     x->pbox.checked = false;
+    x->pbox.y_dirty = false;
+    x->pbox.ninf = x->pbox.y_stale = 0;
     return SPX_OK;
 }
 
 void pbox_on_change(spx_ctx* x) { x->pbox.checked = false; }
+
+void pbox_on_create(spx_ctx* x) { x->pbox.phase1 = (x->opts.flags & SPX_FLAG_PRIMAL_PHASE1) != 0; }
+
+// a reinversion has rebuilt y from c_B: nothing stale; x_b is new, so the rows
+// are classified again (the entry check does it itself when one is due)
+int pbox_on_reinvert(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    if (!s.p1.ph) return SPX_OK;
+    HIP_TRY(hipMemsetAsync(&s.p1.ph->y_stale, 0, sizeof(int32_t), x->stream));
+    s.y_stale = 0;
+    s.y_dirty = false;
+    if (s.phase1 && s.checked && x->algo == SPX_ALGO_PRIMAL_BOX) {
+        HIP_TRY(launch_pbox_classify(x->P, s.args, s.p1, false, x->stream));
+        SPX_TRY(read_phase(x));
+    }
+    return SPX_OK;
+}
+
+// y = c_B B^-1 where phase-1 pivots left y behind (the device decides: the
+// launches do nothing when its mark is clear), then the mark is cleared
+int pbox_fresh_y(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    if (!s.p1.ph || !s.y_dirty) return SPX_OK;
+    Pbox1Args a = s.p1;
+    a.force = 1;
+    HIP_TRY(launch_pbox_vtb(x->P, a, s.cfg, x->stream, nullptr, nullptr));
+    HIP_TRY(hipMemsetAsync(&s.p1.ph->y_stale, 0, sizeof(int32_t), x->stream));
+    s.y_stale = 0;
+    s.y_dirty = false;
+    return SPX_OK;
+}
 
 }  // namespace spx_host
 
@@ -110,6 +200,45 @@ int spx_get_primal_flips(spx_ctx* x, int64_t out[2]) {
     HIP_TRY(hipMemcpy(&r, x->pbox.args.rec, sizeof r, hipMemcpyDeviceToHost));
     out[0] = r.flips;
     out[1] = r.to_upper;
+    return SPX_OK;
+}
+
+int spx_set_primal_phase1(spx_ctx* x, int32_t on) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_primal_phase1 between spx_price and spx_pivot");
+    SPX_TRY(pbox_fresh_y(x));
+    x->pbox.phase1 = on != 0;
+    x->pbox.checked = false;  // the entry check decides again (and classifies)
+    return SPX_OK;
+}
+
+int spx_pbox_vtb_times(spx_ctx* x, double* ms, int64_t* launches) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (!x->timing) return fail(SPX_ERR_STATE, "context created without SPX_FLAG_TIMING");
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    double t = 0.0;
+    for (size_t i = 0; i < x->pbox.n_vtb; ++i) {
+        float e = 0.f;
+        HIP_TRY(hipEventElapsedTime(&e, x->pbox.ev_vtb[2 * i], x->pbox.ev_vtb[2 * i + 1]));
+        t += e;
+    }
+    if (ms) *ms = t;
+    if (launches) *launches = (int64_t)x->pbox.n_vtb;
+    x->pbox.n_vtb = 0;
+    return SPX_OK;
+}
+
+int spx_get_primal_phase1(spx_ctx* x, int64_t out[4]) {
+    if (!x || !out) return fail(SPX_ERR_ARG, "NULL argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!x->pbox.p1.ph) return SPX_OK;  // no bounded primal pass yet
+    PboxPhase r;
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(&r, x->pbox.p1.ph, sizeof r, hipMemcpyDeviceToHost));
+    out[0] = r.passes;
+    out[1] = r.pivots;
+    out[2] = r.ninf0;
+    out[3] = r.ninf;
     return SPX_OK;
 }
 

@@ -95,10 +95,25 @@ struct DualState {
 //    from outside, the entry check passed (x_b recomputed from the placements
 //    and within its bounds) and rbuf holds the pending pivot's row.
 //  - the counters live in args.rec (all 0 while it is not allocated).
+//  - phase 1 (spx_set_primal_phase1): p1.ph != nullptr  <=>
+//    pbox_setup ran (w, yp, vparts and the device phase word are allocated with
+//    the rest, whatever `phase1` says).  ninf / y_stale: the device phase word as
+//    of the last readback by this loop; passes are the four-step ones while
+//    phase1 && (ninf > 0 || y_stale).  y_dirty: a four-step pass was enqueued
+//    since y was last known current, so a readback of y (flush), a switch of the
+//    algorithm or of phase1 first runs the refresh (pbox_fresh_y).  With phase1
+//    off and y_dirty clear the loop is the three-launch loop and never reads p1.
 struct PboxState {
     spx::PboxArgs args{};
     spx::PboxCfg cfg{};
     bool checked = false;
+    spx::Pbox1Args p1{};
+    bool phase1 = false;
+    bool y_dirty = false;
+    int32_t ninf = 0;
+    int32_t y_stale = 0;
+    std::vector<hipEvent_t> ev_vtb;  // timing: pairs around k_pbox_vtb + k_pbox_vtb_sum (spx_pbox_vtb_times)
+    size_t n_vtb = 0;
 };
 
 struct spx_ctx {
@@ -279,5 +294,8 @@ int pbox_setup(spx_ctx* x);  // buffers and launch geometry, on first use
 int iterate_pbox(spx_ctx* x, int64_t k);
 int pbox_on_reset(spx_ctx* x);     // do_reset: counters cleared, nothing checked
 void pbox_on_change(spx_ctx* x);   // the basis, the bounds, b, c or the algorithm were set: nothing checked
+void pbox_on_create(spx_ctx* x);   // phase 1 as opts.flags asks for
+int pbox_on_reinvert(spx_ctx* x);  // B^-1, x_b and y rebuilt: y current, the rows classified again
+int pbox_fresh_y(spx_ctx* x);      // before anything outside the loop reads y: y = c_B B^-1 if phase 1 left it stale
 
 }  // namespace spx_host

@@ -62,6 +62,7 @@ enum : int32_t {
     ST_RUNNING = 0,
     ST_OPTIMAL = 1,
     ST_UNBOUNDED = 2,
+    ST_BREAKDOWN = 3,   // bounded primal phase 1 (spx_pbox.h): no blocking row and no bound on the entering column
     ST_INFEASIBLE = 4,  // dual loop (spx_dual.h): a row with x_b < 0 and no ratio-test candidate
     ST_WINDOW_FULL = 16,
     ST_HANDOFF_TIMEOUT = 17,

@@ -76,15 +76,44 @@ struct PboxArgs {
     double piv_tol;
 };
 
+// Phase 1: the device phase word and the phase-1 counters.
+// Written by one-workgroup kernels only (k_pbox_step1, k_pbox_classify) and by
+// stream-ordered host memsets, so every kernel of a pass reads one value.
+struct alignas(16) PboxPhase {
+    int32_t ninf;     // rows out of their bounds as of the last classification: > 0 makes the next pass a phase-1 pass
+    int32_t y_stale;  // 1: a phase-1 pivot was made since y = c_B B^-1 was last current
+    int64_t passes;   // phase-1 passes since create / spx_reset, flip passes included
+    int64_t pivots;   // phase-1 pivots
+    int64_t ninf0;    // ninf at the last entry check
+    int64_t pad;
+};
+
+struct Pbox1Args {  // what the phase-1 capable kernels take beside PboxArgs
+    PboxPhase* ph;
+    double* w;           // L: +1 below, -1 above, 0 feasible (rows m..L-1: 0)
+    double* yp;          // L: w B^-1, the phase-1 pricing vector
+    double* vparts;      // vtb_blocks x L: k_pbox_vtb's per-row-block partial vectors
+    int32_t vtb_blocks;  // row blocks of PBOX_VTB_ROWS rows
+    int32_t force;       // 1: a readback's refresh of y (ignores status and limit, rebuilds y iff y_stale)
+    double feas_tol;
+};
+
 struct PboxCfg {
     int price_grid = 0;
     bool price_lds = false;   // y staged in LDS (8 L bytes) or read from global memory
     int update_grid = 0;
     bool update_lds = false;  // the pending row and A_p staged in LDS (16 L bytes)
+    // k_pbox_vtb: a function of m alone (the result must not depend on tuning options)
+    int vtb_grid_x = 0;       // column slabs of PBOX_VTB_WAVES 1 KiB chunks
+    int vtb_blocks = 0;       // row blocks
+    int vsum_grid = 0;
 };
 
 constexpr int PBOX_BLOCK = 512;  // threads per workgroup of k_pbox_price / k_pbox_update
 constexpr int PBOX_WAVES = PBOX_BLOCK / 64;
+constexpr int PBOX_VTB_BLOCK = 256;  // k_pbox_vtb / k_pbox_vtb_sum
+constexpr int PBOX_VTB_WAVES = PBOX_VTB_BLOCK / 64;
+constexpr int PBOX_VTB_ROWS = 64;    // rows of S per k_pbox_vtb workgroup
 
 // geometry: price_grid_opt > 0 fixes the pricing grid, global_y keeps y in global memory
 hipError_t pbox_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, PboxCfg* cfg);
@@ -96,5 +125,39 @@ hipError_t launch_pbox_step(const Params& P, const PboxArgs& D, hipStream_t s);
 // rbuf = row st->q of S where a pivot is pending (entry from another loop, whose
 // last launch does not leave it staged)
 hipError_t launch_pbox_stage(const Params& P, hipStream_t s);
+
+// Phase 1.  A pass enqueued while the host last saw ninf > 0 or
+// y stale is four steps, again ordered by kernel boundaries only:
+//   k_pbox_vtb + k_pbox_vtb_sum   ninf > 0: yp = w B^-1; ninf == 0 and y stale:
+//                  y = c_B B^-1; else nothing.  B^-1 = S with the pending pivot:
+//                  v B^-1 = v' S, v' = v but v'_q = v_q + sum_i v_i E_i (one
+//                  m-dot, computed by the workgroups whose row block holds q).
+//                  Workgroup (x, y) owns PBOX_VTB_WAVES 1 KiB column chunks of
+//                  row block y; it lists the block's rows with v'_i != 0 (one
+//                  ballot) and streams those only, lanes own columns (dbl2).
+//                  k_pbox_vtb_sum adds the row blocks' partial vectors in a
+//                  fixed order (four ascending quarters, then lane-wise):
+//                  no floating-point atomics.
+//   k_pbox_price1 / k_pbox_update1 / k_pbox_step1   k_pbox_price / _update /
+//                  _step with the phase read from PboxPhase::ninf.  Phase 1:
+//                  d_j = yp.A_j (no c_j); no candidate: ST_INFEASIBLE; a below
+//                  row blocks only for ahat_i < -piv_tol at x_b / ahat_i (side
+//                  0), an above row only for ahat_i > piv_tol at (x_b - u_k) /
+//                  ahat_i (side 1); no row and u_p = +inf: ST_BREAKDOWN; y is
+//                  not updated by a pivot (y_stale = 1); the commit classifies
+//                  all rows again (w, ninf) and bumps the counters.  Phase 2
+//                  (ninf == 0): the arithmetic of the three plain kernels, so a
+//                  batch enqueued in phase 1 runs on through the switch; the
+//                  first such pass's k_pbox_step1 clears y_stale.
+// k_pbox_classify (one workgroup): w and ninf from x_b and ub_B, at entry (also
+// ninf0) and after a reinversion.
+hipError_t launch_pbox_vtb(const Params& P, const Pbox1Args& X, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
+                           hipEvent_t e1);
+hipError_t launch_pbox_price1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxCfg& c, hipStream_t s,
+                              hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_pbox_update1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxCfg& c, hipStream_t s,
+                               hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_pbox_step1(const Params& P, const PboxArgs& D, const Pbox1Args& X, hipStream_t s);
+hipError_t launch_pbox_classify(const Params& P, const PboxArgs& D, const Pbox1Args& X, bool entry, hipStream_t s);
 
 }  // namespace spx

@@ -441,6 +441,601 @@ __global__ __launch_bounds__(1024) void k_pbox_stage(Params P) {
 }
 
 // ---------------------------------------------------------------------------
+// Phase 1 (spx_pbox.h)
+// ---------------------------------------------------------------------------
+namespace {
+
+// a row's class from its value and its basic column's bound: +1 below, -1 above, 0 feasible
+__device__ __forceinline__ double row_class(double x, double ub, double tol) {
+    return x < -tol ? 1.0 : (x > ub + tol ? -1.0 : 0.0);
+}
+
+struct VtbSnap {
+    int64_t it, limit, q;
+    double aq;
+    int32_t status, ninf, stale, y_buf;
+};
+
+// what a vtb launch has to do: 0 nothing, 1 yp = w B^-1, 2 y = c_B B^-1
+__device__ __forceinline__ int vtb_mode(const VtbSnap& s, int force) {
+    if (force) return s.stale ? 2 : 0;
+    if (s.status != ST_RUNNING || s.it >= s.limit) return 0;
+    return s.ninf > 0 ? 1 : (s.stale ? 2 : 0);
+}
+
+}  // namespace
+
+// out = v B^-1 for v = w (phase 1) or c_B (the switch, a readback), as per-row-
+// block partial vectors.  Workgroup (x, y): row block y (PBOX_VTB_ROWS rows of
+// S), wave k the 1 KiB column chunk PBOX_VTB_WAVES x + k; a lane owns one dbl2
+// of the chunk.  The rows with v'_i != 0 are listed in LDS by one ballot
+// (ascending), then streamed U at a time, double-buffered, non-temporal as the
+// update stream; one accumulator pair per lane in list order, so the bits
+// depend on m alone.
+__global__ __launch_bounds__(PBOX_VTB_BLOCK) void k_pbox_vtb(Params P, Pbox1Args X) {
+    constexpr int WAVES = PBOX_VTB_WAVES, U = 8;
+    __shared__ double s_v[PBOX_VTB_ROWS];
+    __shared__ int32_t s_row[PBOX_VTB_ROWS];
+    __shared__ int32_t s_n;
+    __shared__ double s_dot[WAVES];
+    __shared__ VtbSnap Sv;
+    const DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid == 0) {
+        Sv.status = st->status;
+        Sv.it = st->iter;
+        Sv.limit = st->limit;
+        Sv.q = st->q;
+        Sv.aq = st->aq;
+        Sv.ninf = X.ph->ninf;
+        Sv.stale = X.ph->y_stale;
+    }
+    __syncthreads();
+    const int mode = vtb_mode(Sv, X.force);
+    if (mode == 0) return;
+    const double* v = mode == 1 ? X.w : P.c_B;
+    const int64_t m = P.m, L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const int64_t it = Sv.it, q = Sv.q;
+    const bool pend = it > 0 && q >= 0;
+    const int64_t r0 = (int64_t)blockIdx.y * PBOX_VTB_ROWS;
+    double vq_add = 0.0;
+    if (pend && q >= r0 && q < r0 + PBOX_VTB_ROWS) {  // (workgroup-uniform) v'_q - v_q = sum_i v_i E_i
+        // E_i = -alpha_i / alpha_q (i != q), E_q = 1 / alpha_q - 1: one division, after the sum
+        const double* a_prev = (it & 1) ? P.alpha1 : P.alpha0;
+        const double aq = Sv.aq;
+        double s = 0.0;
+#pragma unroll 4
+        for (int64_t i = tid; i < m; i += PBOX_VTB_BLOCK) s = fma(v[i], i != q ? a_prev[i] : 0.0, s);
+        s = wave_sum(s);
+        if (lane == 0) s_dot[wave] = s;
+        __syncthreads();
+        double t = s_dot[0];
+#pragma unroll
+        for (int k = 1; k < WAVES; ++k) t += s_dot[k];
+        vq_add = fma(v[q], 1.0 / aq - 1.0, -(t / aq));
+    }
+    if (wave == 0) {
+        const int64_t i = r0 + lane;
+        double vi = i < m ? v[i] : 0.0;
+        if (pend && i == q) vi += vq_add;
+        const unsigned long long mask = __ballot(vi != 0.0);
+        const int pos = __popcll(mask & ((1ull << lane) - 1ull));
+        if (vi != 0.0) {
+            s_v[pos] = vi;
+            s_row[pos] = lane;
+        }
+        if (lane == 0) s_n = __popcll(mask);
+    }
+    __syncthreads();
+    const int c = (int)blockIdx.x * WAVES + wave;
+    if (c >= nch) return;
+    const int n = s_n;
+    const dbl2* base = reinterpret_cast<const dbl2*>(P.B0 + r0 * L) + 64 * c + lane;
+    dbl2 acc{0.0, 0.0};
+    dbl2 cur[U], nxt[U];
+#pragma unroll
+    for (int t = 0; t < U; ++t) cur[t] = t < n ? ld2<SPX_NT_BLOAD>(base + (int64_t)s_row[t] * L2) : dbl2{0.0, 0.0};
+    for (int k0 = 0; k0 < n; k0 += U) {
+#pragma unroll
+        for (int t = 0; t < U; ++t)
+            nxt[t] = k0 + U + t < n ? ld2<SPX_NT_BLOAD>(base + (int64_t)s_row[k0 + U + t] * L2) : dbl2{0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < U; ++t) {
+            if (k0 + t < n) {
+                const double vv = s_v[k0 + t];
+                acc.x = fma(vv, cur[t].x, acc.x);
+                acc.y = fma(vv, cur[t].y, acc.y);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < U; ++t) cur[t] = nxt[t];
+    }
+    reinterpret_cast<dbl2*>(X.vparts + (int64_t)blockIdx.y * L)[64 * c + lane] = acc;  // read after the kernel boundary
+}
+
+// the row blocks' partial vectors added in a fixed order, into yp (phase 1) or
+// y: a workgroup owns one 1 KiB chunk, wave g the g-th quarter of the row blocks
+// (ascending), and lane-wise ((s0 + s1) + s2) + s3 closes it -- a function of m
+__global__ __launch_bounds__(PBOX_VTB_BLOCK) void k_pbox_vtb_sum(Params P, Pbox1Args X) {
+    constexpr int WAVES = PBOX_VTB_WAVES;
+    __shared__ dbl2 s_acc[WAVES][64];
+    __shared__ VtbSnap Sv;
+    const DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid == 0) {
+        Sv.status = st->status;
+        Sv.it = st->iter;
+        Sv.limit = st->limit;
+        Sv.ninf = X.ph->ninf;
+        Sv.stale = X.ph->y_stale;
+        Sv.y_buf = st->y_buf;
+    }
+    __syncthreads();
+    const int mode = vtb_mode(Sv, X.force);
+    if (mode == 0) return;
+    const int64_t L2 = P.L >> 1;
+    const int64_t k = (int64_t)blockIdx.x * 64 + lane;  // (L2 is a multiple of 64: the grid is L2 / 64)
+    const int nb = X.vtb_blocks, per = (nb + WAVES - 1) / WAVES;
+    const int b0 = wave * per, b1 = b0 + per < nb ? b0 + per : nb;
+    const dbl2* parts = reinterpret_cast<const dbl2*>(X.vparts) + k;
+    dbl2 acc{0.0, 0.0};
+#pragma unroll 4
+    for (int b = b0; b < b1; ++b) {
+        const dbl2 t = parts[(int64_t)b * L2];
+        acc.x += t.x;
+        acc.y += t.y;
+    }
+    s_acc[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0) {
+        dbl2 r = s_acc[0][lane];
+#pragma unroll
+        for (int g = 1; g < WAVES; ++g) {
+            r.x += s_acc[g][lane].x;
+            r.y += s_acc[g][lane].y;
+        }
+        double* out = mode == 1 ? X.yp : (Sv.y_buf ? P.y1 : P.y0);
+        reinterpret_cast<dbl2*>(out)[k] = r;
+    }
+}
+
+// k_pbox_price with the phase read from the device: phase 1 prices with yp and no c_j
+template <bool LDS>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_price1(Params P, PboxArgs D, Pbox1Args X) {
+    constexpr int WAVES = PBOX_WAVES, U = 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    const DevState* st = P.st;
+    const int32_t status = st->status;
+    const int32_t cnt = st->nb_count;
+    const int32_t y_buf = st->y_buf;
+    const int64_t iter = st->iter, limit = st->limit;
+    const bool ph1 = X.ph->ninf > 0;
+    if (status != ST_RUNNING || iter >= limit) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const dbl2* y_g = reinterpret_cast<const dbl2*>(ph1 ? X.yp : (y_buf ? P.y1 : P.y0));
+    if constexpr (LDS) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) d[k] = y_g[k];
+        __syncthreads();
+    }
+    const dbl2* yv = LDS ? reinterpret_cast<const dbl2*>(dsm) : y_g;
+    const double* ys = reinterpret_cast<const double*>(yv);
+
+    double bkey = INFINITY, bd = 0.0;
+    int64_t bidx = INT64_MAX;
+    const int nwv = (int)gridDim.x * WAVES;
+    for (int s = (int)blockIdx.x * WAVES + wave; s < cnt; s += nwv) {
+        const int64_t j = P.nb_list[s];
+        const int up = D.at_upper[j];
+        const double cj = ph1 ? 0.0 : P.c[j];  // (x - 0.0 = x: exact)
+        double d;
+        if (P.slack_unit && j >= P.ns) {
+            d = ys[j - P.ns] - cj;
+        } else {
+            const dbl2* col = reinterpret_cast<const dbl2*>(P.A + j * L) + lane;
+            dbl2 cur[U], nxt[U];
+#pragma unroll
+            for (int t = 0; t < U; ++t) cur[t] = t < nch ? ld2<SPX_NT_A>(col + 64 * t) : dbl2{0.0, 0.0};
+            double d0 = 0.0, d1 = 0.0;
+            for (int c0 = 0; c0 < nch; c0 += U) {
+#pragma unroll
+                for (int t = 0; t < U; ++t)
+                    nxt[t] = c0 + U + t < nch ? ld2<SPX_NT_A>(col + 64 * (c0 + U + t)) : dbl2{0.0, 0.0};
+#pragma unroll
+                for (int t = 0; t < U; ++t) {
+                    if (c0 + t < nch) {
+                        const dbl2 w = yv[64 * (c0 + t) + lane];
+                        d0 = fma(cur[t].x, w.x, d0);
+                        d1 = fma(cur[t].y, w.y, d1);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < U; ++t) cur[t] = nxt[t];
+            }
+            d = wave_sum(d0 + d1) - cj;
+        }
+        const double key = up ? -d : d;
+        if (key < -P.eps && argmin_better(key, j, bkey, bidx)) {
+            bkey = key;
+            bidx = j;
+            bd = d;
+        }
+    }
+    if (lane == 0) s_red[wave] = PboxPartial{bkey, bidx, bd, 0.0};
+    __syncthreads();
+    if (tid == 0) D.parts[blockIdx.x] = merge_price<WAVES>(s_red);
+}
+
+// k_pbox_update with the phase read from the device: in phase 1 no candidate is
+// ST_INFEASIBLE and row i's ratio entry depends on its class w[i], requested
+// ahead of the stream beside x_b[i] and ub_B[i]
+template <bool XL>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_update1(Params P, PboxArgs D, Pbox1Args X) {
+    constexpr int WAVES = PBOX_WAVES, U = 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    __shared__ ArgMinEntry s_rat[WAVES];
+    __shared__ PboxSnap Sv;
+    __shared__ int32_t s_ninf;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid == 0) {  // one reader per workgroup (k_pbox_update)
+        Sv.status = st->status;
+        Sv.it = st->iter;
+        Sv.limit = st->limit;
+        Sv.qprev = st->q;
+        Sv.aqprev = st->aq;
+        s_ninf = X.ph->ninf;
+    }
+    __syncthreads();
+    const int64_t it = Sv.it, qp = Sv.qprev;
+    const double aqp = Sv.aqprev;
+    const bool ph1 = s_ninf > 0;
+    if (Sv.status != ST_RUNNING || it >= Sv.limit) return;
+
+    double wk = INFINITY, wd = 0.0;
+    int64_t wj = INT64_MAX;
+    for (int g = tid; g < D.price_grid; g += PBOX_BLOCK) {
+        const PboxPartial v = D.parts[g];
+        if (argmin_better(v.key, v.idx, wk, wj)) {
+            wk = v.key;
+            wj = v.idx;
+            wd = v.d;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double k2 = __shfl_xor(wk, off, 64);
+        const int64_t j2 = __shfl_xor(wj, off, 64);
+        const double d2 = __shfl_xor(wd, off, 64);
+        const bool t = argmin_better(k2, j2, wk, wj);
+        wk = t ? k2 : wk;
+        wj = t ? j2 : wj;
+        wd = t ? d2 : wd;
+    }
+    if (lane == 0) s_red[wave] = PboxPartial{wk, wj, wd, 0.0};
+    __syncthreads();
+    const PboxPartial t = merge_price<WAVES>(s_red);
+    if (t.idx == INT64_MAX) {  // phase 1: the violation cannot decrease; phase 2: optimum
+        if (blockIdx.x == 0 && tid == 0) st->status = ph1 ? ST_INFEASIBLE : ST_OPTIMAL;
+        return;
+    }
+    const int64_t p = t.idx;
+    if (blockIdx.x == 0 && tid == 0) {
+        D.rec->p = p;
+        D.rec->d_p = t.d;
+        D.rec->fresh = 1;
+    }
+
+    const int64_t m = P.m, L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const bool pend = it > 0 && qp >= 0;
+    const dbl2* rp = reinterpret_cast<const dbl2*>(pend ? P.rbuf : P.zeros);
+    const dbl2* ap = reinterpret_cast<const dbl2*>(P.A + p * L);
+    if constexpr (XL) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) {
+            d[k] = rp[k];
+            d[L2 + k] = ap[k];
+        }
+        __syncthreads();
+    }
+    const dbl2* xr = XL ? reinterpret_cast<const dbl2*>(dsm) : rp;
+    const dbl2* xa = XL ? reinterpret_cast<const dbl2*>(dsm) + L2 : ap;
+
+    const int64_t i = (int64_t)blockIdx.x * WAVES + wave;
+    double rt = INFINITY;
+    int64_t ri = INT64_MAX;
+    if (i < m) {
+        const double sg = D.at_upper[p] ? -1.0 : 1.0;
+        const double xi = P.x_b[i], ubi = D.ub_B[i];
+        const double wi = ph1 ? X.w[i] : 0.0;
+        const double* a_prev = (it & 1) ? P.alpha1 : P.alpha0;
+        double* a_new = (it & 1) ? P.alpha0 : P.alpha1;
+        const double ei = pend ? eta_entry(a_prev[i], i, qp, aqp) : 0.0;
+        dbl2* row = reinterpret_cast<dbl2*>(P.B0 + i * L) + lane;
+        dbl2 cur[U], nxt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = u < nch ? ld2<SPX_NT_BLOAD>(row + 64 * u) : dbl2{0.0, 0.0};
+        double acc0 = 0.0, acc1 = 0.0;
+        for (int c0 = 0; c0 < nch; c0 += U) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                nxt[u] = c0 + U + u < nch ? ld2<SPX_NT_BLOAD>(row + 64 * (c0 + U + u)) : dbl2{0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (c0 + u < nch) {
+                    const int k = 64 * (c0 + u) + lane;
+                    const dbl2 r = xr[k], a = xa[k];
+                    dbl2 nv;
+                    nv.x = fma(ei, r.x, cur[u].x);
+                    nv.y = fma(ei, r.y, cur[u].y);
+                    st2<SPX_NT_BSTORE>(nv, row + 64 * (c0 + u));
+                    acc0 = fma(nv.x, a.x, acc0);
+                    acc1 = fma(nv.y, a.y, acc1);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        }
+        const double alpha = wave_sum(acc0 + acc1);
+        if (lane == 0) a_new[i] = alpha;
+        const double ah = sg * alpha;
+        if (wi == 0.0) {  // a feasible row: phase 2's entry
+            if (ah > D.piv_tol) {
+                rt = (xi > 0.0 ? xi : 0.0) / ah;
+                ri = 2 * i;
+            } else if (ah < -D.piv_tol && ubi < INFINITY) {
+                const double gap = ubi - xi;
+                rt = (gap > 0.0 ? gap : 0.0) / (-ah);
+                ri = 2 * i + 1;
+            }
+        } else if (wi > 0.0) {  // below: blocks where it rises to 0
+            if (ah < -D.piv_tol) {
+                rt = xi / ah;
+                ri = 2 * i;
+            }
+        } else {  // above: blocks where it falls to its bound
+            if (ah > D.piv_tol) {
+                rt = (xi - ubi) / ah;
+                ri = 2 * i + 1;
+            }
+        }
+    }
+    if (lane == 0) s_rat[wave] = ArgMinEntry{rt, ri};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry b = s_rat[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            const ArgMinEntry v = s_rat[w];
+            const bool tk = argmin_better(v.val, v.idx, b.val, b.idx);
+            b.val = tk ? v.val : b.val;
+            b.idx = tk ? v.idx : b.idx;
+        }
+        D.rparts[blockIdx.x] = b;
+    }
+}
+
+// k_pbox_step with the phase read from the device.  A phase-1 commit leaves y
+// alone (y_stale = 1 after a pivot), classifies every row from the x_b it has
+// just written (w, ninf) and bumps the phase-1 counters; no row and no bound is
+// ST_BREAKDOWN.  The first phase-2 pass after the switch clears y_stale:
+// k_pbox_vtb rebuilt y ahead of this pass's pricing.
+__global__ __launch_bounds__(1024) void k_pbox_step1(Params P, PboxArgs D, Pbox1Args X) {
+    constexpr int BLOCK = 1024, WAVES = BLOCK / 64, CH = 4;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t m = P.m, L = P.L;
+    __shared__ PboxSnap S;
+    __shared__ ArgMinEntry s_red[WAVES];
+    __shared__ ArgMinEntry s_win;
+    __shared__ double s_up;
+    __shared__ int32_t s_at;
+    __shared__ int32_t s_ninf, s_stale, s_cnt;
+    if (tid == 0) {
+        S.it = st->iter;
+        S.limit = st->limit;
+        S.status = st->status;
+        S.y_buf = st->y_buf;
+        S.cnt = st->nb_count;
+        S.fresh = D.rec->fresh;
+        S.p = D.rec->p;
+        S.d_p = D.rec->d_p;
+        s_ninf = X.ph->ninf;
+        s_stale = X.ph->y_stale;
+        s_cnt = 0;
+    }
+    __syncthreads();
+    const int64_t it = S.it;
+    if (S.status != ST_RUNNING || it >= S.limit || !S.fresh) return;
+    const bool ph1 = s_ninf > 0;
+    const double ftol = X.feas_tol;
+
+    double bv = INFINITY;
+    int64_t bi = INT64_MAX;
+    for (int g = tid; g < D.update_grid; g += BLOCK) {
+        const ArgMinEntry v = D.rparts[g];
+        if (argmin_better(v.val, v.idx, bv, bi)) {
+            bv = v.val;
+            bi = v.idx;
+        }
+    }
+    wave_argmin(bv, bi);
+    if (lane == 0) s_red[wave] = ArgMinEntry{bv, bi};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry t = s_red[0];
+        for (int w = 1; w < WAVES; ++w)
+            if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
+        s_win = t;
+        s_up = D.ub[S.p];
+        s_at = D.at_upper[S.p];
+    }
+    __syncthreads();
+    const double tq = s_win.val;
+    const bool none = s_win.idx == INT64_MAX;
+    const int64_t q = none ? 0 : (s_win.idx >> 1);
+    const int side = none ? 0 : (int)(s_win.idx & 1);
+    const int64_t p = S.p;
+    const double u_p = s_up;
+    const int up_p = s_at;
+    const double sg = up_p ? -1.0 : 1.0;
+    const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
+    double* a_cur = (it & 1) ? P.alpha1 : P.alpha0;
+    const bool flip = u_p < INFINITY && (none || u_p <= tq);
+
+    if (flip || none) {
+        if (flip) {
+            const double dx = up_p ? -u_p : u_p;
+            const double* Ap = P.A + p * L;
+            int bad = 0;
+            for (int64_t i = tid; i < m; i += BLOCK) {
+                const double xn = fma(-u_p, sg * al[i], P.x_b[i]);
+                P.x_b[i] = xn;
+                D.b_eff[i] = fma(-dx, Ap[i], D.b_eff[i]);
+                if (ph1) {
+                    const double wv = row_class(xn, D.ub_B[i], ftol);
+                    X.w[i] = wv;
+                    bad += wv != 0.0;
+                }
+            }
+            if (ph1 && bad) atomicAdd(&s_cnt, bad);  // (an integer count: order-free)
+        }
+        for (int64_t i = tid; i < L; i += BLOCK) a_cur[i] = (i == 0) ? 1.0 : 0.0;
+        __syncthreads();
+        if (tid == 0) {
+            if (flip) {
+                D.at_upper[p] = up_p ? 0 : 1;
+                D.rec->flips += 1;
+                if (ph1) {
+                    X.ph->ninf = s_cnt;
+                    X.ph->passes += 1;
+                }
+            } else {
+                st->status = ph1 ? ST_BREAKDOWN : ST_UNBOUNDED;
+            }
+            if (!ph1 && s_stale) X.ph->y_stale = 0;
+            st->q = 0;
+            st->aq = 1.0;
+            st->p = p;
+            st->min_e = S.d_p;
+            D.rec->fresh = 0;
+        }
+        return;
+    }
+
+    double* y = S.y_buf ? P.y1 : P.y0;
+    const double aq = al[q];
+    const double theta = tq, sy = -(S.d_p / aq);
+    const double x_off = up_p ? u_p : 0.0;
+    const bool book = tid == BLOCK - 64;
+    int64_t leave = -1;
+    double c_p = 0.0;
+    int kp = -1, last = -1;
+    if (book) {
+        leave = P.b_ixs[q];
+        c_p = P.c[p];
+        kp = P.nb_pos[p];
+        last = P.nb_list[S.cnt - 1];
+    }
+    const double* Sq = P.B0 + q * L;
+    int bad = 0;
+    for (int64_t i0 = tid; i0 < L; i0 += (int64_t)CH * BLOCK) {
+        double xv[CH], av[CH], yv[CH], rv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            xv[u] = i < m ? P.x_b[i] : 0.0;
+            av[u] = i < m ? al[i] : 0.0;
+            yv[u] = i < L ? y[i] : 0.0;
+            rv[u] = i < L ? Sq[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            if (i < m) {
+                const double xn = (i == q) ? x_off + sg * theta : fma(-theta, sg * av[u], xv[u]);
+                P.x_b[i] = xn;
+                if (ph1) {  // (row q's bound is the entering column's: the bookkeeping lane stores it below)
+                    const double wv = row_class(xn, i == q ? u_p : D.ub_B[i], ftol);
+                    X.w[i] = wv;
+                    bad += wv != 0.0;
+                }
+            }
+            if (i < L) {
+                if (!ph1) y[i] = fma(sy, rv[u], yv[u]);
+                P.rbuf[i] = rv[u];
+            }
+        }
+    }
+    if (ph1 && bad) atomicAdd(&s_cnt, bad);
+    __syncthreads();
+    if (book) {
+        P.c_B[q] = c_p;
+        P.b_ixs[q] = p;
+        D.ub_B[q] = u_p;
+        D.at_upper[p] = 0;
+        D.at_upper[leave] = (int8_t)side;
+        int cnt = S.cnt;
+        P.nb_list[kp] = last;
+        P.nb_pos[last] = kp;
+        P.nb_pos[p] = -1;
+        --cnt;
+        P.nb_list[cnt] = (int32_t)leave;
+        P.nb_pos[leave] = cnt;
+        ++cnt;
+        st->nb_count = cnt;
+        st->aq = aq;
+        st->s_y = sy;
+        st->y_applied = it + 1;
+        st->xb_applied = it + 1;
+        st->p = p;
+        st->q = q;
+        st->min_e = S.d_p;
+        st->iter = it + 1;
+        record_pivot(P, it, p, q);
+        D.rec->fresh = 0;
+        if (side) D.rec->to_upper += 1;
+        if (ph1) {
+            X.ph->ninf = s_cnt;
+            X.ph->passes += 1;
+            X.ph->pivots += 1;
+            X.ph->y_stale = 1;
+        } else if (s_stale) {
+            X.ph->y_stale = 0;
+        }
+    }
+}
+
+// w and ninf from x_b and ub_B (one workgroup): the entry check (ninf0 too) and after a reinversion
+__global__ __launch_bounds__(1024) void k_pbox_classify(Params P, PboxArgs D, Pbox1Args X, int entry) {
+    __shared__ int32_t s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    int bad = 0;
+    for (int64_t i = threadIdx.x; i < P.L; i += 1024) {
+        const double wv = i < P.m ? row_class(P.x_b[i], D.ub_B[i], X.feas_tol) : 0.0;
+        X.w[i] = wv;
+        bad += wv != 0.0;
+    }
+    if (bad) atomicAdd(&s_cnt, bad);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        X.ph->ninf = s_cnt;
+        if (entry) X.ph->ninf0 = s_cnt;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------
 namespace {
@@ -482,7 +1077,18 @@ hipError_t pbox_prepare(const Params& P, int cus, int price_grid_opt, bool globa
     if (cfg->update_lds) {
         e = set_lds(k_pbox_update<true>, vec2);
         if (e != hipSuccess) return e;
+        e = set_lds(k_pbox_update1<true>, vec2);
+        if (e != hipSuccess) return e;
     }
+    if (cfg->price_lds) {  // (the phase-1 capable pricing runs on k_pbox_price's grid)
+        e = set_lds(k_pbox_price1<true>, vec1);
+        if (e != hipSuccess) return e;
+    }
+    // k_pbox_vtb: a wave per 1 KiB column chunk and row block -- from m alone
+    const int nch = (int)(P.L >> 7);
+    cfg->vtb_grid_x = (nch + PBOX_VTB_WAVES - 1) / PBOX_VTB_WAVES;
+    cfg->vtb_blocks = (int)((P.m + PBOX_VTB_ROWS - 1) / PBOX_VTB_ROWS);
+    cfg->vsum_grid = nch;  // k_pbox_vtb_sum: a workgroup per chunk
     if (per_cu < 1) per_cu = 1;
     const int64_t cols = P.n - P.m;  // the non-basic count never changes
     const int64_t want = (cols + PBOX_WAVES - 1) / PBOX_WAVES;
@@ -508,6 +1114,55 @@ hipError_t launch_pbox_update(const Params& P, const PboxArgs& D, const PboxCfg&
 
 hipError_t launch_pbox_step(const Params& P, const PboxArgs& D, hipStream_t s) {
     hipLaunchKernelGGL(k_pbox_step, dim3(1), dim3(1024), 0, s, P, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_vtb(const Params& P, const Pbox1Args& X, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
+                           hipEvent_t e1) {
+    if (e0) {
+        const hipError_t e = hipEventRecord(e0, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_pbox_vtb, dim3(c.vtb_grid_x, c.vtb_blocks), dim3(PBOX_VTB_BLOCK), 0, s, P, X);
+    hipLaunchKernelGGL(k_pbox_vtb_sum, dim3(c.vsum_grid), dim3(PBOX_VTB_BLOCK), 0, s, P, X);
+    if (e1) {
+        const hipError_t e = hipEventRecord(e1, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+namespace {
+
+template <typename K>
+hipError_t launch_timed1(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const Params& P,
+                         const PboxArgs& D, const Pbox1Args& X) {
+    if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), (uint32_t)lds, s, e0, e1, 0, P, D, X);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), lds, s, P, D, X);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_pbox_price1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxCfg& c, hipStream_t s,
+                              hipEvent_t e0, hipEvent_t e1) {
+    if (c.price_lds) return launch_timed1(k_pbox_price1<true>, c.price_grid, (size_t)P.L * 8, s, e0, e1, P, D, X);
+    return launch_timed1(k_pbox_price1<false>, c.price_grid, 0, s, e0, e1, P, D, X);
+}
+
+hipError_t launch_pbox_update1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxCfg& c, hipStream_t s,
+                               hipEvent_t e0, hipEvent_t e1) {
+    if (c.update_lds) return launch_timed1(k_pbox_update1<true>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D, X);
+    return launch_timed1(k_pbox_update1<false>, c.update_grid, 0, s, e0, e1, P, D, X);
+}
+
+hipError_t launch_pbox_step1(const Params& P, const PboxArgs& D, const Pbox1Args& X, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_step1, dim3(1), dim3(1024), 0, s, P, D, X);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_classify(const Params& P, const PboxArgs& D, const Pbox1Args& X, bool entry, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_classify, dim3(1), dim3(1024), 0, s, P, D, X, entry ? 1 : 0);
     return hipGetLastError();
 }
 

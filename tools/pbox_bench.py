@@ -23,8 +23,29 @@ from the returned basis and placements (tests/dual_box_ref.py certificate).
 row (x_j + s = u_j; a bounded slack u_k becomes the row a_k.x >= b_k - u_k,
 negated) on the primal loop with its default eta window.
 
+--phase1 measures the loop's phase 1 (SPX_FLAG_PRIMAL_PHASE1)
+instead, again one child per side, the sides alternating:
+  pbox          as above (flag off): the phase-2 pass rate the others compare with
+  pbox_flag     the same LP with the flag on: a feasible entry, so the same three
+                launches per pass
+  p1_dense      tests/primal_phase1_ref.py boxed_general(m, n, seed) from the slack
+                basis: the start of phase 1, about two thirds of the rows infeasible
+  p1_sparse     boxed_primal's LP with every --sparse-every-th row turned into a
+                violated >= row: few infeasible rows, phase 1 near its end; once
+                they are gone the same context's phase-2 passes are timed after
+                --warm more pivots (pivots and passes per second, flip passes, and
+                under SPX_FLAG_TIMING the kernel times and the count of k_pbox_vtb
+                launches, 0 once the loop is back on the three-launch pass)
+  pbox_again, pbox_flag_again
+Phase-1 records carry the rows out of bounds before and after the timed passes,
+passes and pivots per second, the mean times of k_pbox_vtb (+ its reduction),
+the pricing and the update kernel over the phase-1 passes, and k_pbox_vtb's
+algorithmic bandwidth 8 L x (rows with w_i != 0, the mean of before and after)
+/ time beside the update kernel's 16 m L / time, both against 8 TB/s.
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
+    python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
 """
 import argparse
 import json
@@ -104,6 +125,156 @@ def run_pbox(a):
                                               timing=timing), a.k, a.warm, flips=True)
 
 
+def run_pbox_flag(a):
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = primal_box_ref.boxed_primal(a.m, a.n, a.seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    res = measure(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                                             primal_phase1=True, timing=timing), a.k, a.warm, flips=True)
+    return res
+
+
+def measure_phase1(make_ctx, k, warm, chunk, want_phase2, warm2=0):
+    """Phase-1 passes in chunks of `chunk` pivots, at most k pivots: only chunks
+    that end with rows still out of bounds count (all their passes are phase-1
+    passes).  want_phase2: then on to ninf == 0 and k timed phase-2 pivots."""
+    res = {}
+    with make_ctx(False) as ctx:
+        ctx.iterate(warm)
+        ph0 = ctx.primal_phase1()
+        res["ninf_entry"], res["ninf_before"] = ph0[2], ph0[3]
+        dt = 0.0
+        piv = passes = st = 0
+        ph = ph0
+        while piv < k and ph[3] > 0:
+            _, p0 = ctx.iterate(0)
+            t0 = time.perf_counter()
+            st, p1 = ctx.iterate(chunk)
+            d = time.perf_counter() - t0
+            nph = ctx.primal_phase1()
+            if nph[3] == 0 or int(st) != 0:
+                ph = nph
+                break
+            dt += d
+            piv += p1 - p0
+            passes += nph[0] - ph[0]
+            ph = nph
+        res.update({"ninf_after": ph[3], "pivots": piv, "passes": passes, "status": int(st),
+                    "it_per_s": round(piv / dt, 1) if dt else None, "passes_per_s": round(passes / dt, 1) if dt else None})
+        if want_phase2:
+            guard = 0
+            while ctx.primal_phase1()[3] > 0 and guard < 400:
+                st, _ = ctx.iterate(chunk)
+                guard += 1
+                if int(st) != 0:
+                    break
+            ph = ctx.primal_phase1()
+            rec = {"ninf": ph[3], "phase1_passes_total": ph[0], "phase1_pivots_total": ph[1]}
+            if ph[3] == 0 and int(st) == 0:
+                ctx.iterate(warm2)
+                _, p0 = ctx.iterate(0)
+                f0 = ctx.primal_flips()
+                t0 = time.perf_counter()
+                st, p1 = ctx.iterate(k)
+                d = time.perf_counter() - t0
+                f1 = ctx.primal_flips()
+                rec.update({"warm": warm2, "pivots": p1 - p0, "status": int(st), "it_per_s": round((p1 - p0) / d, 1),
+                            "flip_passes": f1[0] - f0[0], "to_upper": f1[1] - f0[1],
+                            "passes_per_s": round((p1 - p0 + f1[0] - f0[0]) / d, 1),
+                            "phase1_passes_in_block": ctx.primal_phase1()[0] - ph[0]})
+            res["phase2_same_context"] = rec
+    with make_ctx(True) as ctx:
+        ctx.iterate(warm)
+        ctx.kernel_times()
+        ctx.vtb_times()
+        info = ctx.info()
+        ph = ctx.primal_phase1()
+        n0 = ph[3]
+        tp = tu = tv = 0.0
+        npass = nv = piv = st = 0
+        while piv < k and ph[3] > 0:
+            st, _ = ctx.iterate(chunk)
+            nph = ctx.primal_phase1()
+            kt = ctx.kernel_times()
+            vt = ctx.vtb_times()
+            if nph[3] == 0 or int(st) != 0:
+                break
+            tp += kt["price_ms"]
+            tu += kt["update_ms"]
+            tv += vt[0]
+            npass += kt["price_launches"]
+            nv += vt[1]
+            piv += chunk
+            ph = nph
+        if npass:
+            L, m = info["ld"], info["m"]
+            vtb_us, price_us, update_us = 1e3 * tv / nv, 1e3 * tp / npass, 1e3 * tu / npass
+            rows = 0.5 * (n0 + ph[3])
+            bytes_vtb = 8.0 * L * rows
+            bytes_dense = 8.0 * L * m
+            res.update({"timed_passes": npass, "vtb_us": round(vtb_us, 2), "price_us": round(price_us, 2),
+                        "update_us": round(update_us, 2), "w_rows_mean": rows, "w_density": round(rows / m, 4),
+                        "bytes_vtb": bytes_vtb, "vtb_TBps": round(bytes_vtb / (vtb_us * 1e-6) / 1e12, 3),
+                        "vtb_frac_of_8TBps": round(bytes_vtb / (vtb_us * 1e-6) / PEAK, 3),
+                        "vtb_dense_equiv_TBps": round(bytes_dense / (vtb_us * 1e-6) / 1e12, 3),
+                        "bytes_update": info["bytes_update"],
+                        "update_TBps": round(info["bytes_update"] / (update_us * 1e-6) / 1e12, 3),
+                        "update_frac_of_8TBps": round(info["bytes_update"] / (update_us * 1e-6) / PEAK, 3)})
+        if want_phase2 and "pivots" in res.get("phase2_same_context", {}):
+            # the same phase-2 block under SPX_FLAG_TIMING: which launches its passes are
+            guard = 0
+            while ctx.primal_phase1()[3] > 0 and guard < 400:
+                ctx.iterate(chunk)
+                guard += 1
+            ctx.iterate(warm2)
+            ctx.kernel_times()
+            ctx.vtb_times()
+            ctx.iterate(k)
+            kt = ctx.kernel_times()
+            vt = ctx.vtb_times()
+            res["phase2_same_context"].update(
+                {"timed_passes": kt["price_launches"], "vtb_launches": vt[1],
+                 "price_us": round(1e3 * kt["price_ms"] / max(kt["price_launches"], 1), 2),
+                 "update_us": round(1e3 * kt["update_ms"] / max(kt["update_launches"], 1), 2)})
+    return res
+
+
+def run_p1_dense(a):
+    import numpy as np
+
+    import primal_phase1_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = primal_phase1_ref.boxed_general(a.m, a.n, a.seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    return measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                                                     primal_phase1=True, timing=timing), a.k, a.warm, a.k, False)
+
+
+def run_p1_sparse(a):
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = primal_box_ref.boxed_primal(a.m, a.n, a.seed)
+    ns = a.n - a.m
+    ge = np.arange(a.m) % a.sparse_every == 1  # a.x <= b_i becomes a.x >= 0.1 b_i: violated at the slack basis
+    A[ge, :ns] *= -1.0
+    b[ge] *= -0.1
+    u[ns:][ge] = np.inf
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    return measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                                                     primal_phase1=True, timing=timing), a.k, 1, a.sparse_chunk, True, a.warm)  # (warm 1: the entry check)
+
+
 def bounds_as_rows(A, b, c, u):
     """The bounded LP with every finite bound as a row of its own (b stays >= 0
     where the slack basis is feasible for the bounded LP)."""
@@ -171,7 +342,8 @@ def run_solve(a):
 
 def child(a, role):
     cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--m", str(a.m), "--n", str(a.n),
-           "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--refactor", str(a.refactor)]
+           "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--refactor", str(a.refactor),
+           "--sparse-every", str(a.sparse_every), "--sparse-chunk", str(a.sparse_chunk)]
     if a.rows:
         cmd.append("--rows")
     for shape in a.solve_shape:
@@ -195,15 +367,37 @@ def main():
     ap.add_argument("--solve-shape", type=int, nargs=3, action="append", default=[], metavar=("M", "N", "SEED"))
     ap.add_argument("--rows", action="store_true", help="with --solve: the bounds as rows on the windowed primal loop too")
     ap.add_argument("--refactor", type=int, default=500)
-    ap.add_argument("--role", default=None, choices=[None, "primal", "dual", "pbox", "solve"])
+    ap.add_argument("--phase1", action="store_true", help="the phase-1 sides instead (DESIGN.md 7f)")
+    ap.add_argument("--sparse-every", type=int, default=100, help="p1_sparse: every this many rows one starts violated")
+    ap.add_argument("--sparse-chunk", type=int, default=10, help="p1_sparse: pivots per timed chunk")
+    ap.add_argument("--role", default=None,
+                    choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse"])
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
-        run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve}[a.role]
+        run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
+               "pbox_flag": run_pbox_flag, "p1_dense": run_p1_dense, "p1_sparse": run_p1_sparse}[a.role]
         print(json.dumps(run(a)), flush=True)
         return
     if a.k < 252:
         ap.error("--k: at least 252 timed pivots")
     res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "seed": a.seed}
+    if a.phase1:
+        res.update({"sparse_every": a.sparse_every, "sparse_chunk": a.sparse_chunk})
+        for key, role in (("pbox", "pbox"), ("pbox_flag", "pbox_flag"), ("p1_dense", "p1_dense"),
+                          ("p1_sparse", "p1_sparse"), ("p1_dense_again", "p1_dense"), ("pbox_again", "pbox"),
+                          ("pbox_flag_again", "pbox_flag")):
+            res[key] = child(a, role)
+            sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+            sys.stderr.flush()
+        d, q = res["p1_dense"], res["pbox"]
+        res["p1_dense_over_pbox"] = {"pass_rate": round(d["passes_per_s"] / q["it_per_s"], 3),
+                                     "vtb_over_update_bandwidth": round(d["vtb_TBps"] / d["update_TBps"], 3)}
+        res["flag_over_plain_it_per_s"] = round(res["pbox_flag"]["it_per_s"] / q["it_per_s"], 4)
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
     for key, role in (("primal", "primal"), ("dual", "dual"), ("pbox", "pbox"), ("pbox_again", "pbox"),
                       ("dual_again", "dual"), ("primal_again", "primal")):
         res[key] = child(a, role)
