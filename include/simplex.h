@@ -234,7 +234,8 @@ typedef struct spx_opts {
  * LONG_STEP: the bound-flipping (long-step) ratio test.  The candidates are
  *            walked in that order with slope = |delta_q|: a candidate with u_j =
  *            +inf enters; otherwise slope' = slope - u_j (-ahat_j), ahat_j = s
- *            sigma_j a_j; slope' < 0: it enters, else it is flipped to its other
+ *            sigma_j a_j; slope' <= 0: it enters (at exactly 0 it enters at its
+ *            bound and row q is feasible), else it is flipped to its other
  *            bound, slope = slope' and the walk goes on.  No candidate, or all
  *            flipped and none enters: SPX_STATUS_INFEASIBLE with no flip applied.
  *            With dx_j = +u_j for a flipped column at lower, -u_j at upper, and v

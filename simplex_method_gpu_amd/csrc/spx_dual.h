@@ -48,7 +48,7 @@
 //                  slot's record: key, u_j (-ahat_j), d_j.
 //   k_dual_long    one workgroup: merges the partials and walks the candidates in
 //                  (key, column) order with slope |delta_q|; a bounded candidate
-//                  whose u_j (-ahat_j) leaves the slope >= 0 is flipped, the first
+//                  whose u_j (-ahat_j) leaves the slope > 0 is flipped, the first
 //                  other one enters (p, d_p into DualRec; none: ST_INFEASIBLE,
 //                  nothing flipped).  Leaves the flip list and the counters.
 //   k_dual_flips   returns at once without flips; else v = sum_F dx_j A_j in the

@@ -505,7 +505,8 @@ __global__ __launch_bounds__(DUAL_BLOCK) void k_box_xb(Params P) {
 // winner); every later round is the argmin over the records strictly beyond the
 // last (key, column) taken, so the candidates come in (key, column) order.
 // Thread 0 keeps the slope: a candidate with no bound, or whose u_j (-ahat_j)
-// takes the slope below 0, enters; any other is flipped and the walk goes on.
+// takes the slope to 0 or below, enters (at exactly 0 the flips and that column
+// at its bound make row q feasible); any other is flipped and the walk goes on.
 // A pass without flips is round 0 alone.  The first round that scans loads each
 // thread's LONG_SLOTS keys and columns into registers (nb_count <= LONG_SLOTS x
 // LONG_BLOCK; beyond that, or with DualLongArgs::walk_global, every round reads
@@ -569,7 +570,7 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_dual_long(Params P, DualLongArgs
                 const double u = D.ub[bj];
                 const int up = D.at_upper[bj];
                 const double slope2 = slope - cap;
-                if (!(cap < INFINITY) || slope2 < 0.0) {
+                if (!(cap < INFINITY) || slope2 <= 0.0) {
                     D.rec->p = bj;
                     D.rec->d_p = d;
                     w_state = 1;

@@ -31,7 +31,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 import dual_ref
-from dual_ref import INFEASIBLE, MAX_ITER, OPTIMUM
+from dual_ref import INFEASIBLE, MAX_ITER, OPTIMUM, tied, whole
 from dual_se_ref import _rel_gap, row_norms2
 
 NOT_DUAL_FEASIBLE = "not_dual_feasible"
@@ -76,6 +76,10 @@ class DualBoxResult:
     to_upper: int = 0               # pivots whose row left to its upper bound
     placed: int = 0                 # columns the entry normalisation put at upper
     bad_column: int = -1            # NOT_DUAL_FEASIBLE: the column without an upper bound
+    y: np.ndarray = None            # final duals and inverse
+    Binv: np.ndarray = None
+    ties: dict = field(default_factory=dict)  # passes whose argmin met an exact tie: "row", "ratio"
+    integral: bool = True           # x_b, y and B^-1 held integers only after every pass
 
     def primal(self, u):
         x = np.where(self.at_upper, np.where(np.isfinite(u), u, 0.0), 0.0)
@@ -129,6 +133,8 @@ def dual_simplex_box(A, b, c, u, rule=DANTZIG, basis=None, at_upper=None, eps=1e
     trace = []
     gap_row = gap_ratio = np.inf
     to_upper = 0
+    ties = {"row": 0, "ratio": 0}
+    integral = True
     it = 0
     status = MAX_ITER
     while it < max_iter:
@@ -144,6 +150,7 @@ def dual_simplex_box(A, b, c, u, rule=DANTZIG, basis=None, at_upper=None, eps=1e
         else:
             rkey = np.where(rows, -np.abs(delta), np.inf)
         q = int(np.argmin(rkey))
+        ties["row"] += int(tied(rkey))
         if rows.sum() > 1:
             two = np.partition(rkey, 1)[:2]
             gap_row = min(gap_row, _rel_gap(two[0], two[1]))
@@ -160,6 +167,7 @@ def dual_simplex_box(A, b, c, u, rule=DANTZIG, basis=None, at_upper=None, eps=1e
             break
         key = np.where(cand, np.maximum(sigma * d, 0.0) / np.where(cand, -ahat, 1.0), np.inf)
         p = int(np.argmin(key))  # smallest column index on ties
+        ties["ratio"] += int(tied(key))
         if cand.sum() > 1:
             two = np.partition(key, 1)[:2]
             gap_ratio = min(gap_ratio, _rel_gap(two[0], two[1]))
@@ -180,6 +188,7 @@ def dual_simplex_box(A, b, c, u, rule=DANTZIG, basis=None, at_upper=None, eps=1e
         b_ixs[q] = p
         Binv = Binv - np.outer(alpha / aq, rho)
         Binv[q] = rho / aq
+        integral = integral and whole(x_b, y, Binv)
         if it < trace_cap:
             trace.append((p, q))
         it += 1
@@ -188,7 +197,8 @@ def dual_simplex_box(A, b, c, u, rule=DANTZIG, basis=None, at_upper=None, eps=1e
     for j in np.flatnonzero(up):  # ascending j
         zu += c[j] * u[j]
     return DualBoxResult(status, z + zu, it, b_ixs.copy(), x_b.copy(), up.copy(), trace, float(gap_row),
-                         float(gap_ratio), to_upper, placed)
+                         float(gap_ratio), to_upper, placed, y=y.copy(), Binv=Binv.copy(), ties=ties,
+                         integral=integral)
 
 
 def farkas(A, b, u, b_ixs, at_upper, tol=1e-9):

@@ -6,8 +6,11 @@ certificate and Farkas check are imported unchanged.
 Step 2, with the candidates ahat_j = s sigma_j a_j < -piv_tol ordered by (key_j,
 j), key_j = max(sigma_j d_j, 0) / -ahat_j, and slope = |delta_q|:
   walk the candidates; u_j = +inf: j enters; else slope' = slope - u_j (-ahat_j):
-  slope' < 0: j enters, otherwise j is flipped, slope = slope', go on.  No
+  slope' <= 0: j enters, otherwise j is flipped, slope = slope', go on.  No
   candidate, or all flipped: infeasible, nothing changed, no counter moved.
+  (At slope' = 0 exactly the flips and j at its bound make row q feasible, so j
+  must enter: flipping it and running out of candidates would call a feasible
+  LP infeasible.  The slope therefore stays above 0 through a walk.)
 Then with dx_j = +u_j for a flipped column at lower, -u_j at upper, v = sum (in
 the walk's order) dx_j A_j: x_b -= B^-1 v, the flipped columns change side,
 delta_q is taken again from the new x_b[q] with the same s, and the pivot is the
@@ -19,6 +22,12 @@ candidates of every walk (the entering column against the next candidate
 included), and `gap_slope`, the smallest |slope'| / slope over every walk
 decision.  Both say how far the walk is from depending on the fp64 summation
 order.
+
+`ties` counts the passes in which a decision met an exact tie: "row" and "ratio"
+as in tests/dual_box_ref.py, "walk" (two consecutive candidates of the walk,
+the entering column against the next one included, with equal keys) and
+"slope0" (slope' == 0); `walk_run` is the longest run of equal keys among the
+candidates one walk visited.
 """
 from dataclasses import dataclass
 
@@ -26,7 +35,7 @@ import numpy as np
 
 from dual_box_ref import (DANTZIG, NOT_DUAL_FEASIBLE, STEEPEST, DualBoxResult, boxed, certificate,  # noqa: F401
                           dual_simplex_box, farkas, tiny_box_infeasible)
-from dual_ref import INFEASIBLE, MAX_ITER, OPTIMUM
+from dual_ref import INFEASIBLE, MAX_ITER, OPTIMUM, tied, whole
 from dual_se_ref import _rel_gap, row_norms2
 
 TEXTBOOK, LONG_STEP = "textbook", "long"
@@ -39,6 +48,7 @@ class DualLongResult(DualBoxResult):
     max_flips: int = 0      # the largest flip count of one pass
     gap_walk: float = np.inf
     gap_slope: float = np.inf
+    walk_run: int = 0       # the longest run of equal keys among the candidates one walk visited
 
     @property
     def counters(self):
@@ -92,7 +102,9 @@ def dual_simplex_long(A, b, c, u, rule=DANTZIG, ratio=LONG_STEP, basis=None, at_
 
     trace = []
     gap_row = gap_ratio = gap_walk = gap_slope = np.inf
-    to_upper = flips = flip_passes = max_flips = 0
+    to_upper = flips = flip_passes = max_flips = walk_run = 0
+    ties = {"row": 0, "ratio": 0, "walk": 0, "slope0": 0}
+    integral = True
     it = 0
     status = MAX_ITER
     while it < max_iter:
@@ -108,6 +120,7 @@ def dual_simplex_long(A, b, c, u, rule=DANTZIG, ratio=LONG_STEP, basis=None, at_
         else:
             rkey = np.where(rows, -np.abs(delta), np.inf)
         q = int(np.argmin(rkey))
+        ties["row"] += int(tied(rkey))
         if rows.sum() > 1:
             two = np.partition(rkey, 1)[:2]
             gap_row = min(gap_row, _rel_gap(two[0], two[1]))
@@ -127,20 +140,27 @@ def dual_simplex_long(A, b, c, u, rule=DANTZIG, ratio=LONG_STEP, basis=None, at_
         order = cj[np.lexsort((cj, key[cj]))]  # (key, column) ascending
         if len(order) > 1:
             gap_ratio = min(gap_ratio, _rel_gap(key[order[0]], key[order[1]]))
+        ties["ratio"] += int(tied(key))
         slope = abs(delta[q])
         F = []
         p = -1
         gw, gs = np.inf, np.inf
+        walk_tie = slope_tie = False
+        run = 0
         for k, j in enumerate(order):
             j = int(j)
+            run = run + 1 if k > 0 and key[j] == key[order[k - 1]] else 1
+            walk_run = max(walk_run, run)
             if k + 1 < len(order) and ratio == LONG_STEP:  # (the entering column against the next one too)
                 gw = min(gw, _rel_gap(key[j], key[order[k + 1]]))
+                walk_tie = walk_tie or key[j] == key[order[k + 1]]
             if ratio == TEXTBOOK or not np.isfinite(u[j]):
                 p = j
                 break
             slope2 = slope - u[j] * (-ahat[j])
-            gs = min(gs, abs(slope2) / slope)
-            if slope2 < 0.0:
+            gs = min(gs, abs(slope2) / slope)  # (slope > 0: it starts above feas_tol and a flip leaves it above 0)
+            slope_tie = slope_tie or slope2 == 0.0
+            if slope2 <= 0.0:
                 p = j
                 break
             F.append(j)
@@ -150,6 +170,8 @@ def dual_simplex_long(A, b, c, u, rule=DANTZIG, ratio=LONG_STEP, basis=None, at_
             break
         gap_walk = min(gap_walk, gw)
         gap_slope = min(gap_slope, gs)
+        ties["walk"] += int(walk_tie)
+        ties["slope0"] += int(slope_tie)
         # 3. the flips
         if F:
             v = np.zeros(m)
@@ -179,6 +201,7 @@ def dual_simplex_long(A, b, c, u, rule=DANTZIG, ratio=LONG_STEP, basis=None, at_
         b_ixs[q] = p
         Binv = Binv - np.outer(alpha / aq, rho)
         Binv[q] = rho / aq
+        integral = integral and whole(x_b, y, Binv)
         if it < trace_cap:
             trace.append((p, q))
         it += 1
@@ -187,5 +210,6 @@ def dual_simplex_long(A, b, c, u, rule=DANTZIG, ratio=LONG_STEP, basis=None, at_
     for j in np.flatnonzero(up):  # ascending j
         zu += c[j] * u[j]
     return DualLongResult(status, z + zu, it, b_ixs.copy(), x_b.copy(), up.copy(), trace, float(gap_row),
-                          float(gap_ratio), to_upper, placed, flips=flips, flip_passes=flip_passes,
-                          max_flips=max_flips, gap_walk=float(gap_walk), gap_slope=float(gap_slope))
+                          float(gap_ratio), to_upper, placed, y=y.copy(), Binv=Binv.copy(), ties=ties,
+                          integral=integral, flips=flips, flip_passes=flip_passes, max_flips=max_flips,
+                          gap_walk=float(gap_walk), gap_slope=float(gap_slope), walk_run=walk_run)

@@ -47,6 +47,20 @@ class DualResult:
     b_ixs: np.ndarray
     x_b: np.ndarray
     trace: list = field(default_factory=list)
+    y: np.ndarray = None     # final duals and inverse (the exact-tie tests compare them bit for bit)
+    Binv: np.ndarray = None
+    ties: dict = field(default_factory=dict)  # passes whose argmin met an exact tie: "row", "ratio"
+    integral: bool = True    # x_b, y and B^-1 held integers only after every pass
+
+
+def tied(key):
+    """Whether the smallest finite entry of `key` occurs more than once."""
+    k = float(np.min(key))
+    return bool(np.isfinite(k) and np.count_nonzero(key == k) > 1)
+
+
+def whole(*arrays):
+    return all(bool(np.all(v == np.rint(v))) for v in arrays)
 
 
 def dual_simplex(A, b, c, feas_tol=1e-9, piv_tol=1e-9, max_iter=1 << 62, trace_cap=200):
@@ -61,6 +75,8 @@ def dual_simplex(A, b, c, feas_tol=1e-9, piv_tol=1e-9, max_iter=1 << 62, trace_c
     basic = np.zeros(n, dtype=bool)
     basic[b_ixs] = True
     trace = []
+    ties = {"row": 0, "ratio": 0}
+    integral = True
     it = 0
     status = MAX_ITER
     while it < max_iter:
@@ -69,6 +85,7 @@ def dual_simplex(A, b, c, feas_tol=1e-9, piv_tol=1e-9, max_iter=1 << 62, trace_c
         if not x_b[q] < -feas_tol:
             status = OPTIMUM
             break
+        ties["row"] += int(tied(x_b))
         # 2. pivot row
         rho = Binv[q].copy()
         # 3. dual ratio test over the non-basic columns
@@ -80,6 +97,7 @@ def dual_simplex(A, b, c, feas_tol=1e-9, piv_tol=1e-9, max_iter=1 << 62, trace_c
             break
         key = np.where(cand, np.maximum(d, 0.0) / np.where(cand, -a, 1.0), np.inf)
         p = int(np.argmin(key))  # smallest column index on ties
+        ties["ratio"] += int(tied(key))
         # 4. FTRAN and update
         alpha = Binv @ A[:, p]
         aq = alpha[q]
@@ -93,7 +111,9 @@ def dual_simplex(A, b, c, feas_tol=1e-9, piv_tol=1e-9, max_iter=1 << 62, trace_c
         b_ixs[q] = p
         Binv = Binv - np.outer(alpha / aq, rho)
         Binv[q] = rho / aq
+        integral = integral and whole(x_b, y, Binv)
         if it < trace_cap:
             trace.append((p, q))
         it += 1
-    return DualResult(status, float(c_B @ x_b), it, b_ixs.copy(), x_b.copy(), trace)
+    return DualResult(status, float(c_B @ x_b), it, b_ixs.copy(), x_b.copy(), trace, y.copy(), Binv.copy(), ties,
+                      integral)

@@ -21,7 +21,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from dual_ref import INFEASIBLE, MAX_ITER, OPTIMUM
+from dual_ref import INFEASIBLE, MAX_ITER, OPTIMUM, tied, whole
 
 W_FLOOR = 1e-300
 
@@ -38,6 +38,10 @@ class DualSEResult:
     gap_ratio: float = np.inf
     update_err: float = 0.0
     weights: np.ndarray = None  # exact weights of the final basis
+    y: np.ndarray = None        # final duals and inverse
+    Binv: np.ndarray = None
+    ties: dict = field(default_factory=dict)  # passes whose argmin met an exact tie: "row", "ratio"
+    integral: bool = True       # x_b, y and B^-1 held integers only after every pass
 
 
 def row_norms2(Binv):
@@ -83,6 +87,8 @@ def dual_simplex_se(A, b, c, basis=None, feas_tol=1e-9, piv_tol=1e-9, max_iter=1
     trace = []
     gap_row = gap_ratio = np.inf
     update_err = 0.0
+    ties = {"row": 0, "ratio": 0}
+    integral = True
     it = 0
     status = MAX_ITER
     while it < max_iter:
@@ -94,6 +100,7 @@ def dual_simplex_se(A, b, c, basis=None, feas_tol=1e-9, piv_tol=1e-9, max_iter=1
             break
         rkey = np.where(rows, -(x_b * x_b) / w, np.inf)
         q = int(np.argmin(rkey))
+        ties["row"] += int(tied(rkey))
         if rows.sum() > 1:
             two = np.partition(rkey, 1)[:2]
             gap_row = min(gap_row, _rel_gap(two[0], two[1]))
@@ -108,6 +115,7 @@ def dual_simplex_se(A, b, c, basis=None, feas_tol=1e-9, piv_tol=1e-9, max_iter=1
             break
         key = np.where(cand, np.maximum(d, 0.0) / np.where(cand, -a, 1.0), np.inf)
         p = int(np.argmin(key))  # smallest column index on ties
+        ties["ratio"] += int(tied(key))
         if cand.sum() > 1:
             two = np.partition(key, 1)[:2]
             gap_ratio = min(gap_ratio, _rel_gap(two[0], two[1]))
@@ -129,8 +137,9 @@ def dual_simplex_se(A, b, c, basis=None, feas_tol=1e-9, piv_tol=1e-9, max_iter=1
         if check_update:
             exact = row_norms2(Binv)
             update_err = max(update_err, float(np.max(np.abs(w_next - exact) / exact)))
+        integral = integral and whole(x_b, y, Binv)
         if it < trace_cap:
             trace.append((p, q))
         it += 1
     return DualSEResult(status, float(c_B @ x_b), it, b_ixs.copy(), x_b.copy(), trace, float(gap_row),
-                        float(gap_ratio), update_err, row_norms2(Binv))
+                        float(gap_ratio), update_err, row_norms2(Binv), y.copy(), Binv.copy(), ties, integral)

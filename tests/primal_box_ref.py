@@ -37,7 +37,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from dual_box_ref import certificate  # noqa: F401  (the tests take it from here)
-from dual_ref import MAX_ITER, OPTIMUM
+from dual_ref import MAX_ITER, OPTIMUM, tied, whole
 from dual_se_ref import _rel_gap
 
 UNBOUNDED = "unbounded"
@@ -117,6 +117,12 @@ class PrimalBoxResult:
     to_upper: int = 0               # pivots whose row left to its upper bound
     bad_row: int = -1               # NOT_PRIMAL_FEASIBLE: the first row out of its bounds
     bad_column: int = -1            # ... and its basic column
+    y: np.ndarray = None            # final duals and inverse
+    Binv: np.ndarray = None
+    # passes in which a decision met an exact tie: "price" (entering argmin), "ratio" (leaving-row argmin),
+    # "flip" (u_p == t_q: the rule flips)
+    ties: dict = field(default_factory=dict)
+    integral: bool = True           # x_b, y and B^-1 held integers only after every pass
 
     def primal(self, u):
         x = np.where(self.at_upper, np.where(np.isfinite(u), u, 0.0), 0.0)
@@ -159,11 +165,14 @@ def primal_simplex_box(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_tol
         for j in np.flatnonzero(up):  # ascending j
             zu += c[j] * u[j]
         return PrimalBoxResult(status, z + zu, it, b_ixs.copy(), x_b.copy(), up.copy(), trace, float(gap_price),
-                               float(gap_ratio), float(gap_flip), flips, to_upper, **kw)
+                               float(gap_ratio), float(gap_flip), flips, to_upper, y=y.copy(), Binv=Binv.copy(),
+                               ties=ties, integral=integral, **kw)
 
     trace = []
     gap_price = gap_ratio = gap_flip = np.inf
     flips = to_upper = 0
+    ties = {"price": 0, "ratio": 0, "flip": 0}
+    integral = True
     it = 0
     # entry check
     bad = np.flatnonzero((x_b < -feas_tol) | (x_b > u[b_ixs] + feas_tol))
@@ -182,6 +191,7 @@ def primal_simplex_box(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_tol
             break
         key = np.where(cand, key, np.inf)
         p = int(np.argmin(key))  # smallest column on ties
+        ties["price"] += int(tied(key))
         if cand.sum() > 1:
             two = np.partition(key, 1)[:2]
             gap_price = min(gap_price, _rel_gap(two[0], two[1]))
@@ -204,11 +214,15 @@ def primal_simplex_box(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_tol
         u_p = u[p]
         if np.isfinite(u_p) and q >= 0:
             gap_flip = min(gap_flip, _rel_gap(u_p, t[q]))
+            ties["flip"] += int(u_p == t[q])
+        if q >= 0:
+            ties["ratio"] += int(tied(t))
         # 4. flip
         if np.isfinite(u_p) and (q < 0 or u_p <= t[q]):
             x_b = x_b - u_p * ahat
             up[p] = not up[p]
             flips += 1
+            integral = integral and whole(x_b)
             continue
         # 5. unbounded
         if q < 0:
@@ -231,6 +245,7 @@ def primal_simplex_box(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_tol
         b_ixs[q] = p
         Binv = Binv - np.outer(alpha / aq, rho)
         Binv[q] = rho / aq
+        integral = integral and whole(x_b, y, Binv)
         if it < trace_cap:
             trace.append((p, q))
         it += 1

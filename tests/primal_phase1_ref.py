@@ -31,7 +31,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from dual_ref import MAX_ITER, OPTIMUM
+from dual_ref import MAX_ITER, OPTIMUM, tied, whole
 from dual_se_ref import _rel_gap
 from primal_box_ref import UNBOUNDED, certificate  # noqa: F401  (the tests take it from here)
 
@@ -111,6 +111,12 @@ class Phase1Result:
     ninf0: int = 0       # infeasible rows at entry
     ninf: int = 0        # ... at the end
     ninf_hist: list = field(default_factory=list)  # ninf at the start of every pass
+    y: np.ndarray = None   # final duals (c_B.B^-1 where phase 1 left y stale, as the library reads it back) and inverse
+    Binv: np.ndarray = None
+    # passes in which a decision met an exact tie: "price", "ratio", "flip" (u_p == t_q) as in
+    # tests/primal_box_ref.py over both phases, "p1_price", "p1_ratio", "p1_flip" over the phase-1 passes alone
+    ties: dict = field(default_factory=dict)
+    integral: bool = True  # x_b, y and B^-1 held integers only after every pass
 
     def primal(self, u):
         x = np.where(self.at_upper, np.where(np.isfinite(u), u, 0.0), 0.0)
@@ -152,6 +158,8 @@ def primal_simplex_phase1(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_
     trace = []
     gap_price = gap_ratio = gap_flip = np.inf
     flips = to_upper = p1_passes = p1_pivots = 0
+    ties = {"price": 0, "ratio": 0, "flip": 0, "p1_price": 0, "p1_ratio": 0, "p1_flip": 0}
+    integral = True
     hist = []
     it = 0
     w = _classify(x_b, u[b_ixs], feas_tol)
@@ -163,7 +171,13 @@ def primal_simplex_phase1(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_
         for j in np.flatnonzero(up):  # ascending j
             zu += c[j] * u[j]
         return Phase1Result(status, z + zu, it, b_ixs.copy(), x_b.copy(), up.copy(), trace, float(gap_price),
-                            float(gap_ratio), float(gap_flip), flips, to_upper, p1_passes, p1_pivots, ninf0, ninf, hist)
+                            float(gap_ratio), float(gap_flip), flips, to_upper, p1_passes, p1_pivots, ninf0, ninf, hist,
+                            c_B @ Binv if y_stale else y.copy(), Binv.copy(), ties, integral)
+
+    def tie(name, hit, ph1):
+        ties[name] += int(hit)
+        if ph1:
+            ties["p1_" + name] += int(hit)
 
     status = MAX_ITER
     while it < max_iter:
@@ -185,6 +199,7 @@ def primal_simplex_phase1(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_
             break
         key = np.where(cand, key, np.inf)
         p = int(np.argmin(key))
+        tie("price", tied(key), ph1)
         if cand.sum() > 1:
             two = np.partition(key, 1)[:2]
             gap_price = min(gap_price, _rel_gap(two[0], two[1]))
@@ -215,12 +230,16 @@ def primal_simplex_phase1(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_
         u_p = u[p]
         if np.isfinite(u_p) and q >= 0:
             gap_flip = min(gap_flip, _rel_gap(u_p, t[q]))
+            tie("flip", u_p == t[q], ph1)
+        if q >= 0:
+            tie("ratio", tied(t), ph1)
         p1_passes += int(ph1)
         # 4. flip
         if np.isfinite(u_p) and (q < 0 or u_p <= t[q]):
             x_b = x_b - u_p * ahat
             up[p] = not up[p]
             flips += 1
+            integral = integral and whole(x_b)
             if ph1:
                 w = _classify(x_b, u[b_ixs], feas_tol)
                 ninf = int(np.count_nonzero(w))
@@ -251,6 +270,7 @@ def primal_simplex_phase1(A, b, c, u, basis=None, at_upper=None, eps=1e-7, feas_
         b_ixs[q] = p
         Binv = Binv - np.outer(alpha / aq, rho)
         Binv[q] = rho / aq
+        integral = integral and whole(x_b, y, Binv)
         if it < trace_cap:
             trace.append((p, q))
         it += 1
