@@ -178,8 +178,9 @@ typedef struct spx_opts {
  *         spx_iterate(k) count pivots only.  With every bound +inf this is the
  *         primal loop's Dantzig rule with SPX_RATIO_GUARDED.  Scope and refusals
  *         are DUAL's (spx_create: SPX_ERR_ARG naming the combination; spx_price /
- *         spx_pivot / spx_group_iterate: SPX_ERR_STATE).  No Devex / steepest
- *         edge, no non-zero or free lower bounds.  SPX_ALGO_PRIMAL itself still
+ *         spx_pivot / spx_group_iterate: SPX_ERR_STATE).  The entering rule is
+ *         SPX_PRIMAL_PRICING_* (below: Dantzig, or exact steepest edge); no
+ *         Devex, no non-zero or free lower bounds.  SPX_ALGO_PRIMAL itself still
  *         refuses finite bounds.
  *         Phase 1 (opt-in: SPX_FLAG_PRIMAL_PHASE1, spx_set_primal_phase1;
  *         DESIGN.md §7f).  With it the entry check refuses nothing: row i is
@@ -226,6 +227,36 @@ typedef struct spx_opts {
  *           recomputed from B^-1 before the next pass. */
 #define SPX_DUAL_PRICING_DANTZIG  0
 #define SPX_DUAL_PRICING_STEEPEST 1
+
+/* Entering rules of the bounded primal loop (SPX_FLAG_PRIMAL_STEEPEST at
+ * spx_create, spx_set_primal_pricing later; opts.pricing is the windowed primal
+ * loop's field and stays Dantzig under SPX_ALGO_PRIMAL_BOX and SPX_ALGO_DUAL).
+ * DANTZIG:  p = argmin sigma_j d_j over the candidates (above).
+ * STEEPEST: exact primal steepest edge with the weights
+ *           gamma_j = 1 + ||B^-1 A_j||^2 of the non-basic columns; they do not
+ *           depend on the bound a column sits at, and a flip pass changes none.
+ *           The candidates are unchanged (sigma_j d_j < -eps; none:
+ *           OPTIMUM_FOUND) and p = argmin of -d_j^2 / gamma_j over them, first
+ *           column on ties.  The ratio test, the flips, the unbounded exit, the
+ *           commit and the y update are DANTZIG's.  After a pivot on row q with
+ *           alpha = B^-1 A_p, rho = row q of B^-1 and tau = alpha^T B^-1 (both of
+ *           the B^-1 before the pivot, so tau.A_j = A_j.B^-T alpha) and gamma_p =
+ *           1 + ||alpha||^2 recomputed exactly, every column j that was
+ *           non-basic before the pivot and is not p gets, with g = (rho.A_j) /
+ *           alpha_q, gamma_j = max(gamma_j - 2 g (tau.A_j) + g^2 gamma_p, 1 +
+ *           g^2), and the leaving column gamma = max(gamma_p / alpha_q^2, 1)
+ *           (Goldfarb and Reid's update; no reset rule).  Where no pass has
+ *           kept them (spx_create, spx_reset, spx_set_basis, spx_set_algorithm
+ *           into the loop, a change of rule) the weights restart at 1 +
+ *           ||A_j||^2: exact at the slack basis, a reference framework and not
+ *           the exact norm for a warm basis.  spx_reinvert, refactor_every,
+ *           spx_set_cost, spx_set_rhs and spx_set_bounds keep the basis and the
+ *           weights.  Not together with phase 1 (SPX_FLAG_PRIMAL_PHASE1 /
+ *           spx_set_primal_phase1): spx_create refuses the two flags with
+ *           SPX_ERR_ARG, and whichever setter arrives second returns
+ *           SPX_ERR_STATE. */
+#define SPX_PRIMAL_PRICING_DANTZIG  0
+#define SPX_PRIMAL_PRICING_STEEPEST 1
 
 /* Ratio tests of the dual loop's boxed passes (SPX_FLAG_DUAL_LONG_STEP at
  * spx_create, spx_set_dual_ratio later).
@@ -357,6 +388,12 @@ typedef struct spx_opts {
                                        starts with its phase 1 enabled (default off:
                                        a basis out of its bounds is refused); accepted
                                        and inert under the other algorithms         */
+
+#define SPX_FLAG_PRIMAL_STEEPEST 16384 /* the bounded primal loop starts with the entering
+                                         rule SPX_PRIMAL_PRICING_STEEPEST (default
+                                         DANTZIG); accepted and inert under the other
+                                         algorithms; SPX_ERR_ARG together with
+                                         SPX_FLAG_PRIMAL_PHASE1                       */
 
 void spx_default_opts(spx_opts* opts);
 
@@ -500,6 +537,18 @@ int spx_get_primal_flips(spx_ctx* ctx, int64_t out[2]);
  * SPX_ALGO_PRIMAL_BOX).  The entry check runs again before the next pass. */
 int spx_set_primal_phase1(spx_ctx* ctx, int32_t on);
 
+/* Entering rule of the bounded primal loop (SPX_PRIMAL_PRICING_*), between any
+ * two calls and under any algorithm; takes effect with the next bounded primal
+ * pass.  A change of rule restarts the steepest-edge weights.  SPX_ERR_ARG for
+ * NULL or an unknown rule; SPX_ERR_STATE for STEEPEST while phase 1 is on. */
+int spx_set_primal_pricing(spx_ctx* ctx, int32_t rule);
+
+/* Steepest-edge weights w[0..n) of the current basis, by column: the non-basic
+ * entries are live (1 + ||B^-1 A_j||^2 as the recurrence keeps it, a pending
+ * update applied first), a basic column's entry is unspecified.  SPX_ERR_STATE
+ * under SPX_PRIMAL_PRICING_DANTZIG or outside SPX_ALGO_PRIMAL_BOX. */
+int spx_get_primal_weights(spx_ctx* ctx, double* w /* n */);
+
 /* Phase-1 counters of the bounded primal loop, kept on the device by the kernel
  * that commits the pass: out[0] phase-1 passes since spx_create or spx_reset
  * (flip passes included), out[1] phase-1 pivots, out[2] rows out of their
@@ -580,7 +629,9 @@ int spx_kernel_times(spx_ctx* ctx, double* price_ms, int64_t* price_launches,
 /* With SPX_FLAG_TIMING, bounded primal loop with phase 1 on: total device
  * milliseconds and count of the v.B^-1 step (k_pbox_vtb and its reduction) of
  * the four-step passes since the last call (resets); a step that found nothing
- * to do (phase 2, y current) is counted with its near-zero time. */
+ * to do (phase 2, y current) is counted with its near-zero time.  Under
+ * SPX_PRIMAL_PRICING_STEEPEST the same counters carry the tau = alpha^T B^-1
+ * step of every pass (a pass without a pivot with its near-zero time). */
 int spx_pbox_vtb_times(spx_ctx* ctx, double* ms, int64_t* launches);
 
 /* With SPX_FLAG_TIMING: device milliseconds summed since the last call (resets)

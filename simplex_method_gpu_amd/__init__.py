@@ -28,7 +28,7 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL",
            "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST",
            "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX",
-           "FLAG_PRIMAL_PHASE1"]
+           "FLAG_PRIMAL_PHASE1", "PRIMAL_PRICING_DANTZIG", "PRIMAL_PRICING_STEEPEST", "FLAG_PRIMAL_STEEPEST"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -60,6 +60,9 @@ DUAL_PRICING_DANTZIG, DUAL_PRICING_STEEPEST = 0, 1
 DUAL_RATIO_TEXTBOOK, DUAL_RATIO_LONG_STEP = 0, 1
 FLAG_DUAL_LONG_STEP = 4096  # the dual loop starts with the bound-flipping ratio test (default: textbook)
 FLAG_PRIMAL_PHASE1 = 8192  # the bounded primal loop starts with its phase 1 on (default: an infeasible basis is refused)
+# entering rules of the bounded primal loop (include/simplex.h SPX_PRIMAL_PRICING_*)
+PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST = 0, 1
+FLAG_PRIMAL_STEEPEST = 16384  # the bounded primal loop starts with exact steepest-edge pricing (default: Dantzig)
 
 
 class SolveStatus(IntEnum):
@@ -175,7 +178,8 @@ class Context:
                  tableau: bool = False, trace: int = 0, counted_tail: bool = False,
                  price_tail: bool = False, algorithm: int = ALGO_PRIMAL,
                  dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None,
-                 dual_ratio: int = DUAL_RATIO_TEXTBOOK, primal_phase1: bool = False):
+                 dual_ratio: int = DUAL_RATIO_TEXTBOOK, primal_phase1: bool = False,
+                 primal_pricing: int = PRIMAL_PRICING_DANTZIG):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -195,6 +199,9 @@ class Context:
         if dual_ratio not in (DUAL_RATIO_TEXTBOOK, DUAL_RATIO_LONG_STEP):
             raise ValueError("dual_ratio must be DUAL_RATIO_TEXTBOOK or DUAL_RATIO_LONG_STEP")
         self._dual_ratio = dual_ratio
+        if primal_pricing not in (PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST):
+            raise ValueError("primal_pricing must be PRIMAL_PRICING_DANTZIG or PRIMAL_PRICING_STEEPEST")
+        self._primal_pricing = primal_pricing
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
@@ -203,7 +210,8 @@ class Context:
                    | (FLAG_COUNTED_TAIL if counted_tail else 0) | (FLAG_PRICE_TAIL if price_tail else 0)
                    | (FLAG_DUAL_STEEPEST if dual_pricing == DUAL_PRICING_STEEPEST else 0)
                    | (FLAG_DUAL_LONG_STEP if dual_ratio == DUAL_RATIO_LONG_STEP else 0)
-                   | (FLAG_PRIMAL_PHASE1 if primal_phase1 else 0))
+                   | (FLAG_PRIMAL_PHASE1 if primal_phase1 else 0)
+                   | (FLAG_PRIMAL_STEEPEST if primal_pricing == PRIMAL_PRICING_STEEPEST else 0))
         h = ctypes.c_void_p()
         if A_cols is not None:
             A_cols = np.ascontiguousarray(A_cols, dtype=np.float64)
@@ -362,6 +370,20 @@ class Context:
         again before the next pass."""
         check(self._L.spx_set_primal_phase1(self._h, 1 if on else 0))
 
+    def set_primal_pricing(self, rule: int):
+        """Entering rule of the bounded primal loop from the next bounded primal
+        pass on (spx_set_primal_pricing): PRIMAL_PRICING_DANTZIG /
+        PRIMAL_PRICING_STEEPEST.  A change of rule restarts the weights."""
+        check(self._L.spx_set_primal_pricing(self._h, rule))
+        self._primal_pricing = rule
+
+    def primal_weights(self):
+        """Steepest-edge weights of the bounded primal loop by column, n entries
+        (spx_get_primal_weights): the non-basic entries are live."""
+        w = np.empty(self.n, dtype=np.float64)
+        check(self._L.spx_get_primal_weights(self._h, _ptr(w)))
+        return w
+
     def primal_phase1(self):
         """(phase-1 passes, phase-1 pivots, rows out of their bounds at the last
         entry check, rows out of their bounds now) of the bounded primal loop
@@ -475,7 +497,8 @@ class Context:
 
     def vtb_times(self):
         """(milliseconds, launches) of the bounded primal loop's v.B^-1 step in
-        four-step passes since the last call (timing=True; spx_pbox_vtb_times)."""
+        four-step passes since the last call (timing=True; spx_pbox_vtb_times);
+        under PRIMAL_PRICING_STEEPEST, of the tau = alpha^T B^-1 step of every pass."""
         ms, k = ctypes.c_double(), ctypes.c_int64()
         check(self._L.spx_pbox_vtb_times(self._h, ctypes.byref(ms), ctypes.byref(k)))
         return ms.value, k.value
@@ -579,6 +602,7 @@ class Context:
                 "ftran_rows_per_wave", "mbox_fused", "compact_price")
         cfg = dict(zip(keys, list(out)))
         cfg["dual_pricing"] = self._dual_pricing  # (the library keeps it outside spx_config)
+        cfg["primal_pricing"] = self._primal_pricing
         cfg["dual_ratio"] = self._dual_ratio
         return cfg
 

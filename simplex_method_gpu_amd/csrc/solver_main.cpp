@@ -43,6 +43,10 @@
 //                  be out of its bounds (b of any sign, any slack bounds); an
 //                  infeasible LP ends with "Problem infeasible."; --json then
 //                  also carries the phase-1 pass and pivot counts
+//   --primal-pricing R  entering rule of --primal-box: dantzig (default) | steepest
+//                  (exact steepest edge, SPX_PRIMAL_PRICING_STEEPEST); without
+//                  --primal-box it is refused with the usage message (exit 1);
+//                  not with --phase1 (the library's refusal is printed)
 //   --bounds F     upper bounds 0 <= x_j <= u_j of all n columns for --dual or
 //                  --primal-box (spx_set_bounds): F holds n whitespace-separated
 //                  values, "inf" = none; without either the library's refusal is
@@ -91,7 +95,7 @@ static void print_elapsed_time(const char* msg, double dur) {
 static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
-                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1]]"
+                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest]]"
                  " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
@@ -112,6 +116,7 @@ int main(int argc, char* argv[]) {
     double piv_tol = 1e-9, feas_tol = 1e-9, big_m = 0.0;
     int64_t refactor = 0;
     bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false, primal_box = false, phase1 = false;
+    bool primal_pricing_given = false, primal_steepest = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -155,6 +160,13 @@ int main(int argc, char* argv[]) {
             if (r != "dantzig" && r != "steepest") { usage(); return 1; }
             dual_steepest = r == "steepest";
         }
+        else if (s == "--primal-pricing") {
+            need(1);
+            const std::string r = argv[++a];
+            if (r != "dantzig" && r != "steepest") { usage(); return 1; }
+            primal_pricing_given = true;
+            primal_steepest = r == "steepest";
+        }
         else if (s == "--dual-ratio") {
             need(1);
             const std::string r = argv[++a];
@@ -187,6 +199,11 @@ int main(int argc, char* argv[]) {
     }
     if (phase1 && !primal_box) {
         std::cerr << "--phase1 needs --primal-box: it is the bounded primal loop's phase 1\n";
+        return 1;
+    }
+    if (primal_pricing_given && !primal_box) {
+        std::cerr << "--primal-pricing needs --primal-box: it is the bounded primal loop's entering rule\n";
+        usage();
         return 1;
     }
     if (primal_box) {
@@ -250,6 +267,7 @@ int main(int argc, char* argv[]) {
     if (dual_steepest) o.flags |= SPX_FLAG_DUAL_STEEPEST;
     if (dual_long) o.flags |= SPX_FLAG_DUAL_LONG_STEP;
     if (phase1) o.flags |= SPX_FLAG_PRIMAL_PHASE1;
+    if (primal_steepest) o.flags |= SPX_FLAG_PRIMAL_STEEPEST;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)

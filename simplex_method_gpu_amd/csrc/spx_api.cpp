@@ -173,7 +173,7 @@ int setup_common(spx_ctx* x, int64_t m, int64_t n, const spx_opts* opts) {
     }
     x->algo = x->opts.algorithm;
     dual_on_create(x);
-    pbox_on_create(x);
+    SPX_TRY(pbox_on_create(x));
     P.ratio = rule;
     P.piv_tol = rule == SPX_RATIO_REFERENCE ? 0.0 : x->opts.piv_tol;
     P.feas_tol = rule == SPX_RATIO_HARRIS ? x->opts.feas_tol : 0.0;
@@ -1474,6 +1474,7 @@ int spx_set_basis(spx_ctx* x, const int64_t* basis) {
     SPX_TRY(check_basis(x, basis));
     if (x->P.row_shard) return fail(SPX_ERR_STATE, "spx_set_basis needs replicated B^-1 (no row sharding)");
     dual_on_new_basis(x);
+    pbox_weights_lost(x);
     // this rank's non-basic list (ascending, owned columns only) and positions
     std::vector<char> basic((size_t)x->n, 0);
     for (int64_t k = 0; k < x->m; ++k) basic[(size_t)basis[k]] = 1;

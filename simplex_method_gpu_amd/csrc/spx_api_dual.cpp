@@ -345,6 +345,7 @@ int dual_switch_algorithm(spx_ctx* x, int32_t algo) {
     feasibility_unknown(x);
     weights_lost(x);  // (primal passes keep no dual weights)
     pbox_on_change(x);
+    pbox_weights_lost(x);
     return SPX_OK;
 }
 

@@ -4,6 +4,7 @@
 // any of it, and the entry point that is this loop's alone.  The bounds and
 // placements are the dual loop's state, reached through spx_api_dual.cpp's hooks.
 #include <cmath>
+#include <cstdlib>
 
 #include "spx_ctx.h"
 
@@ -89,6 +90,54 @@ int pbox_setup(spx_ctx* x) {
     return SPX_OK;
 }
 
+namespace {
+
+// the steepest-edge buffers and geometry, on first use (after pbox_setup)
+int pbox_se_setup(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    if (s.se.se) return SPX_OK;
+    // experiment (SPX_PBOX_SE_LDS): vectors of k_pbox_price_se staged in LDS -- 0, 1 or 3
+    const char* ev = std::getenv("SPX_PBOX_SE_LDS");
+    HIP_TRY(pbox_se_prepare(x->P, x->cus, s.cfg.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
+                            ev ? std::atoi(ev) : -1, &s.secfg));
+    s.se.vtb_blocks = s.cfg.vtb_blocks;
+    s.se.apply = 0;
+    SPX_TRY(x->alloc(&s.se.gamma, (size_t)x->n));
+    SPX_TRY(x->alloc(&s.se.rho, (size_t)x->L));
+    SPX_TRY(x->alloc(&s.se.tau, (size_t)x->L));
+    SPX_TRY(x->alloc(&s.se.tparts, (size_t)s.cfg.vtb_blocks * (size_t)x->L));
+    SPX_TRY(x->alloc(&s.se.se, 1));
+    s.se_stale = true;
+    return SPX_OK;
+}
+
+// weights nobody kept: gamma_j = 1 + ||A_j||^2 (exact at the slack basis, a
+// reference framework elsewhere) and nothing pending
+int pbox_se_restart(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    if (!s.se_stale) return SPX_OK;
+    HIP_TRY(hipMemsetAsync(s.se.se, 0, sizeof(PboxSeRec), x->stream));
+    HIP_TRY(launch_pbox_se_init(x->P, s.se, s.secfg, x->stream));
+    s.se_stale = false;
+    return SPX_OK;
+}
+
+// timing: the next event pair around the vtb / tau step
+int vtb_events(spx_ctx* x, hipEvent_t* v0, hipEvent_t* v1) {
+    PboxState& s = x->pbox;
+    while (s.ev_vtb.size() < 2 * (s.n_vtb + 1)) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        s.ev_vtb.push_back(e);
+    }
+    *v0 = s.ev_vtb[2 * s.n_vtb];
+    *v1 = s.ev_vtb[2 * s.n_vtb + 1];
+    ++s.n_vtb;
+    return SPX_OK;
+}
+
+}  // namespace
+
 // k pivots or a terminal status.  A pass is three eager launches and makes a
 // pivot or a flip; the host enqueues as many passes as pivots are missing,
 // synchronises once, and goes round again for the flips' share.  Every kernel
@@ -97,10 +146,24 @@ int pbox_setup(spx_ctx* x) {
 // one (k_pbox_vtb first, then the kernels that read the phase from the device),
 // which runs on through the switch inside a round; the readback that shows
 // ninf == 0 and y current brings the three-launch pass back.
+// Steepest edge: a pass is price_se -> update -> step_se -> tau,
+// after the weights were restarted where nobody kept them; the pending weight
+// update lives on the device with its own operands, so nothing here tracks it.
 int iterate_pbox(spx_ctx* x, int64_t k) {
     SPX_TRY(pbox_setup(x));
     if (!x->pbox.checked) SPX_TRY(pbox_check_entry(x));
     PboxState& s = x->pbox;
+    const bool steep = s.rule == SPX_PRIMAL_PRICING_STEEPEST;
+    PboxArgs se_args = s.args;
+    if (steep) {
+        if (s.phase1)
+            return fail(SPX_ERR_STATE, "steepest-edge pricing does not run with the bounded primal loop's phase 1");
+        SPX_TRY(pbox_se_setup(x));
+        SPX_TRY(pbox_se_restart(x));
+        se_args.price_grid = s.secfg.price_grid;  // k_pbox_update merges this pass's partials
+    } else {
+        s.se_stale = true;  // a Dantzig pass keeps no weights
+    }
     const int64_t target = x->pivots + k;
     SPX_TRY(set_limit(x, target));
     while (x->status == SPX_STATUS_MAX_ITER && x->pivots < target) {
@@ -108,6 +171,17 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
         for (int64_t i = 0; i < round; ++i) {
             hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
             if (x->timing) SPX_TRY(pass_events(x, &p0, &p1, &u0, &u1));
+            if (steep) {  // price -> update -> step -> tau
+                hipEvent_t v0 = nullptr, v1 = nullptr;
+                if (x->timing) SPX_TRY(vtb_events(x, &v0, &v1));
+                HIP_TRY(launch_pbox_price_se(x->P, se_args, s.se, s.secfg, false, x->stream, p0, p1));
+                if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
+                HIP_TRY(launch_pbox_update(x->P, se_args, s.cfg, x->stream, u0, u1));
+                HIP_TRY(launch_pbox_step_se(x->P, se_args, s.se, x->stream));
+                HIP_TRY(launch_pbox_tau(x->P, s.se, s.cfg, x->stream, v0, v1));
+                ++x->n_eager;
+                continue;
+            }
             if (s.phase1 && (s.ninf > 0 || s.y_stale)) {
                 s.y_dirty = true;
                 hipEvent_t v0 = nullptr, v1 = nullptr;
@@ -149,12 +223,22 @@ int pbox_on_reset(spx_ctx* x) {
     x->pbox.checked = false;
     x->pbox.y_dirty = false;
     x->pbox.ninf = x->pbox.y_stale = 0;
+    x->pbox.se_stale = true;
     return SPX_OK;
 }
 
+void pbox_weights_lost(spx_ctx* x) { x->pbox.se_stale = true; }
+
 void pbox_on_change(spx_ctx* x) { x->pbox.checked = false; }
 
-void pbox_on_create(spx_ctx* x) { x->pbox.phase1 = (x->opts.flags & SPX_FLAG_PRIMAL_PHASE1) != 0; }
+int pbox_on_create(spx_ctx* x) {
+    x->pbox.phase1 = (x->opts.flags & SPX_FLAG_PRIMAL_PHASE1) != 0;
+    x->pbox.rule = (x->opts.flags & SPX_FLAG_PRIMAL_STEEPEST) ? SPX_PRIMAL_PRICING_STEEPEST : SPX_PRIMAL_PRICING_DANTZIG;
+    if (x->pbox.phase1 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_ARG, "SPX_FLAG_PRIMAL_STEEPEST with SPX_FLAG_PRIMAL_PHASE1: steepest-edge pricing does not "
+                    "run during the bounded primal loop's phase 1");
+    return SPX_OK;
+}
 
 // a reinversion has rebuilt y from c_B: nothing stale; x_b is new, so the rows
 // are classified again (the entry check does it itself when one is due)
@@ -206,9 +290,43 @@ int spx_get_primal_flips(spx_ctx* x, int64_t out[2]) {
 int spx_set_primal_phase1(spx_ctx* x, int32_t on) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_primal_phase1 between spx_price and spx_pivot");
+    if (on && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "spx_set_primal_phase1: phase 1 does not run with steepest-edge pricing "
+                    "(spx_set_primal_pricing); set SPX_PRIMAL_PRICING_DANTZIG first");
     SPX_TRY(pbox_fresh_y(x));
     x->pbox.phase1 = on != 0;
     x->pbox.checked = false;  // the entry check decides again (and classifies)
+    return SPX_OK;
+}
+
+int spx_set_primal_pricing(spx_ctx* x, int32_t rule) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (rule != SPX_PRIMAL_PRICING_DANTZIG && rule != SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_ARG, "bad primal pricing rule %d", rule);
+    if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.phase1)
+        return fail(SPX_ERR_STATE, "spx_set_primal_pricing: steepest-edge pricing does not run with the bounded primal "
+                    "loop's phase 1 (spx_set_primal_phase1); switch phase 1 off first");
+    if (rule != x->pbox.rule) x->pbox.se_stale = true;  // a change of rule restarts the weights
+    x->pbox.rule = rule;
+    return SPX_OK;
+}
+
+int spx_get_primal_weights(spx_ctx* x, double* w) {
+    if (!x || !w) return fail(SPX_ERR_ARG, "NULL argument");
+    if (x->pbox.rule != SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "no primal pricing weights: the bounded primal loop's entering rule is Dantzig");
+    if (x->algo != SPX_ALGO_PRIMAL_BOX)
+        return fail(SPX_ERR_STATE, "no primal pricing weights: the context does not run SPX_ALGO_PRIMAL_BOX");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    PboxState& s = x->pbox;
+    SPX_TRY(pbox_setup(x));
+    SPX_TRY(pbox_se_setup(x));
+    SPX_TRY(pbox_se_restart(x));
+    // a recurrence the next pricing pass would have applied: the same kernel applies it now (the device decides)
+    HIP_TRY(launch_pbox_price_se(x->P, s.args, s.se, s.secfg, true, x->stream, nullptr, nullptr));
+    HIP_TRY(hipMemsetAsync(&s.se.se->pend, 0, sizeof(int32_t), x->stream));
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(w, s.se.gamma, sizeof(double) * (size_t)x->n, hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 

@@ -103,6 +103,16 @@ struct DualState {
 //    since y was last known current, so a readback of y (flush), a switch of the
 //    algorithm or of phase1 first runs the refresh (pbox_fresh_y).  With phase1
 //    off and y_dirty clear the loop is the three-launch loop and never reads p1.
+//  - steepest edge (spx_set_primal_pricing): se.se != nullptr  <=>
+//    pbox_se_setup ran (gamma, rho, tau, tparts and the pending record, allocated
+//    by the first steepest-edge pass or weight readback; a Dantzig context never
+//    allocates or launches any of it).  se.gamma holds the weights of the current
+//    basis up to the recurrence the device record marks pending, or se_stale is
+//    set: the next steepest-edge pass or readback restarts them at 1 + ||A_j||^2
+//    and clears the record.  Only steepest-edge passes keep them: reset,
+//    spx_set_basis, spx_set_algorithm and a change of rule set se_stale; a
+//    reinversion keeps the basis and the record owns its operands, so it stays.
+//    rule == STEEPEST and phase1 never hold together (both setters refuse).
 struct PboxState {
     spx::PboxArgs args{};
     spx::PboxCfg cfg{};
@@ -112,8 +122,12 @@ struct PboxState {
     bool y_dirty = false;
     int32_t ninf = 0;
     int32_t y_stale = 0;
-    std::vector<hipEvent_t> ev_vtb;  // timing: pairs around k_pbox_vtb + k_pbox_vtb_sum (spx_pbox_vtb_times)
+    std::vector<hipEvent_t> ev_vtb;  // timing: pairs around k_pbox_vtb + k_pbox_vtb_sum, or k_pbox_tau + _sum (spx_pbox_vtb_times)
     size_t n_vtb = 0;
+    int32_t rule = SPX_PRIMAL_PRICING_DANTZIG;  // entering rule (spx_set_primal_pricing)
+    spx::PboxSeArgs se{};
+    spx::PboxSeCfg secfg{};
+    bool se_stale = true;
 };
 
 struct spx_ctx {
@@ -294,7 +308,8 @@ int pbox_setup(spx_ctx* x);  // buffers and launch geometry, on first use
 int iterate_pbox(spx_ctx* x, int64_t k);
 int pbox_on_reset(spx_ctx* x);     // do_reset: counters cleared, nothing checked
 void pbox_on_change(spx_ctx* x);   // the basis, the bounds, b, c or the algorithm were set: nothing checked
-void pbox_on_create(spx_ctx* x);   // phase 1 as opts.flags asks for
+int pbox_on_create(spx_ctx* x);    // phase 1 and the entering rule as opts.flags asks for
+void pbox_weights_lost(spx_ctx* x);  // the basis was set from outside or another loop takes it: steepest-edge weights restart
 int pbox_on_reinvert(spx_ctx* x);  // B^-1, x_b and y rebuilt: y current, the rows classified again
 int pbox_fresh_y(spx_ctx* x);      // before anything outside the loop reads y: y = c_B B^-1 if phase 1 left it stale
 

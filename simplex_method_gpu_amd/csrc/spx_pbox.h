@@ -1,6 +1,7 @@
 // spx_pbox.h — the bounded primal simplex loop's kernels (spx_pbox.hip): 0 <= x
 // <= u, one rank, explicit B^-1 (Params::win == 0, in-place storage), Dantzig
-// entering column.  DESIGN.md §7e.
+// entering column, or exact steepest edge (the *_se kernels at the end of this
+// file).  DESIGN.md §7e.
 //
 // A pass at iteration it is three launches on the context's stream; the kernel
 // boundaries are the only ordering between them:
@@ -159,5 +160,68 @@ hipError_t launch_pbox_update1(const Params& P, const PboxArgs& D, const Pbox1Ar
                                hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_pbox_step1(const Params& P, const PboxArgs& D, const Pbox1Args& X, hipStream_t s);
 hipError_t launch_pbox_classify(const Params& P, const PboxArgs& D, const Pbox1Args& X, bool entry, hipStream_t s);
+
+// Steepest edge: gamma_j = 1 + ||B^-1 A_j||^2 for the non-basic
+// columns, entering column argmin -d_j^2 / gamma_j over the candidates.  A pass
+// is four steps, ordered by kernel boundaries only:
+//   k_pbox_price_se  k_pbox_price's stream with three operands: per streamed
+//                  column y.A_j, rho.A_j and tau.A_j (same per-lane order, one
+//                  butterfly each).  While PboxSeRec::pend is set the wave
+//                  first applies the last pivot's recurrence g = (rho.A_j) /
+//                  alpha_q, gamma_j = max(gamma_j - 2 g (tau.A_j) + g^2 gamma_p,
+//                  1 + g^2) and stores gamma_j (one owner per column; the
+//                  leaving column, whose weight the commit wrote, is skipped);
+//                  then key = -d_j^2 / gamma_j.  The partial is (key, j, d_j):
+//                  k_pbox_update merges it unchanged.
+//   k_pbox_update  as in a Dantzig pass.
+//   k_pbox_step_se k_pbox_step; a pivot also reduces gamma_p = 1 + ||alpha||^2
+//                  in a fixed order, writes gamma_leave = max(gamma_p /
+//                  alpha_q^2, 1), and records the pending update with its own
+//                  copy of rho (rbuf is not kept across a reinversion): alpha_q,
+//                  gamma_p, the leaving column, pend = 1, need_tau = 1.  A flip,
+//                  an unbounded pass and an optimum clear pend; a pass cut off
+//                  by the limit leaves it for the next spx_iterate.
+//   k_pbox_tau + k_pbox_tau_sum   tau = alpha^T S, k_pbox_vtb's geometry and
+//                  summation order (a function of m alone) with v = the alpha
+//                  k_pbox_update wrote and no pending correction: after
+//                  k_pbox_update S is B^-1 before the pivot just committed.
+//                  Both return at once unless need_tau is set.
+// k_pbox_se_init: gamma_j = 1 + ||A_j||^2, one wave per column in the pricing
+// dots' summation order.  launch_pbox_price_se(apply = true) applies a pending
+// recurrence outside a pass (weight readback) whatever the status; the host
+// clears pend behind it with a stream-ordered memset.
+struct alignas(16) PboxSeRec {
+    int32_t pend;      // 1: gamma awaits the recurrence of the pivot recorded here
+    int32_t need_tau;  // 1: the last k_pbox_step_se made a pivot (k_pbox_tau runs)
+    int64_t leave;     // the pivot's leaving column
+    double aq;         // alpha_q
+    double gp;         // gamma_p = 1 + ||alpha||^2
+};
+
+struct PboxSeArgs {
+    PboxSeRec* se;
+    double* gamma;       // n
+    double* rho;         // L: row q of B^-1 before the pending pivot
+    double* tau;         // L: alpha^T B^-1, the same B^-1
+    double* tparts;      // vtb_blocks x L: k_pbox_tau's per-row-block partial vectors
+    int32_t vtb_blocks;
+    int32_t apply;       // 1: apply a pending recurrence only (ignores status and limit, no pricing)
+};
+
+struct PboxSeCfg {
+    int lds_vecs = 0;  // vectors of k_pbox_price_se staged in LDS: 0 none, 1 y (rho and tau from L2), 3 all
+    int price_grid = 0;
+    int init_grid = 0;
+};
+
+// lds_vecs_opt: -1 the default (3), else 0 / 1 / 3; lowered to 1, then 0, when the vectors do not fit, and 0
+// under global_y; price_grid as PboxCfg's
+hipError_t pbox_se_prepare(const Params& P, int cus, int price_grid, bool global_y, int lds_vecs_opt, PboxSeCfg* cfg);
+hipError_t launch_pbox_se_init(const Params& P, const PboxSeArgs& E, const PboxSeCfg& c, hipStream_t s);
+hipError_t launch_pbox_price_se(const Params& P, const PboxArgs& D, const PboxSeArgs& E, const PboxSeCfg& c, bool apply,
+                                hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_pbox_step_se(const Params& P, const PboxArgs& D, const PboxSeArgs& E, hipStream_t s);
+hipError_t launch_pbox_tau(const Params& P, const PboxSeArgs& E, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
+                           hipEvent_t e1);
 
 }  // namespace spx

@@ -1036,6 +1036,428 @@ __global__ __launch_bounds__(1024) void k_pbox_classify(Params P, PboxArgs D, Pb
 }
 
 // ---------------------------------------------------------------------------
+// Steepest edge (spx_pbox.h)
+// ---------------------------------------------------------------------------
+namespace {
+
+// a column's dots with y (and, PEND, with rho and tau) in k_pbox_price's order:
+// chunks ascending into two partial sums per lane and operand, one butterfly each
+template <bool PEND>
+__device__ __forceinline__ void se_dots(const dbl2* col, int nch, int lane, const dbl2* yv, const dbl2* rv,
+                                        const dbl2* tv, double& dy, double& dr, double& dt) {
+    constexpr int U = 8;
+    dbl2 cur[U], nxt[U];
+#pragma unroll
+    for (int t = 0; t < U; ++t) cur[t] = t < nch ? ld2<SPX_NT_A>(col + 64 * t) : dbl2{0.0, 0.0};
+    double d0 = 0.0, d1 = 0.0, r0 = 0.0, r1 = 0.0, t0 = 0.0, t1 = 0.0;
+    for (int c0 = 0; c0 < nch; c0 += U) {
+#pragma unroll
+        for (int t = 0; t < U; ++t)
+            nxt[t] = c0 + U + t < nch ? ld2<SPX_NT_A>(col + 64 * (c0 + U + t)) : dbl2{0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < U; ++t) {
+            if (c0 + t < nch) {
+                const int k = 64 * (c0 + t) + lane;
+                const dbl2 w = yv[k];
+                d0 = fma(cur[t].x, w.x, d0);
+                d1 = fma(cur[t].y, w.y, d1);
+                if constexpr (PEND) {
+                    const dbl2 r = rv[k], u = tv[k];
+                    r0 = fma(cur[t].x, r.x, r0);
+                    r1 = fma(cur[t].y, r.y, r1);
+                    t0 = fma(cur[t].x, u.x, t0);
+                    t1 = fma(cur[t].y, u.y, t1);
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < U; ++t) cur[t] = nxt[t];
+    }
+    dy = wave_sum(d0 + d1);
+    if constexpr (PEND) {
+        dr = wave_sum(r0 + r1);
+        dt = wave_sum(t0 + t1);
+    }
+}
+
+}  // namespace
+
+// NL: vectors staged in LDS -- 0 none, 1 y, 3 y, rho and tau (rho and tau only
+// while an update is pending).  The arithmetic does not depend on NL.
+template <int NL>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_price_se(Params P, PboxArgs D, PboxSeArgs E) {
+    constexpr int WAVES = PBOX_WAVES;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    const DevState* st = P.st;
+    const int32_t status = st->status;
+    const int32_t cnt = st->nb_count;
+    const int32_t y_buf = st->y_buf;
+    const int64_t iter = st->iter, limit = st->limit;
+    const bool pend = E.se->pend != 0;
+    const int64_t leave = E.se->leave;
+    const double aq = E.se->aq, gp = E.se->gp;
+    if (E.apply) {
+        if (!pend) return;
+    } else if (status != ST_RUNNING || iter >= limit) {
+        return;
+    }
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const dbl2* y_g = reinterpret_cast<const dbl2*>(y_buf ? P.y1 : P.y0);
+    const dbl2* r_g = reinterpret_cast<const dbl2*>(E.rho);
+    const dbl2* t_g = reinterpret_cast<const dbl2*>(E.tau);
+    if constexpr (NL >= 1) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) d[k] = y_g[k];
+        if (NL == 3 && pend) {
+            for (int64_t k = tid; k < L2; k += PBOX_BLOCK) {
+                d[L2 + k] = r_g[k];
+                d[2 * L2 + k] = t_g[k];
+            }
+        }
+        __syncthreads();
+    }
+    const dbl2* yv = NL >= 1 ? reinterpret_cast<const dbl2*>(dsm) : y_g;
+    const dbl2* rv = NL == 3 ? reinterpret_cast<const dbl2*>(dsm) + L2 : r_g;
+    const dbl2* tv = NL == 3 ? reinterpret_cast<const dbl2*>(dsm) + 2 * L2 : t_g;
+    const double* ys = reinterpret_cast<const double*>(yv);
+    const double* rs = reinterpret_cast<const double*>(rv);
+    const double* ts = reinterpret_cast<const double*>(tv);
+
+    double bkey = INFINITY, bd = 0.0;
+    int64_t bidx = INT64_MAX;
+    const int nwv = (int)gridDim.x * WAVES;
+    for (int s = (int)blockIdx.x * WAVES + wave; s < cnt; s += nwv) {
+        const int64_t j = P.nb_list[s];
+        const int up = D.at_upper[j];
+        double gam = E.gamma[j];
+        const double cj = P.c[j];
+        double dy, dr = 0.0, dt = 0.0;
+        if (P.slack_unit && j >= P.ns) {  // A_j = e_k: no stream
+            dy = ys[j - P.ns];
+            if (pend) {
+                dr = rs[j - P.ns];
+                dt = ts[j - P.ns];
+            }
+        } else {
+            const dbl2* col = reinterpret_cast<const dbl2*>(P.A + j * L) + lane;
+            if (pend) se_dots<true>(col, nch, lane, yv, rv, tv, dy, dr, dt);
+            else se_dots<false>(col, nch, lane, yv, rv, tv, dy, dr, dt);
+        }
+        if (pend && j != leave) {  // Goldfarb and Reid; the commit wrote the leaving column's weight
+            const double g = dr / aq;
+            const double gn = fma(g * g, gp, fma(-2.0 * g, dt, gam));
+            const double fl = fma(g, g, 1.0);
+            gam = gn > fl ? gn : fl;
+            if (lane == 0) E.gamma[j] = gam;  // one owner per column
+        }
+        if (E.apply) continue;
+        const double d = dy - cj;
+        const double sd = up ? -d : d;  // sigma_j d_j (a sign flip: exact)
+        const double key = -(d * d) / gam;
+        if (sd < -P.eps && argmin_better(key, j, bkey, bidx)) {
+            bkey = key;
+            bidx = j;
+            bd = d;
+        }
+    }
+    if (E.apply) return;
+    if (lane == 0) s_red[wave] = PboxPartial{bkey, bidx, bd, 0.0};
+    __syncthreads();
+    if (tid == 0) D.parts[blockIdx.x] = merge_price<WAVES>(s_red);  // read after the kernel boundary (k_pbox_update)
+}
+
+// gamma_j = 1 + ||A_j||^2 for every column, in se_dots' order
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_se_init(Params P, PboxSeArgs E) {
+    constexpr int WAVES = PBOX_WAVES;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const int64_t nwv = (int64_t)gridDim.x * WAVES;
+    for (int64_t j = (int64_t)blockIdx.x * WAVES + wave; j < P.n; j += nwv) {
+        double g;
+        if (P.slack_unit && j >= P.ns) {
+            g = 2.0;
+        } else {
+            const dbl2* col = reinterpret_cast<const dbl2*>(P.A + j * L) + lane;
+            double d0 = 0.0, d1 = 0.0;
+            for (int c = 0; c < nch; ++c) {
+                const dbl2 a = col[64 * c];
+                d0 = fma(a.x, a.x, d0);
+                d1 = fma(a.y, a.y, d1);
+            }
+            g = 1.0 + wave_sum(d0 + d1);
+        }
+        if (lane == 0) E.gamma[j] = g;
+    }
+}
+
+// k_pbox_step with the steepest-edge bookkeeping (spx_pbox.h)
+__global__ __launch_bounds__(1024) void k_pbox_step_se(Params P, PboxArgs D, PboxSeArgs E) {
+    constexpr int BLOCK = 1024, WAVES = BLOCK / 64, CH = 4;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t m = P.m, L = P.L;
+    __shared__ PboxSnap S;
+    __shared__ ArgMinEntry s_red[WAVES];
+    __shared__ ArgMinEntry s_win;
+    __shared__ double s_up;
+    __shared__ int32_t s_at;
+    __shared__ double s_gp[WAVES];
+    if (tid == 0) {
+        S.it = st->iter;
+        S.limit = st->limit;
+        S.status = st->status;
+        S.y_buf = st->y_buf;
+        S.cnt = st->nb_count;
+        S.fresh = D.rec->fresh;
+        S.p = D.rec->p;
+        S.d_p = D.rec->d_p;
+    }
+    __syncthreads();
+    const int64_t it = S.it;
+    if (S.status != ST_RUNNING || it >= S.limit || !S.fresh) {
+        if (tid == 0) {
+            E.se->need_tau = 0;
+            // the optimum was found by a pass whose pricing applied the pending recurrence
+            if (S.status == ST_OPTIMAL) E.se->pend = 0;
+        }
+        return;
+    }
+
+    double bv = INFINITY;
+    int64_t bi = INT64_MAX;
+    for (int g = tid; g < D.update_grid; g += BLOCK) {
+        const ArgMinEntry v = D.rparts[g];
+        if (argmin_better(v.val, v.idx, bv, bi)) {
+            bv = v.val;
+            bi = v.idx;
+        }
+    }
+    wave_argmin(bv, bi);
+    if (lane == 0) s_red[wave] = ArgMinEntry{bv, bi};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry t = s_red[0];
+        for (int w = 1; w < WAVES; ++w)
+            if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
+        s_win = t;
+        s_up = D.ub[S.p];
+        s_at = D.at_upper[S.p];
+    }
+    __syncthreads();
+    const double tq = s_win.val;
+    const bool none = s_win.idx == INT64_MAX;
+    const int64_t q = none ? 0 : (s_win.idx >> 1);
+    const int side = none ? 0 : (int)(s_win.idx & 1);
+    const int64_t p = S.p;
+    const double u_p = s_up;
+    const int up_p = s_at;
+    const double sg = up_p ? -1.0 : 1.0;
+    const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
+    double* a_cur = (it & 1) ? P.alpha1 : P.alpha0;
+    const bool flip = u_p < INFINITY && (none || u_p <= tq);
+
+    if (flip || none) {
+        if (flip) {
+            const double dx = up_p ? -u_p : u_p;
+            const double* Ap = P.A + p * L;
+            for (int64_t i = tid; i < m; i += BLOCK) {
+                P.x_b[i] = fma(-u_p, sg * al[i], P.x_b[i]);
+                D.b_eff[i] = fma(-dx, Ap[i], D.b_eff[i]);
+            }
+        }
+        for (int64_t i = tid; i < L; i += BLOCK) a_cur[i] = (i == 0) ? 1.0 : 0.0;
+        if (tid == 0) {
+            if (flip) {
+                D.at_upper[p] = up_p ? 0 : 1;
+                D.rec->flips += 1;
+            } else {
+                st->status = ST_UNBOUNDED;
+            }
+            st->q = 0;
+            st->aq = 1.0;
+            st->p = p;
+            st->min_e = S.d_p;
+            D.rec->fresh = 0;
+            E.se->pend = 0;  // (this pass's pricing applied it; a flip changes no weight)
+            E.se->need_tau = 0;
+        }
+        return;
+    }
+
+    // pivot it
+    double* y = S.y_buf ? P.y1 : P.y0;
+    const double aq = al[q];
+    const double theta = tq, sy = -(S.d_p / aq);
+    const double x_off = up_p ? u_p : 0.0;
+    const bool book = tid == BLOCK - 64;
+    int64_t leave = -1;
+    double c_p = 0.0;
+    int kp = -1, last = -1;
+    if (book) {
+        leave = P.b_ixs[q];
+        c_p = P.c[p];
+        kp = P.nb_pos[p];
+        last = P.nb_list[S.cnt - 1];
+    }
+    // ||alpha||^2: a thread's rows ascending, one butterfly, the waves in order
+    double a2 = 0.0;
+    for (int64_t i = tid; i < m; i += BLOCK) a2 = fma(al[i], al[i], a2);
+    a2 = wave_sum(a2);
+    if (lane == 0) s_gp[wave] = a2;
+    const double* Sq = P.B0 + q * L;
+    for (int64_t i0 = tid; i0 < L; i0 += (int64_t)CH * BLOCK) {
+        double xv[CH], av[CH], yv[CH], rv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            xv[u] = i < m ? P.x_b[i] : 0.0;
+            av[u] = i < m ? al[i] : 0.0;
+            yv[u] = i < L ? y[i] : 0.0;
+            rv[u] = i < L ? Sq[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            if (i < m) P.x_b[i] = (i == q) ? x_off + sg * theta : fma(-theta, sg * av[u], xv[u]);
+            if (i < L) {
+                y[i] = fma(sy, rv[u], yv[u]);
+                P.rbuf[i] = rv[u];
+                E.rho[i] = rv[u];  // the weight update's own copy
+            }
+        }
+    }
+    __syncthreads();
+    if (book) {
+        double t = s_gp[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) t += s_gp[w];
+        const double gp = 1.0 + t;
+        const double gl = gp / (aq * aq);
+        E.gamma[leave] = gl > 1.0 ? gl : 1.0;
+        E.se->aq = aq;
+        E.se->gp = gp;
+        E.se->leave = leave;
+        E.se->pend = 1;
+        E.se->need_tau = 1;
+        P.c_B[q] = c_p;
+        P.b_ixs[q] = p;
+        D.ub_B[q] = u_p;
+        D.at_upper[p] = 0;
+        D.at_upper[leave] = (int8_t)side;
+        int cnt = S.cnt;
+        P.nb_list[kp] = last;
+        P.nb_pos[last] = kp;
+        P.nb_pos[p] = -1;
+        --cnt;
+        P.nb_list[cnt] = (int32_t)leave;
+        P.nb_pos[leave] = cnt;
+        ++cnt;
+        st->nb_count = cnt;
+        st->aq = aq;
+        st->s_y = sy;
+        st->y_applied = it + 1;
+        st->xb_applied = it + 1;
+        st->p = p;
+        st->q = q;
+        st->min_e = S.d_p;
+        st->iter = it + 1;
+        record_pivot(P, it, p, q);
+        D.rec->fresh = 0;
+        if (side) D.rec->to_upper += 1;
+    }
+}
+
+// tau's per-row-block partial vectors: k_pbox_vtb with v = alpha[iter & 1] (the
+// alpha of the pivot k_pbox_step_se has just committed) and S read as it is
+__global__ __launch_bounds__(PBOX_VTB_BLOCK) void k_pbox_tau(Params P, PboxSeArgs E) {
+    constexpr int WAVES = PBOX_VTB_WAVES, U = 8;
+    __shared__ double s_v[PBOX_VTB_ROWS];
+    __shared__ int32_t s_row[PBOX_VTB_ROWS];
+    __shared__ int32_t s_n;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (!E.se->need_tau) return;  // (written by k_pbox_step_se alone: one value for the whole launch)
+    const double* v = (P.st->iter & 1) ? P.alpha1 : P.alpha0;
+    const int64_t m = P.m, L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const int64_t r0 = (int64_t)blockIdx.y * PBOX_VTB_ROWS;
+    if (wave == 0) {
+        const int64_t i = r0 + lane;
+        const double vi = i < m ? v[i] : 0.0;
+        const unsigned long long mask = __ballot(vi != 0.0);
+        const int pos = __popcll(mask & ((1ull << lane) - 1ull));
+        if (vi != 0.0) {
+            s_v[pos] = vi;
+            s_row[pos] = lane;
+        }
+        if (lane == 0) s_n = __popcll(mask);
+    }
+    __syncthreads();
+    const int c = (int)blockIdx.x * WAVES + wave;
+    if (c >= nch) return;
+    const int n = s_n;
+    const dbl2* base = reinterpret_cast<const dbl2*>(P.B0 + r0 * L) + 64 * c + lane;
+    dbl2 acc{0.0, 0.0};
+    dbl2 cur[U], nxt[U];
+#pragma unroll
+    for (int t = 0; t < U; ++t) cur[t] = t < n ? ld2<SPX_NT_BLOAD>(base + (int64_t)s_row[t] * L2) : dbl2{0.0, 0.0};
+    for (int k0 = 0; k0 < n; k0 += U) {
+#pragma unroll
+        for (int t = 0; t < U; ++t)
+            nxt[t] = k0 + U + t < n ? ld2<SPX_NT_BLOAD>(base + (int64_t)s_row[k0 + U + t] * L2) : dbl2{0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < U; ++t) {
+            if (k0 + t < n) {
+                const double vv = s_v[k0 + t];
+                acc.x = fma(vv, cur[t].x, acc.x);
+                acc.y = fma(vv, cur[t].y, acc.y);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < U; ++t) cur[t] = nxt[t];
+    }
+    reinterpret_cast<dbl2*>(E.tparts + (int64_t)blockIdx.y * L)[64 * c + lane] = acc;  // read after the kernel boundary
+}
+
+// k_pbox_vtb_sum's order, into tau
+__global__ __launch_bounds__(PBOX_VTB_BLOCK) void k_pbox_tau_sum(Params P, PboxSeArgs E) {
+    constexpr int WAVES = PBOX_VTB_WAVES;
+    __shared__ dbl2 s_acc[WAVES][64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (!E.se->need_tau) return;
+    const int64_t L2 = P.L >> 1;
+    const int64_t k = (int64_t)blockIdx.x * 64 + lane;
+    const int nb = E.vtb_blocks, per = (nb + WAVES - 1) / WAVES;
+    const int b0 = wave * per, b1 = b0 + per < nb ? b0 + per : nb;
+    const dbl2* parts = reinterpret_cast<const dbl2*>(E.tparts) + k;
+    dbl2 acc{0.0, 0.0};
+#pragma unroll 4
+    for (int b = b0; b < b1; ++b) {
+        const dbl2 t = parts[(int64_t)b * L2];
+        acc.x += t.x;
+        acc.y += t.y;
+    }
+    s_acc[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0) {
+        dbl2 r = s_acc[0][lane];
+#pragma unroll
+        for (int g = 1; g < WAVES; ++g) {
+            r.x += s_acc[g][lane].x;
+            r.y += s_acc[g][lane].y;
+        }
+        reinterpret_cast<dbl2*>(E.tau)[k] = r;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------
 namespace {
@@ -1163,6 +1585,85 @@ hipError_t launch_pbox_step1(const Params& P, const PboxArgs& D, const Pbox1Args
 
 hipError_t launch_pbox_classify(const Params& P, const PboxArgs& D, const Pbox1Args& X, bool entry, hipStream_t s) {
     hipLaunchKernelGGL(k_pbox_classify, dim3(1), dim3(1024), 0, s, P, D, X, entry ? 1 : 0);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <typename K>
+hipError_t launch_timed_se(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
+                           const Params& P, const PboxArgs& D, const PboxSeArgs& E) {
+    if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), (uint32_t)lds, s, e0, e1, 0, P, D, E);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), lds, s, P, D, E);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t pbox_se_prepare(const Params& P, int cus, int price_grid, bool global_y, int lds_vecs_opt, PboxSeCfg* cfg) {
+    const size_t vec = (size_t)P.L * 8;
+    int nl = lds_vecs_opt < 0 ? 3 : lds_vecs_opt;  // the default: all three in LDS where they fit
+    if (global_y) nl = 0;
+    if (nl == 3 && 3 * vec > PBOX_LDS_CAP) nl = 1;
+    if (nl >= 1 && vec > PBOX_LDS_CAP) nl = 0;
+    nl = nl >= 3 ? 3 : (nl >= 1 ? 1 : 0);
+    cfg->lds_vecs = nl;
+    hipError_t e = hipSuccess;
+    if (nl == 3) e = set_lds(k_pbox_price_se<3>, 3 * vec);
+    else if (nl == 1) e = set_lds(k_pbox_price_se<1>, vec);
+    if (e != hipSuccess) return e;
+    int per_cu = 0;
+    if (nl == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pbox_price_se<3>, PBOX_BLOCK, 3 * vec);
+    else if (nl == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pbox_price_se<1>, PBOX_BLOCK, vec);
+    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pbox_price_se<0>, PBOX_BLOCK, 0);
+    if (e != hipSuccess) return e;
+    if (per_cu < 1) per_cu = 1;
+    const int64_t cols = P.n - P.m;
+    const int64_t want = (cols + PBOX_WAVES - 1) / PBOX_WAVES;
+    const int64_t cap = (int64_t)cus * per_cu;
+    int64_t g = want < cap ? want : cap;
+    if (g < 1) g = 1;
+    // (the partials live in PboxArgs::parts, sized for price_grid: never more workgroups than that)
+    cfg->price_grid = g < price_grid ? (int)g : price_grid;
+    const int64_t wi = (P.n + PBOX_WAVES - 1) / PBOX_WAVES;
+    const int64_t ci = (int64_t)cus * 4;
+    cfg->init_grid = (int)(wi < ci ? wi : ci);
+    if (cfg->init_grid < 1) cfg->init_grid = 1;
+    return hipSuccess;
+}
+
+hipError_t launch_pbox_se_init(const Params& P, const PboxSeArgs& E, const PboxSeCfg& c, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_se_init, dim3(c.init_grid), dim3(PBOX_BLOCK), 0, s, P, E);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_price_se(const Params& P, const PboxArgs& D, const PboxSeArgs& E, const PboxSeCfg& c, bool apply,
+                                hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    PboxSeArgs a = E;
+    a.apply = apply ? 1 : 0;
+    const size_t vec = (size_t)P.L * 8;
+    if (c.lds_vecs == 3) return launch_timed_se(k_pbox_price_se<3>, c.price_grid, 3 * vec, s, e0, e1, P, D, a);
+    if (c.lds_vecs == 1) return launch_timed_se(k_pbox_price_se<1>, c.price_grid, vec, s, e0, e1, P, D, a);
+    return launch_timed_se(k_pbox_price_se<0>, c.price_grid, 0, s, e0, e1, P, D, a);
+}
+
+hipError_t launch_pbox_step_se(const Params& P, const PboxArgs& D, const PboxSeArgs& E, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_step_se, dim3(1), dim3(1024), 0, s, P, D, E);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_tau(const Params& P, const PboxSeArgs& E, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
+                           hipEvent_t e1) {
+    if (e0) {
+        const hipError_t e = hipEventRecord(e0, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_pbox_tau, dim3(c.vtb_grid_x, c.vtb_blocks), dim3(PBOX_VTB_BLOCK), 0, s, P, E);
+    hipLaunchKernelGGL(k_pbox_tau_sum, dim3(c.vsum_grid), dim3(PBOX_VTB_BLOCK), 0, s, P, E);
+    if (e1) {
+        const hipError_t e = hipEventRecord(e1, s);
+        if (e != hipSuccess) return e;
+    }
     return hipGetLastError();
 }
 

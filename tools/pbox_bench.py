@@ -43,9 +43,24 @@ the pricing and the update kernel over the phase-1 passes, and k_pbox_vtb's
 algorithmic bandwidth 8 L x (rows with w_i != 0, the mean of before and after)
 / time beside the update kernel's 16 m L / time, both against 8 TB/s.
 
+--primal-pricing steepest measures exact steepest-edge pricing
+against the Dantzig loop instead, one child per side, the sides alternating:
+  pbox          as above (Dantzig): k_pbox_price
+  pbox_se       the same LP under SPX_PRIMAL_PRICING_STEEPEST: k_pbox_price_se, and
+                tau_us, the mean of k_pbox_tau + k_pbox_tau_sum over the pivot passes
+  pbox_se_lds1 / pbox_se_lds0   the LDS layouts that are not the default (y alone in
+                LDS with rho and tau from L2; nothing in LDS), through the
+                SPX_PBOX_SE_LDS experiment switch
+  pbox_again, pbox_se_again
+and, with --solve, whole solves (the --solve mode above) at every --solve-shape
+under both rules, Dantzig / steepest / Dantzig / steepest, with the ratios of
+pivots and seconds.
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
     python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
+    python tools/pbox_bench.py --primal-pricing steepest [--solve --solve-shape 1024 4096 4
+                               --solve-shape 2048 8192 5] [--out profiles/pbox_se_c3.json]
 """
 import argparse
 import json
@@ -123,6 +138,47 @@ def run_pbox(a):
     del A
     return measure(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
                                               timing=timing), a.k, a.warm, flips=True)
+
+
+def run_pbox_se(a):
+    """The Dantzig side's LP under steepest edge; the tau step's mean time from the timing context."""
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = primal_box_ref.boxed_primal(a.m, a.n, a.seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    tau = {}
+
+    class Timed:  # (measure() reads kernel_times() itself: the tau events are read around it)
+        def __init__(self, timing):
+            self.ctx = spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u, timing=timing,
+                                   primal_pricing=spx.PRIMAL_PRICING_STEEPEST)
+            self.timing = timing
+
+        def __enter__(self):
+            self.ctx.__enter__()
+            return self
+
+        def __exit__(self, *exc):
+            if self.timing:
+                ms, launches = self.last
+                tau.update({"tau_us": round(1e3 * ms / max(launches, 1), 2), "tau_launches": launches})
+            return self.ctx.__exit__(*exc)
+
+        def kernel_times(self):
+            self.last = self.ctx.vtb_times()  # (read and reset with the kernel times: the last read is the timed block)
+            return self.ctx.kernel_times()
+
+        def __getattr__(self, name):
+            return getattr(self.ctx, name)
+
+    res = measure(Timed, a.k, a.warm, flips=True)
+    res.update(tau)
+    res["se_lds"] = os.environ.get("SPX_PBOX_SE_LDS", "default")
+    return res
 
 
 def run_pbox_flag(a):
@@ -306,10 +362,11 @@ def run_solve(a):
     import simplex_method_gpu_amd as spx
 
     out = []
+    rule = spx.PRIMAL_PRICING_STEEPEST if a.primal_pricing == "steepest" else spx.PRIMAL_PRICING_DANTZIG
     for (m, n, seed) in [tuple(s) for s in a.solve_shape]:
         A, b, c, u = primal_box_ref.boxed_primal(m, n, seed)
         with spx.Context(np.ascontiguousarray(A.T), b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
-                         refactor_every=a.refactor) as ctx:
+                         refactor_every=a.refactor, primal_pricing=rule) as ctx:
             ctx.iterate(20)  # (first-launch costs)
             ctx.reset()
             t0 = time.perf_counter()
@@ -317,7 +374,8 @@ def run_solve(a):
             dt = time.perf_counter() - t0
             x, up = ctx.primal()
             fl = ctx.primal_flips()
-        rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "status": int(r.status),
+        rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "primal_pricing": a.primal_pricing,
+               "status": int(r.status),
                "pivots": r.pivots, "z": r.z, "seconds": round(dt, 4), "it_per_s": round(r.pivots / dt, 1),
                "flip_passes": fl[0], "to_upper": fl[1], "at_upper": int(up.sum())}
         if int(r.status) == 1:
@@ -340,15 +398,18 @@ def run_solve(a):
     return out
 
 
-def child(a, role):
-    cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--m", str(a.m), "--n", str(a.n),
+def child(a, role, pricing="dantzig", se_lds=None):
+    env = dict(os.environ)
+    if se_lds is not None:
+        env["SPX_PBOX_SE_LDS"] = str(se_lds)
+    cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--primal-pricing", pricing, "--m", str(a.m), "--n", str(a.n),
            "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--refactor", str(a.refactor),
            "--sparse-every", str(a.sparse_every), "--sparse-chunk", str(a.sparse_chunk)]
     if a.rows:
         cmd.append("--rows")
     for shape in a.solve_shape:
         cmd += ["--solve-shape"] + [str(v) for v in shape]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     if out.returncode != 0:
         sys.stderr.write(out.stdout + out.stderr)
         raise SystemExit(f"{role} run failed ({out.returncode})")
@@ -370,17 +431,43 @@ def main():
     ap.add_argument("--phase1", action="store_true", help="the phase-1 sides instead (DESIGN.md 7f)")
     ap.add_argument("--sparse-every", type=int, default=100, help="p1_sparse: every this many rows one starts violated")
     ap.add_argument("--sparse-chunk", type=int, default=10, help="p1_sparse: pivots per timed chunk")
+    ap.add_argument("--primal-pricing", default="dantzig", choices=["dantzig", "steepest"],
+                    help="steepest: the steepest-edge sides against the Dantzig loop instead (DESIGN.md 7h)")
     ap.add_argument("--role", default=None,
-                    choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse"])
+                    choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se"])
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
         run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
-               "pbox_flag": run_pbox_flag, "p1_dense": run_p1_dense, "p1_sparse": run_p1_sparse}[a.role]
+               "pbox_flag": run_pbox_flag, "p1_dense": run_p1_dense, "p1_sparse": run_p1_sparse,
+               "pbox_se": run_pbox_se}[a.role]
         print(json.dumps(run(a)), flush=True)
         return
     if a.k < 252:
         ap.error("--k: at least 252 timed pivots")
     res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "seed": a.seed}
+    if a.primal_pricing == "steepest":
+        for key, role, lds in (("pbox", "pbox", None), ("pbox_se", "pbox_se", None), ("pbox_se_lds1", "pbox_se", 1),
+                               ("pbox_se_lds0", "pbox_se", 0), ("pbox_again", "pbox", None),
+                               ("pbox_se_again", "pbox_se", None)):
+            res[key] = child(a, role, "steepest" if role == "pbox_se" else "dantzig", lds)
+            sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+            sys.stderr.flush()
+        d, q = res["pbox"], res["pbox_se"]
+        res["se_over_dantzig"] = {k: round(q[k] / d[k], 3) for k in ("price_us", "update_us", "it_per_s")}
+        if a.solve and a.solve_shape:
+            runs = [child(a, "solve", rule) for rule in ("dantzig", "steepest", "dantzig", "steepest")]
+            res["solve"] = []
+            for i in range(len(a.solve_shape)):
+                dz, se = runs[0][i], runs[1][i]
+                res["solve"].append({"dantzig": dz, "steepest": se, "dantzig_again": runs[2][i],
+                                     "steepest_again": runs[3][i],
+                                     "pivot_ratio": round(dz["pivots"] / se["pivots"], 2),
+                                     "time_ratio": round(dz["seconds"] / se["seconds"], 2)})
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
     if a.phase1:
         res.update({"sparse_every": a.sparse_every, "sparse_chunk": a.sparse_chunk})
         for key, role in (("pbox", "pbox"), ("pbox_flag", "pbox_flag"), ("p1_dense", "p1_dense"),
