@@ -247,9 +247,12 @@ typedef struct spx_opts {
  *           g^2), and the leaving column gamma = max(gamma_p / alpha_q^2, 1)
  *           (Goldfarb and Reid's update; no reset rule).  Where no pass has
  *           kept them (spx_create, spx_reset, spx_set_basis, spx_set_algorithm
- *           into the loop, a change of rule) the weights restart at 1 +
- *           ||A_j||^2: exact at the slack basis, a reference framework and not
- *           the exact norm for a warm basis.  spx_reinvert, refactor_every,
+ *           into the loop, a change of rule) the weights restart: at the
+ *           slack basis (spx_create, spx_reset) always at 1 + ||A_j||^2, which is
+ *           exact there; for a warm basis as SPX_PRIMAL_WEIGHTS_* says (below:
+ *           1 + ||A_j||^2 again, a reference framework and not the exact norm, or
+ *           the exact 1 + ||B^-1 A_j||^2 formed on the device).  Dantzig passes
+ *           in between keep no weights either.  spx_reinvert, refactor_every,
  *           spx_set_cost, spx_set_rhs and spx_set_bounds keep the basis and the
  *           weights.  Not together with phase 1 (SPX_FLAG_PRIMAL_PHASE1 /
  *           spx_set_primal_phase1): spx_create refuses the two flags with
@@ -257,6 +260,22 @@ typedef struct spx_opts {
  *           SPX_ERR_STATE. */
 #define SPX_PRIMAL_PRICING_DANTZIG  0
 #define SPX_PRIMAL_PRICING_STEEPEST 1
+
+/* How the steepest-edge weights of the bounded primal loop restart for a warm
+ * basis, i.e. wherever no pass has kept them and the basis is not the slack
+ * basis (SPX_FLAG_PRIMAL_EXACT_WEIGHTS at spx_create, spx_set_primal_weight_init
+ * later).  Inert under SPX_PRIMAL_PRICING_DANTZIG and under the
+ * other algorithms.
+ * REFERENCE: gamma_j = 1 + ||A_j||^2, a reference framework (the default).
+ * EXACT:     gamma_j = 1 + ||B^-1 A_j||^2 of every non-basic column, from the
+ *            B^-1 spx_get_state would return: one fp64 matrix product on the
+ *            device whose result is kept as column norms only.  Its tiling and
+ *            summation order depend on m and n alone, so the weights are the
+ *            same bits from run to run and under every tuning option.  From the
+ *            slack basis both modes start from the same weights and walk the
+ *            same passes. */
+#define SPX_PRIMAL_WEIGHTS_REFERENCE 0
+#define SPX_PRIMAL_WEIGHTS_EXACT     1
 
 /* Ratio tests of the dual loop's boxed passes (SPX_FLAG_DUAL_LONG_STEP at
  * spx_create, spx_set_dual_ratio later).
@@ -394,6 +413,13 @@ typedef struct spx_opts {
                                          DANTZIG); accepted and inert under the other
                                          algorithms; SPX_ERR_ARG together with
                                          SPX_FLAG_PRIMAL_PHASE1                       */
+
+#define SPX_FLAG_PRIMAL_EXACT_WEIGHTS 32768 /* the bounded primal loop restarts its
+                                         steepest-edge weights for a warm basis at
+                                         the exact norms (SPX_PRIMAL_WEIGHTS_EXACT;
+                                         default REFERENCE); accepted and inert under
+                                         SPX_PRIMAL_PRICING_DANTZIG and the other
+                                         algorithms                                  */
 
 void spx_default_opts(spx_opts* opts);
 
@@ -549,6 +575,19 @@ int spx_set_primal_pricing(spx_ctx* ctx, int32_t rule);
  * under SPX_PRIMAL_PRICING_DANTZIG or outside SPX_ALGO_PRIMAL_BOX. */
 int spx_get_primal_weights(spx_ctx* ctx, double* w /* n */);
 
+/* How the bounded primal loop's steepest-edge weights restart for a warm basis
+ * (SPX_PRIMAL_WEIGHTS_*), between any two calls and under any algorithm; takes
+ * effect with the next restart and marks nothing stale.  SPX_ERR_ARG for NULL or
+ * an unknown mode. */
+int spx_set_primal_weight_init(spx_ctx* ctx, int32_t mode);
+
+/* Recomputes the steepest-edge weights of the current basis exactly now (the
+ * kernels of SPX_PRIMAL_WEIGHTS_EXACT), in either mode and at any basis.  A
+ * recurrence still pending from the last pivot is dropped, not applied.  The
+ * basis, x_b, y, the pivot count and the status are kept.  SPX_ERR_STATE under
+ * SPX_PRIMAL_PRICING_DANTZIG or outside SPX_ALGO_PRIMAL_BOX. */
+int spx_refresh_primal_weights(spx_ctx* ctx);
+
 /* Phase-1 counters of the bounded primal loop, kept on the device by the kernel
  * that commits the pass: out[0] phase-1 passes since spx_create or spx_reset
  * (flip passes included), out[1] phase-1 pivots, out[2] rows out of their
@@ -633,6 +672,12 @@ int spx_kernel_times(spx_ctx* ctx, double* price_ms, int64_t* price_launches,
  * SPX_PRIMAL_PRICING_STEEPEST the same counters carry the tau = alpha^T B^-1
  * step of every pass (a pass without a pivot with its near-zero time). */
 int spx_pbox_vtb_times(spx_ctx* ctx, double* ms, int64_t* launches);
+
+/* With SPX_FLAG_TIMING: total device milliseconds and count of the exact weight
+ * recomputations (SPX_PRIMAL_WEIGHTS_EXACT restarts and
+ * spx_refresh_primal_weights; B^-1 brought current, the product, the slack
+ * norms and the sum) since the last call (resets). */
+int spx_pbox_wexact_times(spx_ctx* ctx, double* ms, int64_t* launches);
 
 /* With SPX_FLAG_TIMING: device milliseconds summed since the last call (resets)
  * of out[0] the pricing kernel, out[1] pricing + the cross-rank MINLOC

@@ -28,7 +28,8 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "PRICING_DANTZIG", "PRICING_DEVEX", "PRICING_STEEPEST", "ALGO_PRIMAL", "ALGO_DUAL",
            "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST",
            "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX",
-           "FLAG_PRIMAL_PHASE1", "PRIMAL_PRICING_DANTZIG", "PRIMAL_PRICING_STEEPEST", "FLAG_PRIMAL_STEEPEST"]
+           "FLAG_PRIMAL_PHASE1", "PRIMAL_PRICING_DANTZIG", "PRIMAL_PRICING_STEEPEST", "FLAG_PRIMAL_STEEPEST",
+           "PRIMAL_WEIGHTS_REFERENCE", "PRIMAL_WEIGHTS_EXACT", "FLAG_PRIMAL_EXACT_WEIGHTS"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -63,6 +64,10 @@ FLAG_PRIMAL_PHASE1 = 8192  # the bounded primal loop starts with its phase 1 on 
 # entering rules of the bounded primal loop (include/simplex.h SPX_PRIMAL_PRICING_*)
 PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST = 0, 1
 FLAG_PRIMAL_STEEPEST = 16384  # the bounded primal loop starts with exact steepest-edge pricing (default: Dantzig)
+# how the bounded primal loop's steepest-edge weights restart for a warm basis (include/simplex.h
+# SPX_PRIMAL_WEIGHTS_*): the reference framework 1 + ||A_j||^2, or the exact 1 + ||B^-1 A_j||^2
+PRIMAL_WEIGHTS_REFERENCE, PRIMAL_WEIGHTS_EXACT = 0, 1
+FLAG_PRIMAL_EXACT_WEIGHTS = 32768  # the steepest-edge weights of a warm basis restart at the exact norms
 
 
 class SolveStatus(IntEnum):
@@ -179,7 +184,8 @@ class Context:
                  price_tail: bool = False, algorithm: int = ALGO_PRIMAL,
                  dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None,
                  dual_ratio: int = DUAL_RATIO_TEXTBOOK, primal_phase1: bool = False,
-                 primal_pricing: int = PRIMAL_PRICING_DANTZIG):
+                 primal_pricing: int = PRIMAL_PRICING_DANTZIG,
+                 primal_weights: int = PRIMAL_WEIGHTS_REFERENCE):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -202,6 +208,9 @@ class Context:
         if primal_pricing not in (PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST):
             raise ValueError("primal_pricing must be PRIMAL_PRICING_DANTZIG or PRIMAL_PRICING_STEEPEST")
         self._primal_pricing = primal_pricing
+        if primal_weights not in (PRIMAL_WEIGHTS_REFERENCE, PRIMAL_WEIGHTS_EXACT):
+            raise ValueError("primal_weights must be PRIMAL_WEIGHTS_REFERENCE or PRIMAL_WEIGHTS_EXACT")
+        self._primal_weights = primal_weights
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
@@ -211,7 +220,8 @@ class Context:
                    | (FLAG_DUAL_STEEPEST if dual_pricing == DUAL_PRICING_STEEPEST else 0)
                    | (FLAG_DUAL_LONG_STEP if dual_ratio == DUAL_RATIO_LONG_STEP else 0)
                    | (FLAG_PRIMAL_PHASE1 if primal_phase1 else 0)
-                   | (FLAG_PRIMAL_STEEPEST if primal_pricing == PRIMAL_PRICING_STEEPEST else 0))
+                   | (FLAG_PRIMAL_STEEPEST if primal_pricing == PRIMAL_PRICING_STEEPEST else 0)
+                   | (FLAG_PRIMAL_EXACT_WEIGHTS if primal_weights == PRIMAL_WEIGHTS_EXACT else 0))
         h = ctypes.c_void_p()
         if A_cols is not None:
             A_cols = np.ascontiguousarray(A_cols, dtype=np.float64)
@@ -384,6 +394,18 @@ class Context:
         check(self._L.spx_get_primal_weights(self._h, _ptr(w)))
         return w
 
+    def set_primal_weight_init(self, mode: int):
+        """How the steepest-edge weights of the bounded primal loop restart for a
+        warm basis from the next restart on (spx_set_primal_weight_init):
+        PRIMAL_WEIGHTS_REFERENCE / PRIMAL_WEIGHTS_EXACT."""
+        check(self._L.spx_set_primal_weight_init(self._h, mode))
+        self._primal_weights = mode
+
+    def refresh_primal_weights(self):
+        """Recompute the steepest-edge weights of the current basis exactly now
+        (spx_refresh_primal_weights); a pending recurrence is dropped."""
+        check(self._L.spx_refresh_primal_weights(self._h))
+
     def primal_phase1(self):
         """(phase-1 passes, phase-1 pivots, rows out of their bounds at the last
         entry check, rows out of their bounds now) of the bounded primal loop
@@ -503,6 +525,13 @@ class Context:
         check(self._L.spx_pbox_vtb_times(self._h, ctypes.byref(ms), ctypes.byref(k)))
         return ms.value, k.value
 
+    def wexact_times(self):
+        """(milliseconds, launches) of the exact weight recomputations since the
+        last call (timing=True; spx_pbox_wexact_times)."""
+        ms, k = ctypes.c_double(), ctypes.c_int64()
+        check(self._L.spx_pbox_wexact_times(self._h, ctypes.byref(ms), ctypes.byref(k)))
+        return ms.value, k.value
+
     def wg_times(self):
         """Per-pass clocks of the last two compact window passes (stamps=True,
         spx_wg_times), 100 MHz ticks, indexed by pass parity (iteration & 1):
@@ -604,6 +633,7 @@ class Context:
         cfg["dual_pricing"] = self._dual_pricing  # (the library keeps it outside spx_config)
         cfg["primal_pricing"] = self._primal_pricing
         cfg["dual_ratio"] = self._dual_ratio
+        cfg["primal_weights"] = self._primal_weights
         return cfg
 
 

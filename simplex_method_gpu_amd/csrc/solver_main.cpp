@@ -47,6 +47,12 @@
 //                  (exact steepest edge, SPX_PRIMAL_PRICING_STEEPEST); without
 //                  --primal-box it is refused with the usage message (exit 1);
 //                  not with --phase1 (the library's refusal is printed)
+//   --primal-weights W  how the steepest-edge weights of --primal-box restart
+//                  for a warm basis: reference (default) | exact
+//                  (SPX_FLAG_PRIMAL_EXACT_WEIGHTS); shown in --json.  The CLI
+//                  starts from the slack basis, where both modes walk the same
+//                  passes; an unknown word is refused by name (exit 1), and so
+//                  is the option without --primal-box
 //   --bounds F     upper bounds 0 <= x_j <= u_j of all n columns for --dual or
 //                  --primal-box (spx_set_bounds): F holds n whitespace-separated
 //                  values, "inf" = none; without either the library's refusal is
@@ -95,7 +101,7 @@ static void print_elapsed_time(const char* msg, double dur) {
 static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
-                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest]]"
+                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--primal-weights reference|exact]]"
                  " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
@@ -117,6 +123,7 @@ int main(int argc, char* argv[]) {
     int64_t refactor = 0;
     bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false, primal_box = false, phase1 = false;
     bool primal_pricing_given = false, primal_steepest = false;
+    bool primal_weights_given = false, primal_exact = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -167,6 +174,16 @@ int main(int argc, char* argv[]) {
             primal_pricing_given = true;
             primal_steepest = r == "steepest";
         }
+        else if (s == "--primal-weights") {
+            need(1);
+            const std::string r = argv[++a];
+            if (r != "reference" && r != "exact") {
+                std::cerr << "--primal-weights " << r << ": reference or exact\n";
+                return 1;
+            }
+            primal_weights_given = true;
+            primal_exact = r == "exact";
+        }
         else if (s == "--dual-ratio") {
             need(1);
             const std::string r = argv[++a];
@@ -204,6 +221,10 @@ int main(int argc, char* argv[]) {
     if (primal_pricing_given && !primal_box) {
         std::cerr << "--primal-pricing needs --primal-box: it is the bounded primal loop's entering rule\n";
         usage();
+        return 1;
+    }
+    if (primal_weights_given && !primal_box) {
+        std::cerr << "--primal-weights needs --primal-box: it is the bounded primal loop's weight start\n";
         return 1;
     }
     if (primal_box) {
@@ -268,6 +289,7 @@ int main(int argc, char* argv[]) {
     if (dual_long) o.flags |= SPX_FLAG_DUAL_LONG_STEP;
     if (phase1) o.flags |= SPX_FLAG_PRIMAL_PHASE1;
     if (primal_steepest) o.flags |= SPX_FLAG_PRIMAL_STEEPEST;
+    if (primal_exact) o.flags |= SPX_FLAG_PRIMAL_EXACT_WEIGHTS;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)
@@ -405,7 +427,8 @@ int main(int argc, char* argv[]) {
             std::cout << ", \"dual_ratio\": \"" << (dual_long ? "long" : "textbook") << "\", \"flips\": " << flips[0]
                       << ", \"flip_passes\": " << flips[1] << ", \"max_flips\": " << flips[2];
         if (primal_box)
-            std::cout << ", \"flip_passes\": " << pflips[0] << ", \"to_upper\": " << pflips[1];
+            std::cout << ", \"flip_passes\": " << pflips[0] << ", \"to_upper\": " << pflips[1]
+                      << ", \"primal_weights\": \"" << (primal_exact ? "exact" : "reference") << "\"";
         if (phase1)
             std::cout << ", \"phase1_passes\": " << ph1[0] << ", \"phase1_pivots\": " << ph1[1]
                       << ", \"phase1_rows\": " << ph1[2];

@@ -1329,6 +1329,7 @@ void spx_destroy(spx_ctx* x) {
     for (hipEvent_t e : x->ev_loop) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_fold) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->pbox.ev_vtb) (void)hipEventDestroy(e);
+    for (hipEvent_t e : x->pbox.ev_wx) (void)hipEventDestroy(e);
     if (x->comm) (void)ncclCommDestroy(x->comm);
     for (void* p : x->mbox_opened) (void)hipIpcCloseMemHandle(p);
     for (void* p : x->allocs) (void)hipFree(p);
@@ -1475,6 +1476,7 @@ int spx_set_basis(spx_ctx* x, const int64_t* basis) {
     if (x->P.row_shard) return fail(SPX_ERR_STATE, "spx_set_basis needs replicated B^-1 (no row sharding)");
     dual_on_new_basis(x);
     pbox_weights_lost(x);
+    pbox_basis_set(x);
     // this rank's non-basic list (ascending, owned columns only) and positions
     std::vector<char> basic((size_t)x->n, 0);
     for (int64_t k = 0; k < x->m; ++k) basic[(size_t)basis[k]] = 1;

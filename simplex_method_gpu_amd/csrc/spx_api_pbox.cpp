@@ -111,13 +111,57 @@ int pbox_se_setup(spx_ctx* x) {
     return SPX_OK;
 }
 
-// weights nobody kept: gamma_j = 1 + ||A_j||^2 (exact at the slack basis, a
-// reference framework elsewhere) and nothing pending
+// the exact-weight buffers and geometry, on first use (after pbox_se_setup)
+int pbox_wexact_setup(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    if (s.wx.parts) return SPX_OK;
+    s.wxcfg = pbox_wexact_geometry(x->m, x->n, x->L);
+    HIP_TRY(pbox_wexact_prepare());
+    SPX_TRY(x->alloc(&s.wx_S, (size_t)x->m * (size_t)x->L));
+    SPX_TRY(x->alloc(&s.wx.sparts, s.wxcfg.sparts));
+    SPX_TRY(x->alloc(&s.wx.parts, s.wxcfg.parts));
+    s.wx.S = s.wx_S;
+    s.wx.gamma = s.se.gamma;
+    s.wx.cap = s.wxcfg.cap;
+    s.wx.row_blocks = s.wxcfg.row_blocks;
+    return SPX_OK;
+}
+
+// gamma_j = 1 + ||B^-1 A_j||^2 for the non-basic columns of the current basis:
+// B^-1 brought current into wx_S (the pending pivot applied, as spx_get_state
+// does; the loop's own S and its pending record are left alone), then the
+// product, the slack norms and the sum
+int pbox_wexact_run(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    SPX_TRY(pbox_wexact_setup(x));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (x->timing) {
+        while (s.ev_wx.size() < 2 * (s.n_wx + 1)) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            s.ev_wx.push_back(e);
+        }
+        e0 = s.ev_wx[2 * s.n_wx];
+        e1 = s.ev_wx[2 * s.n_wx + 1];
+        ++s.n_wx;
+        HIP_TRY(hipEventRecord(e0, x->stream));
+    }
+    HIP_TRY(launch_materialize(x->P, s.wx_S, x->stream));
+    HIP_TRY(launch_pbox_wexact(x->P, s.wx, s.wxcfg, x->stream));
+    if (e1) HIP_TRY(hipEventRecord(e1, x->stream));
+    return SPX_OK;
+}
+
+// weights nobody kept, and nothing pending: gamma_j = 1 + ||A_j||^2 (exact at
+// the slack basis, a reference framework elsewhere), or under
+// SPX_PRIMAL_WEIGHTS_EXACT for a warm basis the exact norms
 int pbox_se_restart(spx_ctx* x) {
     PboxState& s = x->pbox;
     if (!s.se_stale) return SPX_OK;
     HIP_TRY(hipMemsetAsync(s.se.se, 0, sizeof(PboxSeRec), x->stream));
-    HIP_TRY(launch_pbox_se_init(x->P, s.se, s.secfg, x->stream));
+    const bool slack_basis = !s.warm && x->pivots == 0;
+    if (s.winit == SPX_PRIMAL_WEIGHTS_EXACT && !slack_basis) SPX_TRY(pbox_wexact_run(x));
+    else HIP_TRY(launch_pbox_se_init(x->P, s.se, s.secfg, x->stream));
     s.se_stale = false;
     return SPX_OK;
 }
@@ -224,16 +268,20 @@ int pbox_on_reset(spx_ctx* x) {
     x->pbox.y_dirty = false;
     x->pbox.ninf = x->pbox.y_stale = 0;
     x->pbox.se_stale = true;
+    x->pbox.warm = false;  // the slack basis again
     return SPX_OK;
 }
 
 void pbox_weights_lost(spx_ctx* x) { x->pbox.se_stale = true; }
+
+void pbox_basis_set(spx_ctx* x) { x->pbox.warm = true; }
 
 void pbox_on_change(spx_ctx* x) { x->pbox.checked = false; }
 
 int pbox_on_create(spx_ctx* x) {
     x->pbox.phase1 = (x->opts.flags & SPX_FLAG_PRIMAL_PHASE1) != 0;
     x->pbox.rule = (x->opts.flags & SPX_FLAG_PRIMAL_STEEPEST) ? SPX_PRIMAL_PRICING_STEEPEST : SPX_PRIMAL_PRICING_DANTZIG;
+    x->pbox.winit = (x->opts.flags & SPX_FLAG_PRIMAL_EXACT_WEIGHTS) ? SPX_PRIMAL_WEIGHTS_EXACT : SPX_PRIMAL_WEIGHTS_REFERENCE;
     if (x->pbox.phase1 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_ARG, "SPX_FLAG_PRIMAL_STEEPEST with SPX_FLAG_PRIMAL_PHASE1: steepest-edge pricing does not "
                     "run during the bounded primal loop's phase 1");
@@ -327,6 +375,48 @@ int spx_get_primal_weights(spx_ctx* x, double* w) {
     HIP_TRY(hipMemsetAsync(&s.se.se->pend, 0, sizeof(int32_t), x->stream));
     HIP_TRY(hipStreamSynchronize(x->stream));
     HIP_TRY(hipMemcpy(w, s.se.gamma, sizeof(double) * (size_t)x->n, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_set_primal_weight_init(spx_ctx* x, int32_t mode) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (mode != SPX_PRIMAL_WEIGHTS_REFERENCE && mode != SPX_PRIMAL_WEIGHTS_EXACT)
+        return fail(SPX_ERR_ARG, "bad primal weight start mode %d", mode);
+    x->pbox.winit = mode;
+    return SPX_OK;
+}
+
+int spx_refresh_primal_weights(spx_ctx* x) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (x->pbox.rule != SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "no primal pricing weights: the bounded primal loop's entering rule is Dantzig");
+    if (x->algo != SPX_ALGO_PRIMAL_BOX)
+        return fail(SPX_ERR_STATE, "no primal pricing weights: the context does not run SPX_ALGO_PRIMAL_BOX");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_refresh_primal_weights between spx_price and spx_pivot");
+    PboxState& s = x->pbox;
+    SPX_TRY(pbox_setup(x));
+    SPX_TRY(pbox_se_setup(x));
+    SPX_TRY(pbox_wexact_run(x));
+    // the weights are those of the current basis: a recurrence recorded for the last pivot is dropped
+    HIP_TRY(hipMemsetAsync(&s.se.se->pend, 0, sizeof(int32_t), x->stream));
+    s.se_stale = false;
+    return SPX_OK;
+}
+
+int spx_pbox_wexact_times(spx_ctx* x, double* ms, int64_t* launches) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (!x->timing) return fail(SPX_ERR_STATE, "context created without SPX_FLAG_TIMING");
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    double t = 0.0;
+    for (size_t i = 0; i < x->pbox.n_wx; ++i) {
+        float e = 0.f;
+        HIP_TRY(hipEventElapsedTime(&e, x->pbox.ev_wx[2 * i], x->pbox.ev_wx[2 * i + 1]));
+        t += e;
+    }
+    if (ms) *ms = t;
+    if (launches) *launches = (int64_t)x->pbox.n_wx;
+    x->pbox.n_wx = 0;
     return SPX_OK;
 }
 

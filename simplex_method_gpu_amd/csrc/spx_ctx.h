@@ -113,6 +113,14 @@ struct DualState {
 //    spx_set_basis, spx_set_algorithm and a change of rule set se_stale; a
 //    reinversion keeps the basis and the record owns its operands, so it stays.
 //    rule == STEEPEST and phase1 never hold together (both setters refuse).
+//  - exact weights (spx_set_primal_weight_init, spx_refresh_primal_weights;
+//    DESIGN.md §7i): wx.parts != nullptr  <=>  pbox_wexact_setup ran (the partial
+//    buffers and wx_S, an m x L copy of the true B^-1, allocated by the first
+//    exact recomputation; a context in REFERENCE mode that never refreshes
+//    allocates and launches none of it).  winit says what a restart does for a
+//    warm basis; warm: spx_set_basis was called since create / the last reset, so
+//    the slack basis is `!warm && pivots == 0`, where a restart is
+//    k_pbox_se_init's in both modes.
 struct PboxState {
     spx::PboxArgs args{};
     spx::PboxCfg cfg{};
@@ -128,6 +136,13 @@ struct PboxState {
     spx::PboxSeArgs se{};
     spx::PboxSeCfg secfg{};
     bool se_stale = true;
+    int32_t winit = SPX_PRIMAL_WEIGHTS_REFERENCE;  // how the weights restart for a warm basis
+    bool warm = false;
+    spx::PboxWexactArgs wx{};
+    spx::PboxWexactCfg wxcfg{};
+    double* wx_S = nullptr;  // m x L
+    std::vector<hipEvent_t> ev_wx;  // timing: pairs around an exact recomputation (spx_pbox_wexact_times)
+    size_t n_wx = 0;
 };
 
 struct spx_ctx {
@@ -310,6 +325,7 @@ int pbox_on_reset(spx_ctx* x);     // do_reset: counters cleared, nothing checke
 void pbox_on_change(spx_ctx* x);   // the basis, the bounds, b, c or the algorithm were set: nothing checked
 int pbox_on_create(spx_ctx* x);    // phase 1 and the entering rule as opts.flags asks for
 void pbox_weights_lost(spx_ctx* x);  // the basis was set from outside or another loop takes it: steepest-edge weights restart
+void pbox_basis_set(spx_ctx* x);     // spx_set_basis: the basis is no longer known to be the slack basis
 int pbox_on_reinvert(spx_ctx* x);  // B^-1, x_b and y rebuilt: y current, the rows classified again
 int pbox_fresh_y(spx_ctx* x);      // before anything outside the loop reads y: y = c_B B^-1 if phase 1 left it stale
 

@@ -224,4 +224,81 @@ hipError_t launch_pbox_step_se(const Params& P, const PboxArgs& D, const PboxSeA
 hipError_t launch_pbox_tau(const Params& P, const PboxSeArgs& E, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
                            hipEvent_t e1);
 
+// Exact weights of a warm basis (spx_pbox_wexact.hip): gamma_j =
+// 1 + ||B^-1 A_j||^2 for every column on nb_list, from W.S = the true B^-1 of the
+// current basis (m x L row-major, nothing pending: the host materialises it
+// first; no kernel here applies an eta).  Three launches, ordered by kernel
+// boundaries only:
+//   k_pbox_wexact        V = S A_N tile by tile with v_mfma_f64_16x16x4_f64, kept
+//                  as column norms only.  Workgroup (x, y) owns rows [128 x, 128 x
+//                  + 128) of S and list slots [128 y, 128 y + 128); its four waves
+//                  own 64 x 64 quadrants (4 x 4 accumulator tiles in registers).
+//                  The K loop runs over 16-wide chunks of S rows and A columns
+//                  (both contiguous along k), staged through two LDS buffers with
+//                  the next chunk's global loads in flight.  Rows >= m, k >= m
+//                  and slots past the list read as zeros (nothing outside S, A or
+//                  the list is addressed); with Params::slack_unit a listed slack
+//                  column is not streamed (k_pbox_wexact_slack has its norm).
+//                  Epilogue: per column the squares of the wave's 64 rows in a
+//                  fixed order (tile, register, then the four row groups of the
+//                  accumulator layout), the two row halves added through LDS;
+//                  one partial per (row block, slot), plain stores.
+//   k_pbox_wexact_slack  slack_unit only: column k of S squared and summed per row
+//                  block, rows ascending, one lane per column; one partial per
+//                  (row block, k).
+//   k_pbox_wexact_sum    gamma_j = 1 + the row blocks' partials in ascending
+//                  row-block order (a unit slack column from the slack partials).
+// The geometry is a function of m and n alone: no tuning option reaches it, so
+// the weights are the same bits from run to run and across those options.
+constexpr int PBOX_WX_BLOCK = 256;  // threads per workgroup of the three kernels
+constexpr int PBOX_WX_TILE = 128;   // rows of S and list slots per k_pbox_wexact workgroup
+constexpr int PBOX_WX_KC = 16;      // doubles of k per staged chunk
+constexpr int PBOX_WX_LD = PBOX_WX_KC + 2;  // LDS row pitch (doubles): conflict-free fragment reads
+
+struct PboxWexactCfg {
+    int row_blocks = 0;  // blocks of PBOX_WX_TILE rows of S: ceil(m / 128)
+    int col_tiles = 0;   // tiles of PBOX_WX_TILE list slots: ceil((n - m) / 128)
+    int slack_grid = 0;  // k_pbox_wexact_slack: blocks of PBOX_WX_BLOCK columns of S
+    int sum_grid = 0;    // k_pbox_wexact_sum: blocks of PBOX_WX_BLOCK list slots
+    int64_t cap = 0;     // list slots: n - m (the non-basic count never changes)
+    size_t parts = 0;    // doubles of the product's partials: row_blocks x cap
+    size_t sparts = 0;   // doubles of the slack partials: row_blocks x L
+};
+
+// first and one-past-last list slot of column tile t for a list of cnt entries
+struct PboxWexactSlice {
+    int64_t lo, hi;
+};
+
+inline PboxWexactCfg pbox_wexact_geometry(int64_t m, int64_t n, int64_t L) {
+    PboxWexactCfg c;
+    c.cap = n - m;
+    c.row_blocks = (int)((m + PBOX_WX_TILE - 1) / PBOX_WX_TILE);
+    c.col_tiles = (int)((c.cap + PBOX_WX_TILE - 1) / PBOX_WX_TILE);
+    c.slack_grid = (int)((m + PBOX_WX_BLOCK - 1) / PBOX_WX_BLOCK);
+    c.sum_grid = (int)((c.cap + PBOX_WX_BLOCK - 1) / PBOX_WX_BLOCK);
+    c.parts = (size_t)c.row_blocks * (size_t)c.cap;
+    c.sparts = (size_t)c.row_blocks * (size_t)L;
+    return c;
+}
+
+inline PboxWexactSlice pbox_wexact_slice(int64_t t, int64_t cnt) {
+    const int64_t lo = t * PBOX_WX_TILE;
+    const int64_t hi = lo + PBOX_WX_TILE < cnt ? lo + PBOX_WX_TILE : cnt;
+    return PboxWexactSlice{lo < cnt ? lo : cnt, hi};
+}
+
+struct PboxWexactArgs {
+    const double* S;  // m x L: the true B^-1
+    double* parts;    // row_blocks x cap
+    double* sparts;   // row_blocks x L
+    double* gamma;    // n (PboxSeArgs::gamma)
+    int64_t cap;
+    int32_t row_blocks;
+    int32_t pad;
+};
+
+hipError_t pbox_wexact_prepare();  // once per process and device: the product kernel's LDS size
+hipError_t launch_pbox_wexact(const Params& P, const PboxWexactArgs& W, const PboxWexactCfg& c, hipStream_t s);
+
 }  // namespace spx

@@ -56,11 +56,30 @@ and, with --solve, whole solves (the --solve mode above) at every --solve-shape
 under both rules, Dantzig / steepest / Dantzig / steepest, with the ratios of
 pivots and seconds.
 
+--warm-resolve measures the exact weight start of a warm basis
+instead, one child process per shape:
+  resolve       at every --solve-shape the LP of tests/dual_box_ref.py boxed(m, n,
+                seed): a boxed dual steepest-edge solve, spx_set_cost with
+                primal_box_ref.cost_variant, spx_set_algorithm(SPX_ALGO_PRIMAL_BOX)
+                under steepest edge and the re-solve; after one untimed sequence
+                (first-launch costs) the two start modes alternate in that process,
+                REFERENCE / EXACT / REFERENCE / EXACT: pivots, flip passes and wall
+                seconds of the re-solve (the exact start inside them), and from one
+                more EXACT sequence under SPX_FLAG_TIMING the exact start's device time
+  kernel        at every --kernel-shape boxed_primal's LP under steepest edge after
+                --warm pivots: five spx_refresh_primal_weights, their device times
+                (spx_pbox_wexact_times), the fp64 rate 2 m^2 (n - m) / time of the
+                fastest, and the mean wall time of a steepest-edge pass of the same
+                context over --k pivots, so the start is also quoted in passes
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
     python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
     python tools/pbox_bench.py --primal-pricing steepest [--solve --solve-shape 1024 4096 4
                                --solve-shape 2048 8192 5] [--out profiles/pbox_se_c3.json]
+    python tools/pbox_bench.py --warm-resolve --solve-shape 1024 4096 4 --solve-shape 2048 8192 5
+                               --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5 --kernel-shape 4096 16384 5
+                               [--out profiles/pbox_wexact.json]
 """
 import argparse
 import json
@@ -398,6 +417,97 @@ def run_solve(a):
     return out
 
 
+def run_warm_resolve(a):
+    """One shape (the first --solve-shape): the re-solve under both start modes, alternating."""
+    import numpy as np
+
+    import dual_box_ref
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    m, n, seed = a.solve_shape[0]
+    A, b, c, u = dual_box_ref.boxed(m, n, seed, False)
+    c2 = primal_box_ref.cost_variant(c, n - m, seed)
+    A_cols = np.ascontiguousarray(A.T)
+
+    def sequence(mode, timing=False):
+        with spx.Context(A_cols, b, c, device=0, window=-1, algorithm=spx.ALGO_DUAL,
+                         dual_pricing=spx.DUAL_PRICING_STEEPEST, upper=u, primal_pricing=spx.PRIMAL_PRICING_STEEPEST,
+                         primal_weights=mode, timing=timing) as ctx:
+            t0 = time.perf_counter()
+            r0 = ctx.solve()
+            t1 = time.perf_counter()
+            ctx.set_cost(c2)
+            ctx.set_algorithm(spx.ALGO_PRIMAL_BOX)
+            t2 = time.perf_counter()
+            r1 = ctx.solve()
+            t3 = time.perf_counter()
+            up = ctx.primal()[1]
+            fl = ctx.primal_flips()
+            rec = {"mode": "exact" if mode == spx.PRIMAL_WEIGHTS_EXACT else "reference", "dual_status": int(r0.status),
+                   "dual_pivots": r0.pivots, "dual_seconds": round(t1 - t0, 4), "status": int(r1.status),
+                   "pivots": r1.pivots - r0.pivots, "flip_passes": fl[0], "to_upper": fl[1], "z": r1.z,
+                   "seconds": round(t3 - t2, 5)}
+            if timing:
+                ms, k = ctx.wexact_times()
+                rec.update({"wexact_ms": round(ms, 4), "wexact_launches": k})
+        if int(r1.status) == 1:
+            viol, dviol, _ = primal_box_ref.certificate(A, b, c2, u, r1.b_ixs, up)
+            rec["cert_ok"] = bool(viol <= 1e-9 and dviol <= 1e-7)
+        return rec
+
+    sequence(spx.PRIMAL_WEIGHTS_EXACT)  # first-launch costs
+    runs = [sequence(mode) for mode in (spx.PRIMAL_WEIGHTS_REFERENCE, spx.PRIMAL_WEIGHTS_EXACT,
+                                        spx.PRIMAL_WEIGHTS_REFERENCE, spx.PRIMAL_WEIGHTS_EXACT)]
+    timed = sequence(spx.PRIMAL_WEIGHTS_EXACT, timing=True)
+    ref_s = min(runs[0]["seconds"], runs[2]["seconds"])
+    ex_s = min(runs[1]["seconds"], runs[3]["seconds"])
+    return {"m": m, "n": n, "seed": seed, "runs": runs, "exact_timed": timed,
+            "pivot_ratio": round(runs[0]["pivots"] / max(runs[1]["pivots"], 1), 2),
+            "time_ratio": round(ref_s / ex_s, 2),
+            "accepted": bool(all(runs[i + 1]["pivots"] < runs[i]["pivots"] and runs[i + 1]["seconds"] < runs[i]["seconds"]
+                                 for i in (0, 2)))}
+
+
+def run_wexact_kernel(a):
+    """One shape (the first --kernel-shape): the exact recomputation's device time."""
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    m, n, seed = a.kernel_shape[0]
+    A, b, c, u = primal_box_ref.boxed_primal(m, n, seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    with spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u, timing=True,
+                     primal_pricing=spx.PRIMAL_PRICING_STEEPEST) as ctx:
+        ctx.iterate(a.warm)
+        ctx.wexact_times()
+        times = []
+        for _ in range(5):
+            ctx.refresh_primal_weights()
+            times.append(round(ctx.wexact_times()[0], 4))
+        nb_slack = int(np.sum(~np.isin(np.arange(n - m, n), ctx.state()["b_ixs"])))
+    with spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                     primal_pricing=spx.PRIMAL_PRICING_STEEPEST) as ctx:
+        ctx.iterate(a.warm)
+        f0 = ctx.primal_flips()
+        _, p0 = ctx.iterate(0)
+        t0 = time.perf_counter()
+        _, p1 = ctx.iterate(a.k)
+        dt = time.perf_counter() - t0
+        f1 = ctx.primal_flips()
+    passes = p1 - p0 + f1[0] - f0[0]
+    pass_us = 1e6 * dt / max(passes, 1)
+    best = min(times)
+    flops = 2.0 * m * m * (n - m)
+    return {"m": m, "n": n, "seed": seed, "warm": a.warm, "wexact_ms": times, "wexact_ms_best": best,
+            "nonbasic_slacks": nb_slack, "flops_all_listed": flops,
+            "fp64_TFLOPs": round(flops / (best * 1e-3) / 1e12, 2), "se_pass_us": round(pass_us, 2),
+            "se_passes_timed": passes, "start_in_se_passes": round(best * 1e3 / pass_us, 1)}
+
+
 def child(a, role, pricing="dantzig", se_lds=None):
     env = dict(os.environ)
     if se_lds is not None:
@@ -409,6 +519,8 @@ def child(a, role, pricing="dantzig", se_lds=None):
         cmd.append("--rows")
     for shape in a.solve_shape:
         cmd += ["--solve-shape"] + [str(v) for v in shape]
+    for shape in a.kernel_shape:
+        cmd += ["--kernel-shape"] + [str(v) for v in shape]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     if out.returncode != 0:
         sys.stderr.write(out.stdout + out.stderr)
@@ -433,14 +545,35 @@ def main():
     ap.add_argument("--sparse-chunk", type=int, default=10, help="p1_sparse: pivots per timed chunk")
     ap.add_argument("--primal-pricing", default="dantzig", choices=["dantzig", "steepest"],
                     help="steepest: the steepest-edge sides against the Dantzig loop instead (DESIGN.md 7h)")
+    ap.add_argument("--warm-resolve", action="store_true",
+                    help="the exact weight start of a warm basis instead (DESIGN.md 7i)")
+    ap.add_argument("--kernel-shape", type=int, nargs=3, action="append", default=[], metavar=("M", "N", "SEED"),
+                    help="with --warm-resolve: shapes at which the exact recomputation alone is timed")
     ap.add_argument("--role", default=None,
-                    choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se"])
+                    choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se",
+                             "warm_resolve", "wexact_kernel"])
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
         run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
                "pbox_flag": run_pbox_flag, "p1_dense": run_p1_dense, "p1_sparse": run_p1_sparse,
-               "pbox_se": run_pbox_se}[a.role]
+               "pbox_se": run_pbox_se, "warm_resolve": run_warm_resolve, "wexact_kernel": run_wexact_kernel}[a.role]
         print(json.dumps(run(a)), flush=True)
+        return
+    if a.warm_resolve:
+        import copy
+
+        res = {"k": a.k, "warm": a.warm, "resolve": [], "kernel": []}
+        for key, role, shapes in (("kernel", "wexact_kernel", a.kernel_shape), ("resolve", "warm_resolve", a.solve_shape)):
+            for shape in shapes:
+                one = copy.copy(a)
+                one.solve_shape, one.kernel_shape = ([shape], []) if key == "resolve" else ([], [shape])
+                res[key].append(child(one, role, "steepest"))
+                sys.stderr.write(f"{key} {shape}: {json.dumps(res[key][-1])}\n")
+                sys.stderr.flush()
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
         return
     if a.k < 252:
         ap.error("--k: at least 252 timed pivots")
