@@ -766,6 +766,30 @@ int spx_info(spx_ctx* ctx, int64_t* m, int64_t* n, int64_t* ld,
 #define SPX_CONFIG_FIELDS 17
 int spx_config(spx_ctx* ctx, int32_t out[SPX_CONFIG_FIELDS]);
 
+/* Where the dual and the bounded primal loop keep the vectors their kernels
+ * read, as their setup resolved it from L = round_up(m, 128) against 150 KiB
+ * of LDS: 24 L bytes fit up to L = 6400, 16 L up to L = 9600, 8 L up to L =
+ * 19200.  1 = staged in LDS, 0 = read from global memory, -1 = that loop's
+ * setup has not run yet (it runs on first use).
+ *   out[0] dual loop: rho and y of the ratio test (16 L bytes)
+ *   out[1] dual loop: the pending row and A_p of the update (16 L)
+ *   out[2] dual loop, steepest edge: the update's operands (24 L must fit)
+ *   out[3] ... rho among them (1), or read from global memory (0:
+ *          SPX_DUAL_RHO_LDS=0, and wherever out[2] is 0)
+ *   out[4] bounded primal loop: y of the pricing pass (8 L)
+ *   out[5] bounded primal loop: the pending row and A_p of the update (16 L)
+ *   out[6] bounded primal loop, steepest edge: vectors of the pricing pass in
+ *          LDS, 3 (y, rho, tau), 1 (y) or 0 (SPX_PBOX_SE_LDS asks for fewer);
+ *          -1 until the first steepest-edge pass or weight readback
+ *   out[7] 1: a slack column is priced from its one entry (A[:, n-m:] = I),
+ *          0: streamed like any column (SPX_DENSE_SLACKS=1, or other slacks)
+ * SPX_FLAG_GLOBAL_Y turns out[0], [2], [4] and [6] to 0.  SPX_DUAL_LDS_CAP and
+ * SPX_PBOX_LDS_CAP (bytes; tests) stand in for the 150 KiB where they are
+ * smaller, so the layouts of a large m can be run at a small one; they are
+ * read when the loop's setup runs and never raise the cap. */
+#define SPX_LOOP_LAYOUT_FIELDS 8
+int spx_loop_layout(spx_ctx* ctx, int32_t out[SPX_LOOP_LAYOUT_FIELDS]);
+
 /* Columns of B^-1 the FTRAN stream reads per row: m, or with the eta window's
  * compact operand (A[:, n-m:] = I, two-kernel passes; SPX_DENSE_FTRAN=1 turns
  * it off) the non-unit columns of B_w as of the last fold: B_w is I except in

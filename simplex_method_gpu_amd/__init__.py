@@ -636,6 +636,18 @@ class Context:
         cfg["primal_weights"] = self._primal_weights
         return cfg
 
+    def loop_layout(self):
+        """Where the dual and the bounded primal loop keep their kernels' vectors
+        (spx_loop_layout): 1 staged in LDS, 0 read from global memory, -1 that
+        loop's setup has not run yet.  ``pbox_se_lds_vecs`` counts the vectors of
+        the steepest-edge pricing pass in LDS (3, 1 or 0); ``slack_unit`` is 1
+        where a slack column is priced from its one entry."""
+        out = (ctypes.c_int32 * 8)()
+        check(self._L.spx_loop_layout(self._h, out))
+        keys = ("dual_price_lds", "dual_update_lds", "dual_se_update_lds", "dual_se_rho_lds", "pbox_price_lds",
+                "pbox_update_lds", "pbox_se_lds_vecs", "slack_unit")
+        return dict(zip(keys, list(out)))
+
 
 def solve(A_cols, b, c, max_iter: int = (1 << 62), eps: float = 1e-7, device: int = -1,
           algorithm: int = ALGO_PRIMAL) -> SolveResult:

@@ -90,6 +90,7 @@ SIGNATURES = {
     "spx_pass_times": (ctypes.c_int, [_p, _p, _p]),
     "spx_info": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p]),
     "spx_config": (ctypes.c_int, [_p, _p]),
+    "spx_loop_layout": (ctypes.c_int, [_p, _p]),
     "spx_phase_times": (ctypes.c_int, [_p, _p]),
     "spx_wg_times": (ctypes.c_int, [_p, _p, _i64, _p]),
     "spx_fold_times": (ctypes.c_int, [_p, _p, _i64, _p]),

@@ -1174,6 +1174,11 @@ bool env_off(const char* name) {
     const char* env = std::getenv(name);
     return env && env[0] == '0';
 }
+size_t env_bytes(const char* name) {
+    const char* env = std::getenv(name);
+    const long long v = env ? std::atoll(env) : 0;
+    return v >= 1 ? (size_t)v : 0;
+}
 
 // k_price's column tickets (WM 2): each pass zeroes the other parity's
 // counter for the pass after it, so a pass that prices twice at one iteration

@@ -210,9 +210,10 @@ void dual_on_create(spx_ctx* x) {
 int dual_setup(spx_ctx* x) {
     DualState& d = x->dual;
     if (d.args.rho) return SPX_OK;
-    // steepest edge, k_dual_update's third operand rho: staged in LDS, or (SPX_DUAL_RHO_LDS=0) read from global memory
+    // steepest edge, k_dual_update's third operand rho: staged in LDS, or (SPX_DUAL_RHO_LDS=0) read from global memory;
+    // SPX_DUAL_LDS_CAP (tests): fewer bytes of LDS than the built-in cap, so that the layouts of a large m run at a small one
     HIP_TRY(dual_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
-                         !env_off("SPX_DUAL_RHO_LDS"), &d.cfg));
+                         !env_off("SPX_DUAL_RHO_LDS"), env_bytes("SPX_DUAL_LDS_CAP"), &d.cfg));
     SPX_TRY(x->alloc(&d.args.tau, (size_t)x->L));
     SPX_TRY(x->alloc(&d.args.wex, (size_t)x->L));
     SPX_TRY(x->alloc(&d.args.w, (size_t)x->L));

@@ -69,7 +69,9 @@ int pbox_setup(spx_ctx* x) {
     if (s.args.rec) return SPX_OK;
     SPX_TRY(dual_setup(x));  // (k_box_xb's geometry; a switch to the dual loop finds its buffers)
     SPX_TRY(box_buffers(x));
-    HIP_TRY(pbox_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0, &s.cfg));
+    // SPX_PBOX_LDS_CAP (tests): fewer bytes of LDS than the built-in cap (also pbox_se_prepare's below)
+    HIP_TRY(pbox_prepare(x->P, x->cus, x->opts.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
+                         env_bytes("SPX_PBOX_LDS_CAP"), &s.cfg));
     SPX_TRY(x->alloc(&s.args.parts, (size_t)s.cfg.price_grid));
     SPX_TRY(x->alloc(&s.args.rparts, (size_t)s.cfg.update_grid));
     s.args.ub = x->dual.args.ub;
@@ -99,7 +101,7 @@ int pbox_se_setup(spx_ctx* x) {
     // experiment (SPX_PBOX_SE_LDS): vectors of k_pbox_price_se staged in LDS -- 0, 1 or 3
     const char* ev = std::getenv("SPX_PBOX_SE_LDS");
     HIP_TRY(pbox_se_prepare(x->P, x->cus, s.cfg.price_grid, (x->opts.flags & SPX_FLAG_GLOBAL_Y) != 0,
-                            ev ? std::atoi(ev) : -1, &s.secfg));
+                            ev ? std::atoi(ev) : -1, env_bytes("SPX_PBOX_LDS_CAP"), &s.secfg));
     s.se.vtb_blocks = s.cfg.vtb_blocks;
     s.se.apply = 0;
     SPX_TRY(x->alloc(&s.se.gamma, (size_t)x->n));
@@ -401,6 +403,25 @@ int spx_refresh_primal_weights(spx_ctx* x) {
     // the weights are those of the current basis: a recurrence recorded for the last pivot is dropped
     HIP_TRY(hipMemsetAsync(&s.se.se->pend, 0, sizeof(int32_t), x->stream));
     s.se_stale = false;
+    return SPX_OK;
+}
+
+int spx_loop_layout(spx_ctx* x, int32_t out[SPX_LOOP_LAYOUT_FIELDS]) {
+    if (!x || !out) return fail(SPX_ERR_ARG, "NULL argument");
+    for (int i = 0; i < SPX_LOOP_LAYOUT_FIELDS; ++i) out[i] = -1;
+    if (x->dual.args.rho) {  // dual_setup ran
+        const DualCfg& c = x->dual.cfg;
+        out[0] = c.price_lds ? 1 : 0;
+        out[1] = c.update_lds ? 1 : 0;
+        out[2] = c.se_update_lds ? 1 : 0;
+        out[3] = (c.se_update_lds && c.se_rho_lds) ? 1 : 0;
+    }
+    if (x->pbox.args.rec) {  // pbox_setup ran
+        out[4] = x->pbox.cfg.price_lds ? 1 : 0;
+        out[5] = x->pbox.cfg.update_lds ? 1 : 0;
+    }
+    if (x->pbox.se.se) out[6] = x->pbox.secfg.lds_vecs;  // pbox_se_setup ran
+    out[7] = x->P.slack_unit ? 1 : 0;
     return SPX_OK;
 }
 

@@ -282,6 +282,7 @@ namespace spx_host {
 // spx_api.cpp, called by the dual loop
 bool env_on(const char* name);   // the variable is set and starts with '1'
 bool env_off(const char* name);  // ... with '0'
+size_t env_bytes(const char* name);  // the variable's value where it is a count >= 1, else 0
 int clear_tickets(spx_ctx* x);
 int read_state(spx_ctx* x);  // the device state to the host: the one synchronisation of an iterate call
 int flush(spx_ctx* x);

@@ -143,8 +143,11 @@ constexpr int DUAL_WAVES = DUAL_BLOCK / 64;
 constexpr double DUAL_W_FLOOR = 1e-300;  // steepest-edge weights stay positive: the key -x_b^2 / w stays finite
 
 // geometry: price_grid_opt > 0 fixes the pricing grid, global_y keeps rho and y
-// (and the steepest-edge update's operands) in global memory
-hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, bool se_rho_lds, DualCfg* cfg);
+// (and the steepest-edge update's operands) in global memory; lds_cap_opt > 0
+// lowers the bytes of LDS a staged layout may take (tests: SPX_DUAL_LDS_CAP), it
+// never raises them
+hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, bool se_rho_lds,
+                        size_t lds_cap_opt, DualCfg* cfg);
 // se: the steepest-edge instantiations (leaving row by -x_b^2 / w, weights kept in D.w)
 // box: the boxed instantiations (two-sided leaving rows, sigma_j in the ratio test)
 hipError_t launch_dual_step(const Params& P, const DualBoxArgs& D, bool se, bool box, bool finish_only, hipStream_t s);

@@ -717,12 +717,14 @@ hipError_t launch_timed(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_
 
 }  // namespace
 
-hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, bool se_rho_lds, DualCfg* cfg) {
+hipError_t dual_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, bool se_rho_lds,
+                        size_t lds_cap_opt, DualCfg* cfg) {
     const size_t vec2 = (size_t)P.L * 16;  // two staged vectors
     const size_t vec3 = (size_t)P.L * 24;  // with rho
-    cfg->price_lds = !global_y && vec2 <= DUAL_LDS_CAP;
-    cfg->update_lds = vec2 <= DUAL_LDS_CAP;
-    cfg->se_update_lds = !global_y && vec3 <= DUAL_LDS_CAP;
+    const size_t lds_cap = lds_cap_opt > 0 && lds_cap_opt < DUAL_LDS_CAP ? lds_cap_opt : DUAL_LDS_CAP;
+    cfg->price_lds = !global_y && vec2 <= lds_cap;
+    cfg->update_lds = vec2 <= lds_cap;
+    cfg->se_update_lds = !global_y && vec3 <= lds_cap;
     cfg->se_rho_lds = se_rho_lds;
     hipError_t e = hipSuccess;
     int per_cu = 0;

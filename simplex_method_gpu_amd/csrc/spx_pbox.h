@@ -116,8 +116,9 @@ constexpr int PBOX_VTB_BLOCK = 256;  // k_pbox_vtb / k_pbox_vtb_sum
 constexpr int PBOX_VTB_WAVES = PBOX_VTB_BLOCK / 64;
 constexpr int PBOX_VTB_ROWS = 64;    // rows of S per k_pbox_vtb workgroup
 
-// geometry: price_grid_opt > 0 fixes the pricing grid, global_y keeps y in global memory
-hipError_t pbox_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, PboxCfg* cfg);
+// geometry: price_grid_opt > 0 fixes the pricing grid, global_y keeps y in global memory; lds_cap_opt > 0 lowers
+// the bytes of LDS a staged layout may take (tests: SPX_PBOX_LDS_CAP), it never raises them
+hipError_t pbox_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, size_t lds_cap_opt, PboxCfg* cfg);
 hipError_t launch_pbox_price(const Params& P, const PboxArgs& D, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
                              hipEvent_t e1);
 hipError_t launch_pbox_update(const Params& P, const PboxArgs& D, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
@@ -215,8 +216,9 @@ struct PboxSeCfg {
 };
 
 // lds_vecs_opt: -1 the default (3), else 0 / 1 / 3; lowered to 1, then 0, when the vectors do not fit, and 0
-// under global_y; price_grid as PboxCfg's
-hipError_t pbox_se_prepare(const Params& P, int cus, int price_grid, bool global_y, int lds_vecs_opt, PboxSeCfg* cfg);
+// under global_y; price_grid as PboxCfg's, lds_cap_opt as pbox_prepare's
+hipError_t pbox_se_prepare(const Params& P, int cus, int price_grid, bool global_y, int lds_vecs_opt, size_t lds_cap_opt,
+                           PboxSeCfg* cfg);
 hipError_t launch_pbox_se_init(const Params& P, const PboxSeArgs& E, const PboxSeCfg& c, hipStream_t s);
 hipError_t launch_pbox_price_se(const Params& P, const PboxArgs& D, const PboxSeArgs& E, const PboxSeCfg& c, bool apply,
                                 hipStream_t s, hipEvent_t e0, hipEvent_t e1);

@@ -1481,11 +1481,12 @@ hipError_t launch_timed(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_
 
 }  // namespace
 
-hipError_t pbox_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, PboxCfg* cfg) {
+hipError_t pbox_prepare(const Params& P, int cus, int price_grid_opt, bool global_y, size_t lds_cap_opt, PboxCfg* cfg) {
     const size_t vec1 = (size_t)P.L * 8;   // y
     const size_t vec2 = (size_t)P.L * 16;  // the pending row and A_p
-    cfg->price_lds = !global_y && vec1 <= PBOX_LDS_CAP;
-    cfg->update_lds = vec2 <= PBOX_LDS_CAP;
+    const size_t lds_cap = lds_cap_opt > 0 && lds_cap_opt < PBOX_LDS_CAP ? lds_cap_opt : PBOX_LDS_CAP;
+    cfg->price_lds = !global_y && vec1 <= lds_cap;
+    cfg->update_lds = vec2 <= lds_cap;
     hipError_t e = hipSuccess;
     int per_cu = 0;
     if (cfg->price_lds) {
@@ -1600,12 +1601,14 @@ hipError_t launch_timed_se(K kernel, int grid, size_t lds, hipStream_t s, hipEve
 
 }  // namespace
 
-hipError_t pbox_se_prepare(const Params& P, int cus, int price_grid, bool global_y, int lds_vecs_opt, PboxSeCfg* cfg) {
+hipError_t pbox_se_prepare(const Params& P, int cus, int price_grid, bool global_y, int lds_vecs_opt, size_t lds_cap_opt,
+                           PboxSeCfg* cfg) {
     const size_t vec = (size_t)P.L * 8;
+    const size_t lds_cap = lds_cap_opt > 0 && lds_cap_opt < PBOX_LDS_CAP ? lds_cap_opt : PBOX_LDS_CAP;
     int nl = lds_vecs_opt < 0 ? 3 : lds_vecs_opt;  // the default: all three in LDS where they fit
     if (global_y) nl = 0;
-    if (nl == 3 && 3 * vec > PBOX_LDS_CAP) nl = 1;
-    if (nl >= 1 && vec > PBOX_LDS_CAP) nl = 0;
+    if (nl == 3 && 3 * vec > lds_cap) nl = 1;
+    if (nl >= 1 && vec > lds_cap) nl = 0;
     nl = nl >= 3 ? 3 : (nl >= 1 ? 1 : 0);
     cfg->lds_vecs = nl;
     hipError_t e = hipSuccess;

@@ -56,6 +56,17 @@ def boxed(m, n, seed, flipc=False):
     return A, b, c, u
 
 
+def boxed_tall(m, n, seed, flipc=False):
+    """boxed() for m far above n - m (tests/test_gpu_lds_cap.py: n = m + 64).
+    There boxed()'s ranged rows contradict each other: 64 columns cannot keep
+    every third row's G x within [h, h + u_slack] for thousands of independent
+    h.  The structural draws are boxed()'s; the bounded slacks get 16 x its
+    bounds, which leaves the LP feasible and the slacks flippable."""
+    A, b, c, u = boxed(m, n, seed, flipc)
+    u[n - m:] = u[n - m:] * 16.0
+    return A, b, c, u
+
+
 def tiny_box_infeasible():
     """x1 + x2 >= 2 with x1, x2 <= 0.5: the bounds make the covering row infeasible."""
     A = np.array([[1.0, 1.0, 1.0, 0.0], [-1.0, -1.0, 0.0, 1.0]])

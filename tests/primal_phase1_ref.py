@@ -66,6 +66,39 @@ def boxed_general(m, n, seed):
     return A, b, c, u
 
 
+def boxed_general_tall(m, n, seed, every=300):
+    """boxed_general() for m far above n - m (tests/test_gpu_lds_cap.py: n = m +
+    64), where a third of thousands of rows out of their bounds would take
+    phase 1 thousands of pivots: the same kinds of row in the same order of
+    draws, but only every `every`-th row is a >= row below 0 or a ranged row
+    whose slack starts above its bound; the other ranged rows get bounds their
+    slack starts inside (primal_box_ref.boxed_primal's 1.02 .. 1.3 b)."""
+    r = np.random.default_rng(seed + 4000)
+    ns = n - m
+    A = np.zeros((m, n))
+    A[:, :ns] = r.uniform(-0.5, 1.0, (m, ns))
+    A[:, ns:] = np.eye(m)
+    us = r.uniform(0.25, 0.75, ns)
+    us[::4] = np.inf
+    x0 = r.uniform(0, 0.25, ns)
+    ax = A[:, :ns] @ x0
+    f = r.uniform(1.1, 1.5, m)
+    b = np.abs(ax) * f + 0.05 * ns / 8
+    i = np.arange(m)
+    ge = (i % every == 1) & (ax > 0)
+    A[ge, :ns] *= -1
+    b[ge] = -(ax[ge] * r.uniform(0.5, 0.9, int(ge.sum())))
+    c = np.zeros(n)
+    c[:ns] = r.uniform(-0.5, 1.5, ns)
+    sl = np.full(m, np.inf)
+    rg = (i % 3 == 0) & ~ge
+    tight = r.uniform(0.3, 0.8, m)
+    wide = r.uniform(1.02, 1.3, m)
+    sl[rg] = np.abs(b[rg]) * np.where(i[rg] % every == 0, tight[rg], wide[rg])
+    u = np.concatenate([us, sl])
+    return A, b, c, u
+
+
 def contradict(A, b, u):
     """boxed_general's LP made infeasible: row 1 = -row 0 on the structural
     columns, b0 = 1, b1 = -2, both slacks without a bound (r0.x <= 1 and

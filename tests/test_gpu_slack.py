@@ -1,7 +1,9 @@
 """GPU: non-basic slack columns priced as unit vectors (Params::slack_unit,
 A[:, n-m:] = I) against the same columns streamed densely
-(SPX_DENSE_SLACKS=1): the same bits in every representation and dispatch,
-through whole solves in which most slacks leave the basis."""
+(SPX_DENSE_SLACKS=1): the same bits in every representation and dispatch of
+the primal loop, through whole solves in which most slacks leave the basis.
+The dual and the bounded primal loop's dense-slack branches (their pricing
+kernels and k_pbox_wexact) are tested in tests/test_gpu_lds_cap.py."""
 import os
 
 import numpy as np
