@@ -149,8 +149,9 @@ typedef struct spx_opts {
  *         the entering column starts from the bound it sat at.  Without a
  *         finite bound the loop and its kernels are the unbounded ones.  Finite
  *         bounds with SPX_ALGO_PRIMAL are SPX_ERR_STATE; the bound-flipping ratio
- *         test is SPX_DUAL_RATIO_LONG_STEP (below); no non-zero or free lower
- *         bounds.
+ *         test is SPX_DUAL_RATIO_LONG_STEP (below).  Finite lower bounds of any
+ *         sign run shifted (spx_set_bounds_lu below); no free and no upper-only
+ *         columns.
  * PRIMAL_BOX: the primal simplex method with bounded variables 0 <= x_j <= u_j
  *         (DESIGN.md §7e), for a basis that is primal feasible within its
  *         bounds; it shares the bounds, placements and effective right-hand
@@ -180,8 +181,10 @@ typedef struct spx_opts {
  *         are DUAL's (spx_create: SPX_ERR_ARG naming the combination; spx_price /
  *         spx_pivot / spx_group_iterate: SPX_ERR_STATE).  The entering rule is
  *         SPX_PRIMAL_PRICING_* (below: Dantzig, or exact steepest edge); no
- *         Devex, no non-zero or free lower bounds.  SPX_ALGO_PRIMAL itself still
- *         refuses finite bounds.
+ *         Devex.  Finite lower bounds of any sign run shifted and free columns
+ *         run under Dantzig pricing (spx_set_bounds_lu below); no
+ *         upper-only columns.  SPX_ALGO_PRIMAL itself still refuses finite
+ *         bounds.
  *         Phase 1 (opt-in: SPX_FLAG_PRIMAL_PHASE1, spx_set_primal_phase1;
  *         DESIGN.md §7f).  With it the entry check refuses nothing: row i is
  *         *below* when x_b[i] < -feas_tol, *above* when x_b[i] > u_k + feas_tol,
@@ -596,7 +599,8 @@ int spx_refresh_primal_weights(spx_ctx* ctx);
 int spx_get_primal_phase1(spx_ctx* ctx, int64_t out[4]);
 
 /* Upper bounds ub[0..n) of all columns, slacks included (+inf = none, NULL =
- * none at all); lower bounds are 0.  The basis and the pivot count are kept and
+ * none at all); lower bounds are 0 (other lower bounds: spx_set_bounds_lu below;
+ * this call clears them).  The basis and the pivot count are kept and
  * the status is back to running: a non-basic column at an upper bound that
  * became infinite goes to lower, every non-basic column is put on its dual
  * feasible side and x_b is recomputed, so spx_solve re-optimises from the old
@@ -609,8 +613,41 @@ int spx_get_primal_phase1(spx_ctx* ctx, int64_t out[4]);
 int spx_set_bounds(spx_ctx* ctx, const double* ub /* n, +inf = none */);
 int spx_get_bounds(spx_ctx* ctx, double* ub /* n */);
 
+/* General bounds lb[j] <= x_j <= ub[j] of all columns, slacks included
+ * (DESIGN.md §7j).  lb NULL = all 0, ub NULL = all +inf.  Accepted per column:
+ *   shifted  lb[j] finite of any sign, ub[j] >= lb[j] or +inf (lb[j] == ub[j]: a
+ *            fixed column).  The device keeps x'_j = x_j - lb[j] in [0, ub[j] -
+ *            lb[j]] and the effective right-hand side b - A.lb - sum_{j at upper}
+ *            (ub[j] - lb[j]) A_j; both bounded loops, every pricing rule, phase 1
+ *            and the long-step ratio test run unchanged on the shifted problem.
+ *   free     lb[j] = -inf and ub[j] = +inf: SPX_ALGO_PRIMAL_BOX with
+ *            SPX_PRIMAL_PRICING_DANTZIG only.  A non-basic free column sits at 0
+ *            and is a candidate when |d_j| > eps (key -|d_j|; it moves up when
+ *            d_j < 0, down otherwise); it never flips; a row whose basic column
+ *            is free never blocks, is never out of its bounds and never leaves.
+ * Every readback is in the caller's variables: spx_get_primal gives lb[j] or
+ * ub[j] exactly for a non-basic column, spx_get_state's x_b includes the basic
+ * column's lower bound, spx_objective and spx_solve's z include sum_j c_j lb[j]
+ * (summed on the host over ascending j with the current c).  y, reduced costs,
+ * traces, weights and counters are those of the shifted problem, which has the
+ * same ones.  Otherwise as spx_set_bounds, whose refusals apply; in addition
+ * SPX_ERR_ARG for NaN, lb[j] = +inf, lb[j] > ub[j] and for an upper-only column
+ * (lb[j] = -inf with a finite ub[j]); SPX_ERR_STATE for a free column on a
+ * context that runs SPX_ALGO_DUAL (spx_set_algorithm(SPX_ALGO_DUAL) on a context
+ * holding one is refused in the same way: a non-basic free column has no dual
+ * feasible side unless d_j = 0) or whose entering rule is
+ * SPX_PRIMAL_PRICING_STEEPEST (spx_set_primal_pricing refuses that rule on a
+ * context holding one).  A refused call changes nothing.  With lb NULL or all 0
+ * the call is spx_set_bounds(ctx, ub): the same kernels and the same bits.
+ * spx_set_bounds(ctx, ub) on a context that had lower bounds clears them;
+ * spx_get_bounds returns the caller's ub. */
+int spx_set_bounds_lu(spx_ctx* ctx, const double* lb /* n; NULL = all 0; -inf = no lower bound */,
+                      const double* ub /* n; NULL = all +inf */);
+int spx_get_bounds_lu(spx_ctx* ctx, double* lb /* n */, double* ub /* n */);
+
 /* The full primal vector x[0..n): basic values, u_j for a non-basic column at
- * its upper bound (at_upper[j] = 1), 0 otherwise. */
+ * its upper bound (at_upper[j] = 1), its lower bound otherwise (0 without
+ * spx_set_bounds_lu, and for a free column). */
 int spx_get_primal(spx_ctx* ctx, double* x /* n */, int8_t* at_upper /* n, may be NULL */);
 
 /* Whole solve, device-resident: at most max_iter loop passes (reference

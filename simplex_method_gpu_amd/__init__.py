@@ -185,7 +185,7 @@ class Context:
                  dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None,
                  dual_ratio: int = DUAL_RATIO_TEXTBOOK, primal_phase1: bool = False,
                  primal_pricing: int = PRIMAL_PRICING_DANTZIG,
-                 primal_weights: int = PRIMAL_WEIGHTS_REFERENCE):
+                 primal_weights: int = PRIMAL_WEIGHTS_REFERENCE, lower=None):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -239,7 +239,13 @@ class Context:
             self.m, self.n = m, n
         self._h = h
         self._L = L
-        if upper is not None:  # 0 <= x <= upper: ALGO_DUAL or ALGO_PRIMAL_BOX (the library refuses it otherwise)
+        if lower is not None:  # lower <= x <= upper (spx_set_bounds_lu); lower all 0 is the call below
+            try:
+                self.set_bounds_lu(lower, upper)
+            except Exception:
+                self.close()
+                raise
+        elif upper is not None:  # 0 <= x <= upper: ALGO_DUAL or ALGO_PRIMAL_BOX (the library refuses it otherwise)
             try:
                 self.set_bounds(upper)
             except Exception:
@@ -435,10 +441,38 @@ class Context:
         check(self._L.spx_get_bounds(self._h, _ptr(ub)))
         return ub
 
+    def set_bounds_lu(self, lower, upper):
+        """General bounds ``lower <= x <= upper`` of all n columns, slacks
+        included (spx_set_bounds_lu): ``None`` = all 0 / all ``inf``.  A finite
+        lower bound of any sign runs shifted under ALGO_DUAL and
+        ALGO_PRIMAL_BOX; ``lower = -inf`` with ``upper = inf`` is a free column
+        (ALGO_PRIMAL_BOX with Dantzig pricing only).  The readbacks (``primal``,
+        ``state``'s ``x_b``, ``objective``, ``solve``) are in the caller's
+        variables.  Otherwise as :meth:`set_bounds`."""
+        lb = ub = None
+        if lower is not None:
+            lb = np.ascontiguousarray(lower, dtype=np.float64)
+            if lb.shape != (self.n,):
+                raise ValueError(f"lower must have {self.n} entries")
+        if upper is not None:
+            ub = np.ascontiguousarray(upper, dtype=np.float64)
+            if ub.shape != (self.n,):
+                raise ValueError(f"upper must have {self.n} entries")
+        check(self._L.spx_set_bounds_lu(self._h, None if lb is None else _ptr(lb), None if ub is None else _ptr(ub)))
+
+    def bounds_lu(self):
+        """(lower, upper): the bounds in force (spx_get_bounds_lu), ``-inf`` /
+        ``inf`` where none."""
+        lb = np.empty(self.n, dtype=np.float64)
+        ub = np.empty(self.n, dtype=np.float64)
+        check(self._L.spx_get_bounds_lu(self._h, _ptr(lb), _ptr(ub)))
+        return lb, ub
+
     def primal(self):
         """(x, at_upper): the full primal vector of n entries -- basic values,
-        u_j for a non-basic column at its upper bound, 0 otherwise -- and the
-        at-upper flags (spx_get_primal)."""
+        u_j for a non-basic column at its upper bound, its lower bound (0 unless
+        :meth:`set_bounds_lu` gave another; 0 for a free column) otherwise --
+        and the at-upper flags (spx_get_primal)."""
         x = np.empty(self.n, dtype=np.float64)
         up = np.zeros(self.n, dtype=np.int8)
         check(self._L.spx_get_primal(self._h, _ptr(x), _ptr(up)))

@@ -60,6 +60,8 @@ SIGNATURES = {
     "spx_set_rhs": (ctypes.c_int, [_p, _p]),
     "spx_set_bounds": (ctypes.c_int, [_p, _p]),
     "spx_get_bounds": (ctypes.c_int, [_p, _p]),
+    "spx_set_bounds_lu": (ctypes.c_int, [_p, _p, _p]),
+    "spx_get_bounds_lu": (ctypes.c_int, [_p, _p, _p]),
     "spx_get_primal": (ctypes.c_int, [_p, _p, _p]),
     "spx_set_dual_pricing": (ctypes.c_int, [_p, _i32]),
     "spx_get_dual_weights": (ctypes.c_int, [_p, _p]),

@@ -57,6 +57,11 @@
 //                  --primal-box (spx_set_bounds): F holds n whitespace-separated
 //                  values, "inf" = none; without either the library's refusal is
 //                  printed (exit 1); not with --mps (its reader turns bounds into rows)
+//   --lower F      lower bounds l_j <= x_j of all n columns for --dual or
+//                  --primal-box (spx_set_bounds_lu), with or without --bounds: F
+//                  in --bounds' format, "-inf" = a free column (--primal-box with
+//                  Dantzig pricing); z and x are in the caller's variables;
+//                  without --dual or --primal-box it is refused by name (exit 1)
 //   --tableau      window tableau (SPX_FLAG_TABLEAU): T_w = B_w A
 //                  kept in HBM, no per-pivot A / B^-1 stream
 //   --mps          the input is an MPS file (mps_io.h): converted to the
@@ -102,7 +107,7 @@ static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
                  " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--primal-weights reference|exact]]"
-                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F]"
+                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -114,7 +119,7 @@ int main(int argc, char* argv[]) {
     int device = -1;
     bool iter_lines = true, json = false, gen = false, solve = true;
     int threads = 0;
-    std::string write_bin, write_text, bounds_path;
+    std::string write_bin, write_text, bounds_path, lower_path;
     int64_t gm = 0, gn = 0;
     uint64_t gseed = 0;
     const char* path = nullptr;
@@ -161,6 +166,7 @@ int main(int argc, char* argv[]) {
         else if (s == "--primal-box") primal_box = true;
         else if (s == "--phase1") phase1 = true;
         else if (s == "--bounds") { need(1); bounds_path = argv[++a]; }
+        else if (s == "--lower") { need(1); lower_path = argv[++a]; }
         else if (s == "--dual-pricing") {
             need(1);
             const std::string r = argv[++a];
@@ -216,6 +222,10 @@ int main(int argc, char* argv[]) {
     }
     if (phase1 && !primal_box) {
         std::cerr << "--phase1 needs --primal-box: it is the bounded primal loop's phase 1\n";
+        return 1;
+    }
+    if (!lower_path.empty() && !primal_box && !dual) {
+        std::cerr << "--lower needs --dual or --primal-box: lower bounds are the bounded loops'\n";
         return 1;
     }
     if (primal_pricing_given && !primal_box) {
@@ -298,30 +308,40 @@ int main(int argc, char* argv[]) {
         std::cerr << "spx_create failed (" << rc << "): " << spx_last_error() << "\n";
         return EXIT_FAILURE;
     }
-    if (!bounds_path.empty()) {
+    if (!bounds_path.empty() || !lower_path.empty()) {
+        const char* opt = !bounds_path.empty() ? "--bounds" : "--lower";
         if (mps_in) {
-            std::cerr << "--bounds does not combine with --mps: the MPS reader turns bounds into rows\n";
+            std::cerr << opt << " does not combine with --mps: the MPS reader turns bounds into rows\n";
             spx_destroy(ctx);
             return EXIT_FAILURE;
         }
-        std::ifstream bf(bounds_path);
-        std::vector<double> ub;
-        std::string tok;
-        bool bad = !bf;
-        while (!bad && bf >> tok) {
-            char* end = nullptr;
-            const double v = std::strtod(tok.c_str(), &end);  // ("inf" / "+inf" / "infinity" parse as infinity)
-            if (end == tok.c_str() || *end != '\0') bad = true;
-            ub.push_back(v);
-        }
-        if (bad || (int64_t)ub.size() != n) {
-            std::cerr << "--bounds " << bounds_path << ": expected " << n << " values (one per column, inf = none)\n";
+        // n whitespace-separated values ("inf" / "+inf" / "-inf" / "infinity" parse as infinities)
+        auto read_values = [&](const char* name, const std::string& file, const char* none, std::vector<double>& out) {
+            std::ifstream bf(file);
+            std::string tok;
+            bool bad = !bf;
+            while (!bad && bf >> tok) {
+                char* end = nullptr;
+                const double v = std::strtod(tok.c_str(), &end);
+                if (end == tok.c_str() || *end != '\0') bad = true;
+                out.push_back(v);
+            }
+            if (bad || (int64_t)out.size() != n) {
+                std::cerr << name << " " << file << ": expected " << n << " values (one per column, " << none << ")\n";
+                return false;
+            }
+            return true;
+        };
+        std::vector<double> ub, lb;
+        if ((!bounds_path.empty() && !read_values("--bounds", bounds_path, "inf = none", ub)) ||
+            (!lower_path.empty() && !read_values("--lower", lower_path, "-inf = free", lb))) {
             spx_destroy(ctx);
             return EXIT_FAILURE;
         }
-        rc = spx_set_bounds(ctx, ub.data());
+        const char* call = lb.empty() ? "spx_set_bounds" : "spx_set_bounds_lu";
+        rc = lb.empty() ? spx_set_bounds(ctx, ub.data()) : spx_set_bounds_lu(ctx, lb.data(), ub.empty() ? nullptr : ub.data());
         if (rc != SPX_OK) {
-            std::cerr << "spx_set_bounds failed (" << rc << "): " << spx_last_error() << "\n";
+            std::cerr << call << " failed (" << rc << "): " << spx_last_error() << "\n";
             spx_destroy(ctx);
             return EXIT_FAILURE;
         }

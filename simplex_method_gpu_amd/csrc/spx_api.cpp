@@ -1795,6 +1795,11 @@ int spx_get_state(spx_ctx* x, double* x_b, int64_t* b_ixs, double* y, double* c_
     SPX_TRY(read_state(x));  // drains the stream; y_buf after the flush
     if (x_b) HIP_TRY(hipMemcpy(x_b, x->P.x_b, mb, hipMemcpyDeviceToHost));
     if (b_ixs) HIP_TRY(hipMemcpy(b_ixs, x->P.b_ixs, mb, hipMemcpyDeviceToHost));
+    if (x_b && !x->dual.lb.empty()) {  // general bounds: the device holds x - l
+        std::vector<int64_t> bix((size_t)x->m);
+        HIP_TRY(hipMemcpy(bix.data(), x->P.b_ixs, mb, hipMemcpyDeviceToHost));
+        box_unshift_xb(x, x_b, bix.data());
+    }
     if (y) HIP_TRY(hipMemcpy(y, x->st_host->y_buf ? x->P.y1 : x->P.y0, mb, hipMemcpyDeviceToHost));
     if (c_b) HIP_TRY(hipMemcpy(c_b, x->P.c_B, mb, hipMemcpyDeviceToHost));
     if (status) *status = x->status;

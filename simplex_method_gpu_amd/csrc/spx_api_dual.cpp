@@ -230,8 +230,20 @@ int dual_setup(spx_ctx* x) {
 
 int box_sync(spx_ctx* x) {
     if (!x->dual.boxed) return SPX_OK;
-    HIP_TRY(launch_box_rhs(x->P, x->dual.args, x->dual.b_user, x->b, x->stream));
+    if (x->dual.shifted)  // some lower bound is not 0: the A.l term too
+        HIP_TRY(launch_box_rhs_lu(x->P, x->dual.args, x->dual.d_lsh, x->dual.b_user, x->b, x->stream));
+    else
+        HIP_TRY(launch_box_rhs(x->P, x->dual.args, x->dual.b_user, x->b, x->stream));
     return SPX_OK;
+}
+
+void box_unshift_xb(const spx_ctx* x, double* x_b, const int64_t* b_ixs) {
+    const std::vector<double>& lb = x->dual.lb;
+    if (lb.empty()) return;
+    for (size_t i = 0; i < (size_t)x->m; ++i) {
+        const double l = lb[(size_t)b_ixs[i]];
+        if (std::isfinite(l)) x_b[i] += l;
+    }
 }
 
 int box_buffers(spx_ctx* x) {
@@ -300,7 +312,8 @@ int dual_on_reset(spx_ctx* x) {
     DualState& d = x->dual;
     if (d.boxed) {  // every column back at its lower bound: b_eff = b
         HIP_TRY(hipMemsetAsync(d.args.at_upper, 0, (size_t)x->n, x->stream));
-        HIP_TRY(hipMemcpyAsync(x->b, d.b_user, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
+        if (d.shifted) SPX_TRY(box_sync(x));  // b_eff = b - A.l (launch_reset reads it; ub_B follows in do_reset)
+        else HIP_TRY(hipMemcpyAsync(x->b, d.b_user, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
     }
     if (d.args.rec) HIP_TRY(hipMemsetAsync(d.args.rec, 0, sizeof(DualRec), x->stream));
     if (d.args.lrec) HIP_TRY(hipMemsetAsync(d.args.lrec, 0, sizeof(DualLongRec), x->stream));  // the flip counters too
@@ -324,6 +337,10 @@ int dual_switch_algorithm(spx_ctx* x, int32_t algo) {
         return fail(SPX_ERR_STATE, "the primal loop does not run with finite upper bounds (spx_set_bounds): bounded "
                     "variables are the dual simplex loop's and the bounded primal loop's (SPX_ALGO_PRIMAL_BOX); remove "
                     "the bounds first");
+    if (algo == SPX_ALGO_DUAL && x->dual.nfree > 0)
+        return fail(SPX_ERR_STATE, "the dual simplex loop does not run free columns (%lld of them, spx_set_bounds_lu): a "
+                    "non-basic free column has no dual feasible side unless d_j = 0; SPX_ALGO_PRIMAL_BOX runs them",
+                    (long long)x->dual.nfree);
     // the bounded primal loop's phase 1 does not maintain y: whichever loop takes the
     // basis gets y = c_B B^-1 (the primal loop would go on updating a stale y)
     SPX_TRY(pbox_fresh_y(x));
@@ -360,6 +377,12 @@ int dual_objective_offset(spx_ctx* x, double* zu) {
     SPX_TRY(fetch_placements(x, up));
     for (size_t j = 0; j < n; ++j)  // ascending j
         if (up[j]) *zu += c[j] * x->dual.ub[j];
+    if (!x->dual.lb.empty()) {  // shifted variables: + sum_j c_j l_j, ascending j, its own sum
+        double zl = 0.0;
+        for (size_t j = 0; j < n; ++j)
+            if (std::isfinite(x->dual.lb[j])) zl += c[j] * x->dual.lb[j];
+        *zu += zl;
+    }
     return SPX_OK;
 }
 
@@ -442,6 +465,12 @@ int spx_set_bounds(spx_ctx* x, const double* ub) {
         for (size_t j = 0; j < n; ++j)
             if (pos[j] >= 0 && e[j] < -x->opts.eps && !(ub && std::isfinite(ub[j]))) return no_feasible_side(x, e[j], j);
     }
+    // lower bounds are 0 from here on: a context that had others (spx_set_bounds_lu) is boxed, so b_eff is
+    // formed again below from b_user without the A.l term
+    d.lb.clear();
+    d.ub_user.clear();
+    d.shifted = false;
+    d.nfree = 0;
     if (!finite && !d.boxed) {  // nothing to keep: today's kernels, today's state
         d.ub.assign(n, INFINITY);
         return set_running(x);
@@ -474,8 +503,93 @@ int spx_set_bounds(spx_ctx* x, const double* ub) {
 
 int spx_get_bounds(spx_ctx* x, double* ub) {
     if (!x || !ub) return fail(SPX_ERR_ARG, "NULL argument");
-    for (size_t j = 0; j < (size_t)x->n; ++j) ub[j] = x->dual.ub.empty() ? INFINITY : x->dual.ub[j];
+    const std::vector<double>& u = x->dual.lb.empty() ? x->dual.ub : x->dual.ub_user;  // the caller's, not the range
+    for (size_t j = 0; j < (size_t)x->n; ++j) ub[j] = u.empty() ? INFINITY : u[j];
     return SPX_OK;
+}
+
+int spx_get_bounds_lu(spx_ctx* x, double* lb, double* ub) {
+    if (!x || !lb || !ub) return fail(SPX_ERR_ARG, "NULL argument");
+    for (size_t j = 0; j < (size_t)x->n; ++j) lb[j] = x->dual.lb.empty() ? 0.0 : x->dual.lb[j];
+    return spx_get_bounds(x, ub);
+}
+
+int spx_set_bounds_lu(spx_ctx* x, const double* lb, const double* ub) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    const size_t n = (size_t)x->n;
+    bool general = false;
+    int64_t nfree = 0;
+    for (size_t j = 0; j < n; ++j) {
+        const double l = lb ? lb[j] : 0.0, u = ub ? ub[j] : INFINITY;
+        if (std::isnan(l) || std::isnan(u)) return fail(SPX_ERR_ARG, "a bound of column %lld is NaN", (long long)j);
+        if (l == INFINITY) return fail(SPX_ERR_ARG, "lower bound of column %lld is +inf", (long long)j);
+        if (l > u || u == -INFINITY)
+            return fail(SPX_ERR_ARG, "lower bound %g of column %lld is above its upper bound %g", l, (long long)j, u);
+        if (l == -INFINITY && std::isfinite(u))
+            return fail(SPX_ERR_ARG, "column %lld has an upper bound %g and no lower bound: upper-only columns are not "
+                        "supported (substitute x = -x', or give a finite lower bound)", (long long)j, u);
+        general = general || l != 0.0;
+        nfree += l == -INFINITY;
+    }
+    if (!general) return spx_set_bounds(x, ub);  // lower bounds 0: the same call, the same kernels, the same bits
+    if (x->opts.nranks > 1 || x->P.row_shard)
+        return fail(SPX_ERR_STATE, "spx_set_bounds_lu needs one rank and replicated B^-1 (nranks %d%s)", x->opts.nranks,
+                    x->P.row_shard ? ", row-sharded" : "");
+    const bool pbox = x->algo == SPX_ALGO_PRIMAL_BOX;
+    if (x->algo != SPX_ALGO_DUAL && !pbox)
+        return fail(SPX_ERR_STATE, "bounds need the dual simplex loop (SPX_ALGO_DUAL) or the bounded primal loop "
+                    "(SPX_ALGO_PRIMAL_BOX): the primal loop does not run bounded variables");
+    if (x->broken) return fail(SPX_ERR_STATE, "no valid basis (a failed spx_set_basis): call spx_reset");
+    if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_bounds_lu between spx_price and spx_pivot");
+    if (nfree > 0 && !pbox)
+        return fail(SPX_ERR_STATE, "the dual simplex loop does not run free columns (%lld of them): a non-basic free "
+                    "column has no dual feasible side unless d_j = 0; SPX_ALGO_PRIMAL_BOX runs them", (long long)nfree);
+    if (nfree > 0 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "free columns (%lld of them) do not run with steepest-edge pricing "
+                    "(spx_set_primal_pricing); set SPX_PRIMAL_PRICING_DANTZIG first", (long long)nfree);
+    SPX_TRY(dual_setup(x));
+    DualState& d = x->dual;
+    std::vector<double> range(n), lsh(n);
+    bool shifted = false;
+    for (size_t j = 0; j < n; ++j) {
+        const double l = lb[j], u = ub ? ub[j] : INFINITY;  // (general: lb is not NULL)
+        lsh[j] = std::isfinite(l) ? l : 0.0;
+        range[j] = std::isfinite(u) ? u - lsh[j] : INFINITY;
+        shifted = shifted || lsh[j] != 0.0;
+    }
+    if (!pbox) {  // refused before anything changes: a column that would have no dual feasible side
+        std::vector<double> e;
+        std::vector<int32_t> pos;
+        SPX_TRY(fetch_reduced_costs(x, e, pos));
+        for (size_t j = 0; j < n; ++j)
+            if (pos[j] >= 0 && e[j] < -x->opts.eps && !std::isfinite(range[j])) return no_feasible_side(x, e[j], j);
+    }
+    pbox_on_change(x);
+    SPX_TRY(box_buffers(x));
+    if (!d.d_lsh) SPX_TRY(x->alloc(&d.d_lsh, n));
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    if (!d.boxed) {  // P.b is still the caller's b, every column at lower
+        HIP_TRY(hipMemcpy(d.b_user, x->b, (size_t)x->L * sizeof(double), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemset(d.args.at_upper, 0, n));
+    }
+    d.lb.assign(lb, lb + n);
+    d.ub_user.assign(n, INFINITY);
+    if (ub) d.ub_user.assign(ub, ub + n);
+    d.ub = range;
+    d.shifted = shifted;
+    d.nfree = nfree;
+    HIP_TRY(hipMemcpy(const_cast<double*>(d.args.ub), d.ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.d_lsh, lsh.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    // a column at an upper bound that no longer exists goes to lower
+    std::vector<int8_t> up(n);
+    HIP_TRY(hipMemcpy(up.data(), d.args.at_upper, n, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < n; ++j)
+        if (up[j] && !std::isfinite(d.ub[j])) up[j] = 0;
+    HIP_TRY(hipMemcpy(d.args.at_upper, up.data(), n, hipMemcpyHostToDevice));
+    d.boxed = true;  // the boxed kernels and b_user / b_eff, whatever the ranges are
+    feasibility_unknown(x);
+    SPX_TRY(set_running(x));
+    return pbox ? box_recompute_xb(x) : box_normalise(x, true);
 }
 
 int spx_get_primal(spx_ctx* x, double* xv, int8_t* at_upper) {
@@ -486,7 +600,12 @@ int spx_get_primal(spx_ctx* x, double* xv, int8_t* at_upper) {
     SPX_TRY(spx_get_state(x, xb.data(), bix.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
     std::vector<int8_t> up;
     SPX_TRY(fetch_placements(x, up));
-    for (size_t j = 0; j < n; ++j) xv[j] = up[j] ? x->dual.ub[j] : 0.0;
+    if (x->dual.lb.empty()) {
+        for (size_t j = 0; j < n; ++j) xv[j] = up[j] ? x->dual.ub[j] : 0.0;
+    } else {  // exactly the caller's bound (not l + (u - l)); a free column sits at 0; x_b came back unshifted
+        const DualState& d = x->dual;
+        for (size_t j = 0; j < n; ++j) xv[j] = up[j] ? d.ub_user[j] : (std::isfinite(d.lb[j]) ? d.lb[j] : 0.0);
+    }
     for (size_t i = 0; i < m; ++i) xv[(size_t)bix[i]] = xb[i];
     if (at_upper) std::memcpy(at_upper, up.data(), n);
     return SPX_OK;

@@ -31,13 +31,40 @@ int read_phase(spx_ctx* x) {
     return SPX_OK;
 }
 
+// free columns: the two arrays on first use, then is_free from the
+// bounds and lb_B from the basis (k_pbox_step_f keeps lb_B from there on)
+int pbox_free_sync(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    const size_t n = (size_t)x->n, m = (size_t)x->m, L = (size_t)x->L;
+    if (!s.fr.lb_B) {
+        SPX_TRY(x->alloc(&s.fr_flags, n));
+        s.fr.is_free = s.fr_flags;
+        SPX_TRY(x->alloc(&s.fr.lb_B, L));
+        HIP_TRY(pbox_free_prepare(x->P, s.cfg));
+    }
+    const std::vector<double>& lb = x->dual.lb;
+    std::vector<int8_t> fr(n);
+    for (size_t j = 0; j < n; ++j) fr[j] = lb[j] == -INFINITY ? 1 : 0;
+    std::vector<int64_t> bix(m);
+    std::vector<double> lbB(L, 0.0);
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(bix.data(), x->P.b_ixs, m * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < m; ++i) lbB[i] = fr[(size_t)bix[i]] ? -INFINITY : 0.0;
+    HIP_TRY(hipMemcpy(s.fr_flags, fr.data(), n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s.fr.lb_B, lbB.data(), L * sizeof(double), hipMemcpyHostToDevice));
+    return SPX_OK;
+}
+
 int pbox_check_entry(spx_ctx* x) {
     const size_t m = (size_t)x->m;
+    const bool fr = x->dual.nfree > 0;
     SPX_TRY(pbox_fresh_y(x));  // (a phase 1 that was switched off mid-way: the plain passes need y)
     SPX_TRY(box_replace_xb(x));
+    if (fr) SPX_TRY(pbox_free_sync(x));
     if (x->pbox.phase1) {
         // phase 1: a row out of its bounds is not an error; the device classifies and the passes start there
-        HIP_TRY(launch_pbox_classify(x->P, x->pbox.args, x->pbox.p1, true, x->stream));
+        if (fr) HIP_TRY(launch_pbox_classify_f(x->P, x->pbox.args, x->pbox.p1, x->pbox.fr, true, x->stream));
+        else HIP_TRY(launch_pbox_classify(x->P, x->pbox.args, x->pbox.p1, true, x->stream));
         HIP_TRY(launch_pbox_stage(x->P, x->stream));
         SPX_TRY(read_phase(x));
         x->pbox.checked = true;
@@ -50,7 +77,12 @@ int pbox_check_entry(spx_ctx* x) {
     HIP_TRY(hipMemcpy(ubB.data(), x->pbox.args.ub_B, m * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(bix.data(), x->P.b_ixs, m * sizeof(int64_t), hipMemcpyDeviceToHost));
     const double tol = x->opts.feas_tol;
+    if (fr) {  // the *_f kernels read the phase from the device: phase 2 (the rows below pass, or nothing runs)
+        HIP_TRY(hipMemsetAsync(&x->pbox.p1.ph->ninf, 0, sizeof(int32_t), x->stream));
+        x->pbox.ninf = 0;
+    }
     for (size_t i = 0; i < m; ++i) {
+        if (fr && x->dual.lb[(size_t)bix[i]] == -INFINITY) continue;  // a free basic column is within its bounds
         if (xb[i] >= -tol && xb[i] <= ubB[i] + tol) continue;
         return fail(SPX_ERR_STATE, "basis is not primal feasible (x_b %g in row %lld, basic column %lld with bounds "
                     "[0, %g], feas_tol %g): the bounded primal loop has no phase 1; SPX_ALGO_DUAL repairs it",
@@ -200,6 +232,9 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
     if (!x->pbox.checked) SPX_TRY(pbox_check_entry(x));
     PboxState& s = x->pbox;
     const bool steep = s.rule == SPX_PRIMAL_PRICING_STEEPEST;
+    const bool fr = x->dual.nfree > 0;  // free columns: every pass on the *_f kernels
+    if (fr && steep)  // (both setters refuse the combination)
+        return fail(SPX_ERR_STATE, "free columns do not run with steepest-edge pricing");
     PboxArgs se_args = s.args;
     if (steep) {
         if (s.phase1)
@@ -225,6 +260,20 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
                 HIP_TRY(launch_pbox_update(x->P, se_args, s.cfg, x->stream, u0, u1));
                 HIP_TRY(launch_pbox_step_se(x->P, se_args, s.se, x->stream));
                 HIP_TRY(launch_pbox_tau(x->P, s.se, s.cfg, x->stream, v0, v1));
+                ++x->n_eager;
+                continue;
+            }
+            if (fr) {  // k_pbox_vtb in front while the host last saw phase 1 or a stale y, as below
+                if (s.phase1 && (s.ninf > 0 || s.y_stale)) {
+                    s.y_dirty = true;
+                    hipEvent_t v0 = nullptr, v1 = nullptr;
+                    if (x->timing) SPX_TRY(vtb_events(x, &v0, &v1));
+                    HIP_TRY(launch_pbox_vtb(x->P, s.p1, s.cfg, x->stream, v0, v1));
+                }
+                HIP_TRY(launch_pbox_price_f(x->P, s.args, s.p1, s.fr, s.cfg, x->stream, p0, p1));
+                if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
+                HIP_TRY(launch_pbox_update_f(x->P, s.args, s.p1, s.fr, s.cfg, x->stream, u0, u1));
+                HIP_TRY(launch_pbox_step_f(x->P, s.args, s.p1, s.fr, x->stream));
                 ++x->n_eager;
                 continue;
             }
@@ -299,7 +348,9 @@ int pbox_on_reinvert(spx_ctx* x) {
     s.y_stale = 0;
     s.y_dirty = false;
     if (s.phase1 && s.checked && x->algo == SPX_ALGO_PRIMAL_BOX) {
-        HIP_TRY(launch_pbox_classify(x->P, s.args, s.p1, false, x->stream));
+        // (checked: lb_B is that of this basis)
+        if (x->dual.nfree > 0) HIP_TRY(launch_pbox_classify_f(x->P, s.args, s.p1, s.fr, false, x->stream));
+        else HIP_TRY(launch_pbox_classify(x->P, s.args, s.p1, false, x->stream));
         SPX_TRY(read_phase(x));
     }
     return SPX_OK;
@@ -356,6 +407,9 @@ int spx_set_primal_pricing(spx_ctx* x, int32_t rule) {
     if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.phase1)
         return fail(SPX_ERR_STATE, "spx_set_primal_pricing: steepest-edge pricing does not run with the bounded primal "
                     "loop's phase 1 (spx_set_primal_phase1); switch phase 1 off first");
+    if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->dual.nfree > 0)
+        return fail(SPX_ERR_STATE, "spx_set_primal_pricing: steepest-edge pricing does not run with free columns (%lld of "
+                    "them, spx_set_bounds_lu)", (long long)x->dual.nfree);
     if (rule != x->pbox.rule) x->pbox.se_stale = true;  // a change of rule restarts the weights
     x->pbox.rule = rule;
     return SPX_OK;

@@ -82,6 +82,19 @@ struct DualState {
     bool boxed = false;
     std::vector<double> ub;
     double* b_user = nullptr;  // L
+    // general bounds (spx_set_bounds_lu).  lb is empty (no lower
+    // bound but 0: everything above holds as it reads) or holds n lower bounds,
+    // some non-zero (-inf: a free column); then ub_user holds the caller's n
+    // upper bounds, ub (and args.ub) the ranges ub_user - lb (+inf for a free
+    // column), boxed is set whatever the ranges are, and Params::b is b_user -
+    // A lsh - the at-upper sum of the ranges (lsh = lb, 0 where -inf).  shifted
+    // <=> some lsh[j] != 0: box_sync then runs k_box_rhs_lu with d_lsh, the device
+    // copy of lsh (allocated by the first such call, never freed).  nfree counts
+    // the free columns: > 0 only while the context does not run SPX_ALGO_DUAL.
+    std::vector<double> lb, ub_user;
+    bool shifted = false;
+    int64_t nfree = 0;
+    double* d_lsh = nullptr;  // n
 };
 
 // The bounded primal loop's host state (spx_pbox.h; everything that reads or
@@ -143,6 +156,14 @@ struct PboxState {
     double* wx_S = nullptr;  // m x L
     std::vector<hipEvent_t> ev_wx;  // timing: pairs around an exact recomputation (spx_pbox_wexact_times)
     size_t n_wx = 0;
+    // free columns: fr.lb_B != nullptr  <=>  pbox_free_setup ran
+    // (is_free and lb_B, allocated by the first entry check of a context with
+    // DualState::nfree > 0; any other context allocates and launches none of it).
+    // The entry check uploads both from DualState::lb and the basis; between
+    // entry checks k_pbox_step_f keeps lb_B.  While nfree > 0 every pass runs the
+    // *_f kernels, the rule is Dantzig, and with phase1 off the device's ninf is 0.
+    spx::PboxFreeArgs fr{};
+    int8_t* fr_flags = nullptr;  // n (fr.is_free)
 };
 
 struct spx_ctx {
@@ -318,6 +339,9 @@ int box_buffers(spx_ctx* x);
 // boxed: a column at an upper bound that no longer exists goes to lower; then
 // Params::b from the placements and x_b = B^-1 Params::b (B^-1 untouched)
 int box_replace_xb(spx_ctx* x);
+// general bounds: x_b[i] += the lower bound of row i's basic column (0 for a free
+// one), on a host copy of x_b with its b_ixs; nothing without lower bounds
+void box_unshift_xb(const spx_ctx* x, double* x_b, const int64_t* b_ixs);
 
 // spx_api_pbox.cpp: all the rest of the runtime knows of the bounded primal loop
 int pbox_setup(spx_ctx* x);  // buffers and launch geometry, on first use

@@ -170,6 +170,11 @@ hipError_t launch_dual_norms(const Params& P, const DualSeArgs& D, const DualCfg
 // b_eff = b_user - sum over the non-basic columns at upper of u_j A_j (ascending
 // j, one thread per row: no atomics), and D.ub_B from b_ixs
 hipError_t launch_box_rhs(const Params& P, const DualBoxArgs& D, const double* b_user, double* b_eff, hipStream_t s);
+// shifted variables x' = x - l (D.ub = u - l, lsh = n lower bounds,
+// 0 where none): b_eff = b_user - A lsh - the at-upper sum, the columns with
+// lsh[j] != 0 or at upper only, ascending j, no atomics; D.ub_B as above
+hipError_t launch_box_rhs_lu(const Params& P, const DualBoxArgs& D, const double* lsh, const double* b_user,
+                             double* b_eff, hipStream_t s);
 // x_b = (true B^-1) P.b, the pending pivot applied in registers (k_dual_norms' form)
 hipError_t launch_box_xb(const Params& P, const DualCfg& c, hipStream_t s);
 

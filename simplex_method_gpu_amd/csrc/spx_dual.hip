@@ -469,6 +469,31 @@ __global__ __launch_bounds__(BOX_BLOCK) void k_box_rhs(Params P, DualBoxArgs D, 
     b_eff[i] = acc;
 }
 
+// k_box_rhs for shifted variables x'_j = x_j - l_j: b_eff_i = b_i
+// - sum_j l_j A_ij - sum_{j non-basic at upper} (u_j - l_j) A_ij, one pass over
+// ascending j in which a column is read only where l_j != 0 or it sits at its
+// upper bound (its lower term first); D.ub holds u - l.  The same fixed order,
+// no atomics; ub_B as k_box_rhs writes it.
+__global__ __launch_bounds__(BOX_BLOCK) void k_box_rhs_lu(Params P, DualBoxArgs D, const double* lsh,
+                                                          const double* b_user, double* b_eff) {
+    const int64_t i = (int64_t)blockIdx.x * BOX_BLOCK + threadIdx.x;
+    const int64_t m = P.m, n = P.n, L = P.L;
+    if (i >= L) return;
+    double acc = i < m ? b_user[i] : 0.0;
+    if (i < m) {
+        for (int64_t j = 0; j < n; ++j) {
+            const double lj = lsh[j];
+            const bool up = D.at_upper[j] && P.nb_pos[j] >= 0;
+            if (lj == 0.0 && !up) continue;
+            const double a = P.A[j * L + i];
+            if (lj != 0.0) acc = fma(-lj, a, acc);
+            if (up) acc = fma(-D.ub[j], a, acc);
+        }
+        D.ub_B[i] = D.ub[P.b_ixs[i]];
+    }
+    b_eff[i] = acc;
+}
+
 // One row per wave: x_b_i = (S[i] + E_i r') . b, the pending pivot applied in
 // registers as k_dual_norms does (nothing is written to B^-1).
 __global__ __launch_bounds__(DUAL_BLOCK) void k_box_xb(Params P) {
@@ -850,6 +875,13 @@ hipError_t launch_dual_norms(const Params& P, const DualSeArgs& D, const DualCfg
 hipError_t launch_box_rhs(const Params& P, const DualBoxArgs& D, const double* b_user, double* b_eff, hipStream_t s) {
     const int grid = (int)((P.L + BOX_BLOCK - 1) / BOX_BLOCK);
     hipLaunchKernelGGL(k_box_rhs, dim3(grid), dim3(BOX_BLOCK), 0, s, P, D, b_user, b_eff);
+    return hipGetLastError();
+}
+
+hipError_t launch_box_rhs_lu(const Params& P, const DualBoxArgs& D, const double* lsh, const double* b_user,
+                             double* b_eff, hipStream_t s) {
+    const int grid = (int)((P.L + BOX_BLOCK - 1) / BOX_BLOCK);
+    hipLaunchKernelGGL(k_box_rhs_lu, dim3(grid), dim3(BOX_BLOCK), 0, s, P, D, lsh, b_user, b_eff);
     return hipGetLastError();
 }
 

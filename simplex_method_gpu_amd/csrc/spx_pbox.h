@@ -162,6 +162,45 @@ hipError_t launch_pbox_update1(const Params& P, const PboxArgs& D, const Pbox1Ar
 hipError_t launch_pbox_step1(const Params& P, const PboxArgs& D, const Pbox1Args& X, hipStream_t s);
 hipError_t launch_pbox_classify(const Params& P, const PboxArgs& D, const Pbox1Args& X, bool entry, hipStream_t s);
 
+// Free columns: -inf < x_j < +inf.  A context that holds one runs
+// every pass on the *_f kernels: k_pbox_price1 / _update1 / _step1 (which read
+// the phase from the device, so one set covers both phases) with two more
+// facts, "column j is free" and "row i's basic column is free":
+//   k_pbox_price_f   is_free[j] read per column beside at_upper[j], ahead of the
+//                  column's stream; a non-basic free column sits at 0, is a
+//                  candidate when |d_j| > eps and its key is -|d_j|.  The dot is
+//                  k_pbox_price's: d_j does not depend on the grid or on where y
+//                  is read from.
+//   k_pbox_update_f  sigma_p of a free entering column is +1 for d_p < 0, else -1
+//                  (d_p from the merged partial).  lb_B[i] is requested ahead of
+//                  the stream with x_b[i], ub_B[i] and w[i]; a feasible row
+//                  enters the ratio test to its lower bound only where lb_B[i] is
+//                  finite, so a row whose basic column is free (ub_B = +inf too)
+//                  never blocks.
+//   k_pbox_step_f    a free entering column has u_p = +inf: it never flips, no row
+//                  is ST_UNBOUNDED (phase 1: ST_BREAKDOWN), a pivot puts x_b[q] =
+//                  sigma_p theta.  The commit stores lb_B[q] (-inf for a free
+//                  entering column, else 0) beside ub_B[q]; rows are classified
+//                  with both, so a free basic row has w_i = 0 and is not counted.
+//                  A leaving column is never free.
+//   k_pbox_classify_f  k_pbox_classify with lb_B.
+// Same grids and LDS sizes as the kernels they derive from (pbox_prepare's
+// PboxCfg); ordering by kernel boundaries only, no floating-point atomics.
+struct PboxFreeArgs {
+    const int8_t* is_free;  // n: 1 = the column is free
+    double* lb_B;           // L: the lower bound of row i's basic column, 0 or -inf (rows m..L-1: 0)
+};
+
+hipError_t pbox_free_prepare(const Params& P, const PboxCfg& c);  // the LDS sizes of the staged instantiations
+hipError_t launch_pbox_price_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                               const PboxCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_pbox_update_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                                const PboxCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_pbox_step_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                              hipStream_t s);
+hipError_t launch_pbox_classify_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                                  bool entry, hipStream_t s);
+
 // Steepest edge: gamma_j = 1 + ||B^-1 A_j||^2 for the non-basic
 // columns, entering column argmin -d_j^2 / gamma_j over the candidates.  A pass
 // is four steps, ordered by kernel boundaries only:

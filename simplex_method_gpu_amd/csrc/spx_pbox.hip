@@ -1036,6 +1036,461 @@ __global__ __launch_bounds__(1024) void k_pbox_classify(Params P, PboxArgs D, Pb
 }
 
 // ---------------------------------------------------------------------------
+// Free columns (spx_pbox.h)
+// ---------------------------------------------------------------------------
+namespace {
+
+// row_class with the basic column's lower bound (0, or -inf for a free column:
+// such a row is never out of its bounds)
+__device__ __forceinline__ double row_class_f(double x, double lb, double ub, double tol) {
+    return x < lb - tol ? 1.0 : (x > ub + tol ? -1.0 : 0.0);
+}
+
+}  // namespace
+
+// k_pbox_price1 with free columns: one more wave-uniform flag per column, read
+// ahead of its stream beside at_upper; a free column's key is -|d_j|.  The dot
+// is k_pbox_price's, chunk for chunk.
+template <bool LDS>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_price_f(Params P, PboxArgs D, Pbox1Args X, PboxFreeArgs F) {
+    constexpr int WAVES = PBOX_WAVES, U = 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    const DevState* st = P.st;
+    const int32_t status = st->status;
+    const int32_t cnt = st->nb_count;
+    const int32_t y_buf = st->y_buf;
+    const int64_t iter = st->iter, limit = st->limit;
+    const bool ph1 = X.ph->ninf > 0;
+    if (status != ST_RUNNING || iter >= limit) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const dbl2* y_g = reinterpret_cast<const dbl2*>(ph1 ? X.yp : (y_buf ? P.y1 : P.y0));
+    if constexpr (LDS) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) d[k] = y_g[k];
+        __syncthreads();
+    }
+    const dbl2* yv = LDS ? reinterpret_cast<const dbl2*>(dsm) : y_g;
+    const double* ys = reinterpret_cast<const double*>(yv);
+
+    double bkey = INFINITY, bd = 0.0;
+    int64_t bidx = INT64_MAX;
+    const int nwv = (int)gridDim.x * WAVES;
+    for (int s = (int)blockIdx.x * WAVES + wave; s < cnt; s += nwv) {
+        const int64_t j = P.nb_list[s];
+        const int up = D.at_upper[j];
+        const int fr = F.is_free[j];
+        const double cj = ph1 ? 0.0 : P.c[j];  // (x - 0.0 = x: exact)
+        double d;
+        if (P.slack_unit && j >= P.ns) {
+            d = ys[j - P.ns] - cj;
+        } else {
+            const dbl2* col = reinterpret_cast<const dbl2*>(P.A + j * L) + lane;
+            dbl2 cur[U], nxt[U];
+#pragma unroll
+            for (int t = 0; t < U; ++t) cur[t] = t < nch ? ld2<SPX_NT_A>(col + 64 * t) : dbl2{0.0, 0.0};
+            double d0 = 0.0, d1 = 0.0;
+            for (int c0 = 0; c0 < nch; c0 += U) {
+#pragma unroll
+                for (int t = 0; t < U; ++t)
+                    nxt[t] = c0 + U + t < nch ? ld2<SPX_NT_A>(col + 64 * (c0 + U + t)) : dbl2{0.0, 0.0};
+#pragma unroll
+                for (int t = 0; t < U; ++t) {
+                    if (c0 + t < nch) {
+                        const dbl2 w = yv[64 * (c0 + t) + lane];
+                        d0 = fma(cur[t].x, w.x, d0);
+                        d1 = fma(cur[t].y, w.y, d1);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < U; ++t) cur[t] = nxt[t];
+            }
+            d = wave_sum(d0 + d1) - cj;
+        }
+        const double key = fr ? -fabs(d) : (up ? -d : d);  // free: either direction improves
+        if (key < -P.eps && argmin_better(key, j, bkey, bidx)) {
+            bkey = key;
+            bidx = j;
+            bd = d;
+        }
+    }
+    if (lane == 0) s_red[wave] = PboxPartial{bkey, bidx, bd, 0.0};
+    __syncthreads();
+    if (tid == 0) D.parts[blockIdx.x] = merge_price<WAVES>(s_red);
+}
+
+// k_pbox_update1 with free columns: sigma_p of a free entering column is the
+// sign that improves (+1 for d_p < 0), and row i's basic column's lower bound
+// lb_B[i] (0 or -inf) is requested ahead of the stream beside x_b[i], ub_B[i]
+// and w[i]: a row whose basic column is free never blocks
+template <bool XL>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_update_f(Params P, PboxArgs D, Pbox1Args X, PboxFreeArgs F) {
+    constexpr int WAVES = PBOX_WAVES, U = 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    __shared__ ArgMinEntry s_rat[WAVES];
+    __shared__ PboxSnap Sv;
+    __shared__ int32_t s_ninf;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid == 0) {  // one reader per workgroup (k_pbox_update)
+        Sv.status = st->status;
+        Sv.it = st->iter;
+        Sv.limit = st->limit;
+        Sv.qprev = st->q;
+        Sv.aqprev = st->aq;
+        s_ninf = X.ph->ninf;
+    }
+    __syncthreads();
+    const int64_t it = Sv.it, qp = Sv.qprev;
+    const double aqp = Sv.aqprev;
+    const bool ph1 = s_ninf > 0;
+    if (Sv.status != ST_RUNNING || it >= Sv.limit) return;
+
+    double wk = INFINITY, wd = 0.0;
+    int64_t wj = INT64_MAX;
+    for (int g = tid; g < D.price_grid; g += PBOX_BLOCK) {
+        const PboxPartial v = D.parts[g];
+        if (argmin_better(v.key, v.idx, wk, wj)) {
+            wk = v.key;
+            wj = v.idx;
+            wd = v.d;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double k2 = __shfl_xor(wk, off, 64);
+        const int64_t j2 = __shfl_xor(wj, off, 64);
+        const double d2 = __shfl_xor(wd, off, 64);
+        const bool t = argmin_better(k2, j2, wk, wj);
+        wk = t ? k2 : wk;
+        wj = t ? j2 : wj;
+        wd = t ? d2 : wd;
+    }
+    if (lane == 0) s_red[wave] = PboxPartial{wk, wj, wd, 0.0};
+    __syncthreads();
+    const PboxPartial t = merge_price<WAVES>(s_red);
+    if (t.idx == INT64_MAX) {  // phase 1: the violation cannot decrease; phase 2: optimum
+        if (blockIdx.x == 0 && tid == 0) st->status = ph1 ? ST_INFEASIBLE : ST_OPTIMAL;
+        return;
+    }
+    const int64_t p = t.idx;
+    if (blockIdx.x == 0 && tid == 0) {
+        D.rec->p = p;
+        D.rec->d_p = t.d;
+        D.rec->fresh = 1;
+    }
+
+    const int64_t m = P.m, L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const bool pend = it > 0 && qp >= 0;
+    const dbl2* rp = reinterpret_cast<const dbl2*>(pend ? P.rbuf : P.zeros);
+    const dbl2* ap = reinterpret_cast<const dbl2*>(P.A + p * L);
+    if constexpr (XL) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) {
+            d[k] = rp[k];
+            d[L2 + k] = ap[k];
+        }
+        __syncthreads();
+    }
+    const dbl2* xr = XL ? reinterpret_cast<const dbl2*>(dsm) : rp;
+    const dbl2* xa = XL ? reinterpret_cast<const dbl2*>(dsm) + L2 : ap;
+
+    const int64_t i = (int64_t)blockIdx.x * WAVES + wave;
+    double rt = INFINITY;
+    int64_t ri = INT64_MAX;
+    if (i < m) {
+        const double sg = F.is_free[p] ? (t.d < 0.0 ? 1.0 : -1.0) : (D.at_upper[p] ? -1.0 : 1.0);
+        const double xi = P.x_b[i], ubi = D.ub_B[i], lbi = F.lb_B[i];
+        const double wi = ph1 ? X.w[i] : 0.0;
+        const double* a_prev = (it & 1) ? P.alpha1 : P.alpha0;
+        double* a_new = (it & 1) ? P.alpha0 : P.alpha1;
+        const double ei = pend ? eta_entry(a_prev[i], i, qp, aqp) : 0.0;
+        dbl2* row = reinterpret_cast<dbl2*>(P.B0 + i * L) + lane;
+        dbl2 cur[U], nxt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = u < nch ? ld2<SPX_NT_BLOAD>(row + 64 * u) : dbl2{0.0, 0.0};
+        double acc0 = 0.0, acc1 = 0.0;
+        for (int c0 = 0; c0 < nch; c0 += U) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                nxt[u] = c0 + U + u < nch ? ld2<SPX_NT_BLOAD>(row + 64 * (c0 + U + u)) : dbl2{0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (c0 + u < nch) {
+                    const int k = 64 * (c0 + u) + lane;
+                    const dbl2 r = xr[k], a = xa[k];
+                    dbl2 nv;
+                    nv.x = fma(ei, r.x, cur[u].x);
+                    nv.y = fma(ei, r.y, cur[u].y);
+                    st2<SPX_NT_BSTORE>(nv, row + 64 * (c0 + u));
+                    acc0 = fma(nv.x, a.x, acc0);
+                    acc1 = fma(nv.y, a.y, acc1);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        }
+        const double alpha = wave_sum(acc0 + acc1);
+        if (lane == 0) a_new[i] = alpha;
+        const double ah = sg * alpha;
+        if (wi == 0.0) {  // a feasible row: phase 2's entry; no lower bound (a free basic column): no entry
+            if (ah > D.piv_tol && lbi > -INFINITY) {
+                rt = (xi > 0.0 ? xi : 0.0) / ah;
+                ri = 2 * i;
+            } else if (ah < -D.piv_tol && ubi < INFINITY) {
+                const double gap = ubi - xi;
+                rt = (gap > 0.0 ? gap : 0.0) / (-ah);
+                ri = 2 * i + 1;
+            }
+        } else if (wi > 0.0) {  // below: blocks where it rises to 0
+            if (ah < -D.piv_tol) {
+                rt = xi / ah;
+                ri = 2 * i;
+            }
+        } else {  // above: blocks where it falls to its bound
+            if (ah > D.piv_tol) {
+                rt = (xi - ubi) / ah;
+                ri = 2 * i + 1;
+            }
+        }
+    }
+    if (lane == 0) s_rat[wave] = ArgMinEntry{rt, ri};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry b = s_rat[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            const ArgMinEntry v = s_rat[w];
+            const bool tk = argmin_better(v.val, v.idx, b.val, b.idx);
+            b.val = tk ? v.val : b.val;
+            b.idx = tk ? v.idx : b.idx;
+        }
+        D.rparts[blockIdx.x] = b;
+    }
+}
+
+// k_pbox_step1 with free columns.  A free entering column starts from 0 with
+// the sign k_pbox_update_f used and has no bound to flip to (u_p = +inf: no row
+// is ST_UNBOUNDED, in phase 1 ST_BREAKDOWN); a pivot stores lb_B[q] (-inf for a
+// free entering column, else 0) beside ub_B[q]; rows are classified with
+// lb_B.  The leaving column is never free (its row had no ratio entry), so the
+// placements after a pivot are k_pbox_step1's.
+__global__ __launch_bounds__(1024) void k_pbox_step_f(Params P, PboxArgs D, Pbox1Args X, PboxFreeArgs F) {
+    constexpr int BLOCK = 1024, WAVES = BLOCK / 64, CH = 4;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t m = P.m, L = P.L;
+    __shared__ PboxSnap S;
+    __shared__ ArgMinEntry s_red[WAVES];
+    __shared__ ArgMinEntry s_win;
+    __shared__ double s_up;
+    __shared__ int32_t s_at, s_fr;
+    __shared__ int32_t s_ninf, s_stale, s_cnt;
+    if (tid == 0) {
+        S.it = st->iter;
+        S.limit = st->limit;
+        S.status = st->status;
+        S.y_buf = st->y_buf;
+        S.cnt = st->nb_count;
+        S.fresh = D.rec->fresh;
+        S.p = D.rec->p;
+        S.d_p = D.rec->d_p;
+        s_ninf = X.ph->ninf;
+        s_stale = X.ph->y_stale;
+        s_cnt = 0;
+    }
+    __syncthreads();
+    const int64_t it = S.it;
+    if (S.status != ST_RUNNING || it >= S.limit || !S.fresh) return;
+    const bool ph1 = s_ninf > 0;
+    const double ftol = X.feas_tol;
+
+    double bv = INFINITY;
+    int64_t bi = INT64_MAX;
+    for (int g = tid; g < D.update_grid; g += BLOCK) {
+        const ArgMinEntry v = D.rparts[g];
+        if (argmin_better(v.val, v.idx, bv, bi)) {
+            bv = v.val;
+            bi = v.idx;
+        }
+    }
+    wave_argmin(bv, bi);
+    if (lane == 0) s_red[wave] = ArgMinEntry{bv, bi};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry t = s_red[0];
+        for (int w = 1; w < WAVES; ++w)
+            if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
+        s_win = t;
+        s_up = D.ub[S.p];
+        s_at = D.at_upper[S.p];
+        s_fr = F.is_free[S.p];
+    }
+    __syncthreads();
+    const double tq = s_win.val;
+    const bool none = s_win.idx == INT64_MAX;
+    const int64_t q = none ? 0 : (s_win.idx >> 1);
+    const int side = none ? 0 : (int)(s_win.idx & 1);
+    const int64_t p = S.p;
+    const double u_p = s_up;
+    const int up_p = s_at;
+    const bool fr_p = s_fr != 0;
+    const double sg = fr_p ? (S.d_p < 0.0 ? 1.0 : -1.0) : (up_p ? -1.0 : 1.0);
+    const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
+    double* a_cur = (it & 1) ? P.alpha1 : P.alpha0;
+    const bool flip = u_p < INFINITY && (none || u_p <= tq);  // (a free column: u_p = +inf)
+
+    if (flip || none) {
+        if (flip) {
+            const double dx = up_p ? -u_p : u_p;
+            const double* Ap = P.A + p * L;
+            int bad = 0;
+            for (int64_t i = tid; i < m; i += BLOCK) {
+                const double xn = fma(-u_p, sg * al[i], P.x_b[i]);
+                P.x_b[i] = xn;
+                D.b_eff[i] = fma(-dx, Ap[i], D.b_eff[i]);
+                if (ph1) {
+                    const double wv = row_class_f(xn, F.lb_B[i], D.ub_B[i], ftol);
+                    X.w[i] = wv;
+                    bad += wv != 0.0;
+                }
+            }
+            if (ph1 && bad) atomicAdd(&s_cnt, bad);  // (an integer count: order-free)
+        }
+        for (int64_t i = tid; i < L; i += BLOCK) a_cur[i] = (i == 0) ? 1.0 : 0.0;
+        __syncthreads();
+        if (tid == 0) {
+            if (flip) {
+                D.at_upper[p] = up_p ? 0 : 1;
+                D.rec->flips += 1;
+                if (ph1) {
+                    X.ph->ninf = s_cnt;
+                    X.ph->passes += 1;
+                }
+            } else {
+                st->status = ph1 ? ST_BREAKDOWN : ST_UNBOUNDED;
+            }
+            if (!ph1 && s_stale) X.ph->y_stale = 0;
+            st->q = 0;
+            st->aq = 1.0;
+            st->p = p;
+            st->min_e = S.d_p;
+            D.rec->fresh = 0;
+        }
+        return;
+    }
+
+    double* y = S.y_buf ? P.y1 : P.y0;
+    const double aq = al[q];
+    const double theta = tq, sy = -(S.d_p / aq);
+    const double x_off = up_p ? u_p : 0.0;  // (a free column sits at 0 and is never at upper)
+    const double l_p = fr_p ? -INFINITY : 0.0;
+    const bool book = tid == BLOCK - 64;
+    int64_t leave = -1;
+    double c_p = 0.0;
+    int kp = -1, last = -1;
+    if (book) {
+        leave = P.b_ixs[q];
+        c_p = P.c[p];
+        kp = P.nb_pos[p];
+        last = P.nb_list[S.cnt - 1];
+    }
+    const double* Sq = P.B0 + q * L;
+    int bad = 0;
+    for (int64_t i0 = tid; i0 < L; i0 += (int64_t)CH * BLOCK) {
+        double xv[CH], av[CH], yv[CH], rv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            xv[u] = i < m ? P.x_b[i] : 0.0;
+            av[u] = i < m ? al[i] : 0.0;
+            yv[u] = i < L ? y[i] : 0.0;
+            rv[u] = i < L ? Sq[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            if (i < m) {
+                const double xn = (i == q) ? x_off + sg * theta : fma(-theta, sg * av[u], xv[u]);
+                P.x_b[i] = xn;
+                if (ph1) {  // (row q's bounds are the entering column's: the bookkeeping lane stores them below)
+                    const double wv = row_class_f(xn, i == q ? l_p : F.lb_B[i], i == q ? u_p : D.ub_B[i], ftol);
+                    X.w[i] = wv;
+                    bad += wv != 0.0;
+                }
+            }
+            if (i < L) {
+                if (!ph1) y[i] = fma(sy, rv[u], yv[u]);
+                P.rbuf[i] = rv[u];
+            }
+        }
+    }
+    if (ph1 && bad) atomicAdd(&s_cnt, bad);
+    __syncthreads();
+    if (book) {
+        P.c_B[q] = c_p;
+        P.b_ixs[q] = p;
+        D.ub_B[q] = u_p;
+        F.lb_B[q] = l_p;
+        D.at_upper[p] = 0;
+        D.at_upper[leave] = (int8_t)side;
+        int cnt = S.cnt;
+        P.nb_list[kp] = last;
+        P.nb_pos[last] = kp;
+        P.nb_pos[p] = -1;
+        --cnt;
+        P.nb_list[cnt] = (int32_t)leave;
+        P.nb_pos[leave] = cnt;
+        ++cnt;
+        st->nb_count = cnt;
+        st->aq = aq;
+        st->s_y = sy;
+        st->y_applied = it + 1;
+        st->xb_applied = it + 1;
+        st->p = p;
+        st->q = q;
+        st->min_e = S.d_p;
+        st->iter = it + 1;
+        record_pivot(P, it, p, q);
+        D.rec->fresh = 0;
+        if (side) D.rec->to_upper += 1;
+        if (ph1) {
+            X.ph->ninf = s_cnt;
+            X.ph->passes += 1;
+            X.ph->pivots += 1;
+            X.ph->y_stale = 1;
+        } else if (s_stale) {
+            X.ph->y_stale = 0;
+        }
+    }
+}
+
+// k_pbox_classify with lb_B: a row whose basic column is free is feasible
+__global__ __launch_bounds__(1024) void k_pbox_classify_f(Params P, PboxArgs D, Pbox1Args X, PboxFreeArgs F, int entry) {
+    __shared__ int32_t s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    int bad = 0;
+    for (int64_t i = threadIdx.x; i < P.L; i += 1024) {
+        const double wv = i < P.m ? row_class_f(P.x_b[i], F.lb_B[i], D.ub_B[i], X.feas_tol) : 0.0;
+        X.w[i] = wv;
+        bad += wv != 0.0;
+    }
+    if (bad) atomicAdd(&s_cnt, bad);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        X.ph->ninf = s_cnt;
+        if (entry) X.ph->ninf0 = s_cnt;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Steepest edge (spx_pbox.h)
 // ---------------------------------------------------------------------------
 namespace {
@@ -1586,6 +2041,49 @@ hipError_t launch_pbox_step1(const Params& P, const PboxArgs& D, const Pbox1Args
 
 hipError_t launch_pbox_classify(const Params& P, const PboxArgs& D, const Pbox1Args& X, bool entry, hipStream_t s) {
     hipLaunchKernelGGL(k_pbox_classify, dim3(1), dim3(1024), 0, s, P, D, X, entry ? 1 : 0);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <typename K>
+hipError_t launch_timed_f(K kernel, int grid, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const Params& P,
+                          const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F) {
+    if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), (uint32_t)lds, s, e0, e1, 0, P, D, X, F);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(PBOX_BLOCK), lds, s, P, D, X, F);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t pbox_free_prepare(const Params& P, const PboxCfg& c) {
+    hipError_t e = hipSuccess;
+    if (c.price_lds) e = set_lds(k_pbox_price_f<true>, (size_t)P.L * 8);
+    if (e == hipSuccess && c.update_lds) e = set_lds(k_pbox_update_f<true>, (size_t)P.L * 16);
+    return e;
+}
+
+hipError_t launch_pbox_price_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                               const PboxCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    if (c.price_lds) return launch_timed_f(k_pbox_price_f<true>, c.price_grid, (size_t)P.L * 8, s, e0, e1, P, D, X, F);
+    return launch_timed_f(k_pbox_price_f<false>, c.price_grid, 0, s, e0, e1, P, D, X, F);
+}
+
+hipError_t launch_pbox_update_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                                const PboxCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    if (c.update_lds) return launch_timed_f(k_pbox_update_f<true>, c.update_grid, (size_t)P.L * 16, s, e0, e1, P, D, X, F);
+    return launch_timed_f(k_pbox_update_f<false>, c.update_grid, 0, s, e0, e1, P, D, X, F);
+}
+
+hipError_t launch_pbox_step_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_step_f, dim3(1), dim3(1024), 0, s, P, D, X, F);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_classify_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs& F,
+                                  bool entry, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_classify_f, dim3(1), dim3(1024), 0, s, P, D, X, F, entry ? 1 : 0);
     return hipGetLastError();
 }
 

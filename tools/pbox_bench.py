@@ -72,6 +72,20 @@ instead, one child process per shape:
                 fastest, and the mean wall time of a steepest-edge pass of the same
                 context over --k pivots, so the start is also quoted in passes
 
+--free measures the free-column kernels instead, in phase 1,
+where the kernels they derive from run; one child per side, the sides
+alternating:
+  p1_parent     boxed_general(m, n, seed) from the slack basis on the library
+                --parent-lib (a build of the parent commit): k_pbox_price1 /
+                k_pbox_update1
+  p1_free       the same LP with every fifth structural column free (j % 5 == 2:
+                no bounds at all), on this build: k_pbox_price_f / k_pbox_update_f
+  p1_nofree     the LP of p1_parent on this build (no free column: the parent's
+                kernels)
+  p1_parent_again, p1_free_again, p1_nofree_again
+with the ratios of the kernel times and of the pass rates to p1_parent, and
+p1_parent_again over p1_parent as the session's run-to-run spread.
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
     python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
@@ -80,6 +94,7 @@ instead, one child process per shape:
     python tools/pbox_bench.py --warm-resolve --solve-shape 1024 4096 4 --solve-shape 2048 8192 5
                                --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5 --kernel-shape 4096 16384 5
                                [--out profiles/pbox_wexact.json]
+    python tools/pbox_bench.py --free --parent-lib PATH [--out profiles/pbox_lu_c3.json]
 """
 import argparse
 import json
@@ -332,6 +347,36 @@ def run_p1_dense(a):
                                                      primal_phase1=True, timing=timing), a.k, a.warm, a.k, False)
 
 
+def run_p1_free(a):
+    """p1_dense's LP with every fifth structural column free."""
+    import numpy as np
+
+    import primal_phase1_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = primal_phase1_ref.boxed_general(a.m, a.n, a.seed)
+    ns = a.n - a.m
+    fr = np.arange(ns) % 5 == 2
+    l = np.zeros(a.n)
+    l[:ns][fr] = -np.inf
+    u[:ns][fr] = np.inf
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    res = measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, lower=l,
+                                                    upper=u, primal_phase1=True, timing=timing), a.k, a.warm, a.k, False)
+    res["free_columns"] = int(fr.sum())
+    return res
+
+
+def run_p1_parent(a):
+    """p1_dense on a build of the parent commit (SPX_LIB), which lacks the entry points this package binds since."""
+    from simplex_method_gpu_amd import _lib
+
+    for name in ("spx_set_bounds_lu", "spx_get_bounds_lu"):
+        _lib.SIGNATURES.pop(name)
+    return run_p1_dense(a)
+
+
 def run_p1_sparse(a):
     import numpy as np
 
@@ -508,10 +553,12 @@ def run_wexact_kernel(a):
             "se_passes_timed": passes, "start_in_se_passes": round(best * 1e3 / pass_us, 1)}
 
 
-def child(a, role, pricing="dantzig", se_lds=None):
+def child(a, role, pricing="dantzig", se_lds=None, lib=None):
     env = dict(os.environ)
     if se_lds is not None:
         env["SPX_PBOX_SE_LDS"] = str(se_lds)
+    if lib is not None:
+        env["SPX_LIB"] = os.path.abspath(lib)
     cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--primal-pricing", pricing, "--m", str(a.m), "--n", str(a.n),
            "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--refactor", str(a.refactor),
            "--sparse-every", str(a.sparse_every), "--sparse-chunk", str(a.sparse_chunk)]
@@ -549,14 +596,17 @@ def main():
                     help="the exact weight start of a warm basis instead (DESIGN.md 7i)")
     ap.add_argument("--kernel-shape", type=int, nargs=3, action="append", default=[], metavar=("M", "N", "SEED"),
                     help="with --warm-resolve: shapes at which the exact recomputation alone is timed")
+    ap.add_argument("--free", action="store_true", help="the free-column kernels against the parent build instead (DESIGN.md 7j)")
+    ap.add_argument("--parent-lib", default=None, help="with --free: libsimplex.so built from the parent commit")
     ap.add_argument("--role", default=None,
                     choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se",
-                             "warm_resolve", "wexact_kernel"])
+                             "warm_resolve", "wexact_kernel", "p1_free", "p1_parent"])
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
         run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
                "pbox_flag": run_pbox_flag, "p1_dense": run_p1_dense, "p1_sparse": run_p1_sparse,
-               "pbox_se": run_pbox_se, "warm_resolve": run_warm_resolve, "wexact_kernel": run_wexact_kernel}[a.role]
+               "pbox_se": run_pbox_se, "warm_resolve": run_warm_resolve, "wexact_kernel": run_wexact_kernel,
+               "p1_free": run_p1_free, "p1_parent": run_p1_parent}[a.role]
         print(json.dumps(run(a)), flush=True)
         return
     if a.warm_resolve:
@@ -596,6 +646,23 @@ def main():
                                      "steepest_again": runs[3][i],
                                      "pivot_ratio": round(dz["pivots"] / se["pivots"], 2),
                                      "time_ratio": round(dz["seconds"] / se["seconds"], 2)})
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
+    if a.free:
+        if not a.parent_lib or not os.path.exists(a.parent_lib):
+            ap.error("--free needs --parent-lib: a libsimplex.so built from the parent commit")
+        for key, role in (("p1_parent", "p1_parent"), ("p1_free", "p1_free"), ("p1_nofree", "p1_dense"),
+                          ("p1_parent_again", "p1_parent"), ("p1_free_again", "p1_free"), ("p1_nofree_again", "p1_dense")):
+            res[key] = child(a, role, lib=a.parent_lib if role == "p1_parent" else None)
+            sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+            sys.stderr.flush()
+        keys = ("vtb_us", "price_us", "update_us", "passes_per_s")
+        base = res["p1_parent"]
+        for key in ("p1_free", "p1_nofree", "p1_parent_again", "p1_free_again", "p1_nofree_again"):
+            res[f"{key}_over_p1_parent"] = {k: round(res[key][k] / base[k], 4) for k in keys}
         print(json.dumps(res), flush=True)
         if a.out:
             with open(a.out, "w") as f:
