@@ -98,6 +98,30 @@ def moved_lower(l, u, seed):
     return l2
 
 
+def lower_twin(A, b, u, seed):
+    """(l, b2, u2): the LP (A, b, c, 0 <= x <= u) of a neighbouring golden file
+    moved to lower bounds l: l_j ~ U[-0.5, 0.5] on about 40 % of all n columns,
+    slacks included, 0 elsewhere; b2 = b + A.l; u2 = u + l (+inf stays).  No
+    column becomes fixed or free.  The shifted problem of (A, b2, c, l, u2) is
+    the neighbour's own LP up to rounding of order 1e-14, so, its golden argmins
+    being separated by 1e-6, the twin walks the neighbour's golden passes."""
+    n = A.shape[1]
+    r = np.random.default_rng(seed + 9700)
+    pick = r.uniform(0, 1, n) < 0.4
+    l = np.where(pick, r.uniform(-0.5, 0.5, n), 0.0)
+    return l, b + A @ l, np.where(np.isfinite(u), u + l, np.inf)
+
+
+def shifted(A, b, l, u):
+    """(b_eff, range) as the device forms them from finite lower bounds: b_eff =
+    b - sum_j l_j A_j over l_j != 0 in ascending j, one product and one
+    subtraction per entry (no fma); range_j = fl(u_j - l_j), +inf stays."""
+    beff = np.array(b, dtype=np.float64)
+    for j in np.flatnonzero(l != 0.0):
+        beff = beff - l[j] * A[:, j]
+    return beff, np.where(np.isfinite(u), u - l, np.inf)
+
+
 def tiny_unbounded_free():
     """max -x0, x0 free, one row x0 + s = 1: x0 falls without a bound (the slack
     rises, nothing blocks)."""
@@ -110,6 +134,12 @@ class LuResult(Phase1Result):
     """Phase1Result in the caller's variables: x_b includes the basic columns'
     lower bounds and z the sum c.l; `x_shifted` is the loop's own x_b."""
     x_shifted: np.ndarray = None
+    free_entered: int = 0   # pivots whose entering column is free
+    free_basic: int = 0     # free columns in the final basis
+    fixed_flips: int = 0    # passes in which a fixed column (u_j = l_j) enters and flips at once
+    ray_col: int = -1       # UNBOUNDED: the entering column that no row blocks
+    # `ties` has one key more than Phase1Result's: "free_price", the passes whose pricing tie has a free column among
+    # the tied minima
 
     def primal_lu(self, l, u):
         x = np.where(self.at_upper, u, np.where(np.isfinite(l), l, 0.0))
@@ -161,7 +191,9 @@ def primal_simplex_lu(A, b, c, l, u, basis=None, at_upper=None, eps=1e-7, feas_t
     trace = []
     gap_price = gap_ratio = gap_flip = np.inf
     flips = to_upper = p1_passes = p1_pivots = 0
-    ties = {"price": 0, "ratio": 0, "flip": 0, "p1_price": 0, "p1_ratio": 0, "p1_flip": 0}
+    ties = {"price": 0, "ratio": 0, "flip": 0, "p1_price": 0, "p1_ratio": 0, "p1_flip": 0, "free_price": 0}
+    free_entered = fixed_flips = 0
+    ray_col = -1
     integral = True
     hist = []
     it = 0
@@ -179,7 +211,7 @@ def primal_simplex_lu(A, b, c, l, u, basis=None, at_upper=None, eps=1e-7, feas_t
         return LuResult(status, z + (zu + zl), it, b_ixs.copy(), x_b + lsh[b_ixs], up.copy(),
                         trace, float(gap_price), float(gap_ratio), float(gap_flip), flips, to_upper, p1_passes,
                         p1_pivots, ninf0, ninf, hist, c_B @ Binv if y_stale else y.copy(), Binv.copy(), ties, integral,
-                        x_b.copy())
+                        x_b.copy(), free_entered, int(np.count_nonzero(free[b_ixs])), fixed_flips, ray_col)
 
     def tie(name, hit, ph1):
         ties[name] += int(hit)
@@ -207,6 +239,7 @@ def primal_simplex_lu(A, b, c, l, u, basis=None, at_upper=None, eps=1e-7, feas_t
         key = np.where(cand, key, np.inf)
         p = int(np.argmin(key))
         tie("price", tied(key), ph1)
+        ties["free_price"] += int(tied(key) and bool(np.any(free & (key == key[p]))))
         if cand.sum() > 1:
             two = np.partition(key, 1)[:2]
             gap_price = min(gap_price, _rel_gap(two[0], two[1]))
@@ -248,6 +281,7 @@ def primal_simplex_lu(A, b, c, l, u, basis=None, at_upper=None, eps=1e-7, feas_t
             x_b = x_b - u_p * ahat
             up[p] = not up[p]
             flips += 1
+            fixed_flips += int(u_p == 0.0)
             integral = integral and whole(x_b)
             if ph1:
                 w = _classify(x_b, lo0[b_ixs], u[b_ixs], feas_tol)
@@ -257,6 +291,7 @@ def primal_simplex_lu(A, b, c, l, u, basis=None, at_upper=None, eps=1e-7, feas_t
         if q < 0:
             p1_passes -= int(ph1)  # (the pass committed nothing)
             status = BREAKDOWN if ph1 else UNBOUNDED
+            ray_col = p
             break
         # 6. pivot
         theta = t[q]
@@ -277,6 +312,7 @@ def primal_simplex_lu(A, b, c, l, u, basis=None, at_upper=None, eps=1e-7, feas_t
         to_upper += int(hi[q])
         basic[p] = True
         up[p] = False
+        free_entered += int(free[p])
         b_ixs[q] = p
         Binv = Binv - np.outer(alpha / aq, rho)
         Binv[q] = rho / aq

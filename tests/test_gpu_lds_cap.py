@@ -18,7 +18,13 @@ Context.loop_layout() that it runs the layout it means to run:
    40 pivots and again after solve() everything equals the default layout's bit
    for bit; the solve also meets the golden files.  The pricing grids need no
    pinning: 768 non-basic columns ask for 96 workgroups, below any occupancy
-   limit, with or without LDS.
+   limit, with or without LDS.  The `pbox_free` case (general bounds with free
+   columns, tests/test_gpu_primal_lu.py's LPs) runs the *_f kernels: the library
+   cannot report which instantiation of them it launched, but loop_layout()'s
+   pbox_* fields govern the *_f launches too (pbox_free_prepare,
+   launch_pbox_price_f and launch_pbox_update_f read the two flags that
+   pbox_prepare set), so pbox_update_lds == 0 is k_pbox_update_f<false> and
+   pbox_price_lds == 0 is k_pbox_price_f<false>.
 2. Dense slacks.  SPX_DENSE_SLACKS=1 streams a slack column like any other; a
    unit column streamed densely contributes exact zeros, so the same equality
    holds at 130 x 390.  The exception is refresh_primal_weights(): the slack
@@ -62,6 +68,7 @@ import test_gpu_dual_se as t_se
 import test_gpu_primal_box as t_pbox
 import test_gpu_primal_box_se as t_pse
 import test_gpu_primal_box_wexact as t_wx
+import test_gpu_primal_lu as t_lu
 import test_gpu_primal_phase1 as t_p1
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +172,10 @@ def _ck_p1(spx, shape, r, tp, tq, x, up, cnt):
     t_p1._check_optimum(spx, r, x, up, A, b, c, u, g["highs_z"])
 
 
+def _ck_free(spx, shape, r, tp, tq, x, up, cnt):
+    t_lu._check_against_golden(spx, _by_shape("primal_lu_optima.json")[shape], t_lu._lp(*shape), r, tp, tq, x, up, *cnt)
+
+
 CASES = [
     Case("dual_dantzig", "dual", False, _mk_dual, _ck_dual, boxed=False),
     Case("dual_steepest", "dual", True, lambda spx, m, n, seed: t_se._ctx(spx, m, n, seed), _ck_se, "dual",
@@ -175,6 +186,8 @@ CASES = [
     Case("pbox_dantzig", "pbox", False, lambda spx, m, n, seed: t_pbox._ctx(spx, m, n, seed), _ck_pbox, None,
          ("primal_flips",)),
     Case("pbox_phase1", "pbox", False, lambda spx, m, n, seed: t_p1._ctx(spx, t_p1._lp(m, n, seed)), _ck_p1, None,
+         ("primal_flips", "primal_phase1")),
+    Case("pbox_free", "pbox", False, lambda spx, m, n, seed: t_lu._ctx(spx, t_lu._lp(m, n, seed)), _ck_free, None,
          ("primal_flips", "primal_phase1")),
     Case("pbox_steepest", "pbox", True, lambda spx, m, n, seed: t_pse._ctx(spx, m, n, seed), _ck_pse, "primal",
          ("primal_flips",)),

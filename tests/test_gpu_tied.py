@@ -1,5 +1,9 @@
 """GPU: exact ties in the dual loop (Dantzig and steepest-edge rows), the boxed
-dual loop, the long-step ratio test, the bounded primal loop and its phase 1.
+dual loop, the long-step ratio test, the bounded primal loop, its phase 1 and
+the free-column rules of general bounds (the *_f kernels: the key -|d_j| of a
+free column under the common argmin, sigma_p from the sign of d_p, a row whose
+basic column is free never blocks, a fixed column flips at once; tied_lp.tied_lu
+has integer lower bounds, fixed columns and free columns of both cost signs).
 
 The LPs are the integer interval-matrix LPs of tests/tied_lp.py: A = [+-U | I]
 is totally unimodular and b, c, u are integers, so every x_b, y, B^-1 entry,
@@ -41,19 +45,23 @@ _REFS = {}
 
 
 def _case(g):
-    """((A_cols (n, m), b, c, u), the reference's result), computed once per case."""
+    """((A_cols (n, m), b, c, u), the reference's result), computed once per
+    case; (A_cols, b, c, l, u) for the general-bounds variants."""
     k = (g["variant"], g["m"])
     if k not in _REFS:
         lp = tied_lp.case_lp(g["variant"], g["m"], g["n"], g["seed"], bool(g["mixed"]))
         r = tied_lp.case_ref(g["variant"], lp, trace_cap=200)
-        _REFS[k] = ((np.ascontiguousarray(lp[0].T), lp[1], lp[2], lp[3]), r)
+        _REFS[k] = ((np.ascontiguousarray(lp[0].T), *lp[1:]), r)
     return _REFS[k]
 
 
 def _ctx(spx, variant, lp, **kw):
     """The arguments the sibling files use for the variant's loop."""
-    At, b, c, u = lp
     kw.setdefault("trace", 200)
+    if variant in tied_lp.LU_VARIANTS:
+        At, b, c, l, u = lp
+        return spx.Context(At, b, c, algorithm=spx.ALGO_PRIMAL_BOX, lower=l, upper=u, primal_phase1=True, **kw)
+    At, b, c, u = lp
     rule = spx.DUAL_PRICING_STEEPEST if variant.endswith("steepest") else spx.DUAL_PRICING_DANTZIG
     if variant.startswith("dual_"):
         return spx.Context(At, b, c, window=-1, algorithm=spx.ALGO_DUAL, dual_pricing=rule, **kw)
@@ -73,13 +81,14 @@ def _run_and_check(spx, g, **kw):
         r = ctx.solve(g["ref_pivots"] + MARGIN)
         tp, tq = ctx.trace()
         s = ctx.state(binv=True)
-        up = ctx.primal()[1] if boxed else np.zeros(g["n"], dtype=bool)
+        x, up = ctx.primal() if boxed else (None, np.zeros(g["n"], dtype=bool))
         dflips, pflips, ph = ctx.dual_flips(), ctx.primal_flips(), ctx.primal_phase1()
     print(f"{variant} {g['m']}x{g['n']} {kw}: status {int(r.status)} z={r.z} (HiGHS {g['highs_z']}) pivots={r.pivots} "
           f"(reference {g['ref_pivots']}) dual flips {dflips} primal flips {pflips} phase 1 {ph}; ties {g['ties']}")
     # the golden record, the live reference and the run agree on what is compared
     assert ref.status == g["ref_status"] and ref.pivots == g["ref_pivots"] and ref.integral
-    want = spx.SolveStatus.Infeasible if g["ref_status"] == "infeasible" else spx.SolveStatus.OptimumFound
+    want = {"infeasible": spx.SolveStatus.Infeasible, "unbounded": spx.SolveStatus.Unbounded,
+            "optimum": spx.SolveStatus.OptimumFound}[g["ref_status"]]
     assert r.status == want, r.status
     assert r.pivots == g["ref_pivots"], (r.pivots, g["ref_pivots"])
     k = min(g["ref_pivots"], 200)
@@ -91,11 +100,12 @@ def _run_and_check(spx, g, **kw):
         assert dflips == (g["flips"], g["flip_passes"], g["max_flips"]), dflips
     else:
         assert dflips == (0, 0, 0), dflips
-    if variant in ("pbox", "phase1", "phase1_infeasible"):
+    lu = variant in tied_lp.LU_VARIANTS
+    if variant in ("pbox", "phase1", "phase1_infeasible") or lu:
         assert pflips == (g["flips"], g["to_upper"]), pflips
     else:
         assert pflips == (0, 0), pflips
-    if variant.startswith("phase1"):
+    if variant.startswith("phase1") or lu:
         assert ph == (g["p1_passes"], g["p1_pivots"], g["ninf0"], g["ninf"]), ph
     else:
         assert ph == (0, 0, 0, 0), ph
@@ -104,7 +114,9 @@ def _run_and_check(spx, g, **kw):
     for name, got, exp in (("x_b", s["x_b"], ref.x_b), ("y", s["y"], ref.y), ("binv", s["binv"], ref.Binv)):
         assert np.array_equal(got, np.rint(got)), name  # integral
         assert np.array_equal(got, exp), (name, float(np.max(np.abs(got - exp))))
-    assert np.array_equal(r.x_b, ref.x_b)
+    assert np.array_equal(r.x_b, ref.x_b)  # (general bounds: both in the caller's variables, l included)
+    if lu:
+        assert np.array_equal(x, ref.primal_lu(lp[3], lp[4]))  # a non-basic column exactly l_j, u_j or 0 (free)
 
 
 @pytest.mark.parametrize("g", GOLDEN, ids=IDS)
@@ -128,6 +140,25 @@ def test_walk_from_global_memory(spx, monkeypatch, g):
     """k_dual_long's path that reads the keys from global memory in every round
     walks the same tied keys in the same (key, column) order."""
     monkeypatch.setenv("SPX_DUAL_LONG_GLOBAL", "1")
+    _run_and_check(spx, g)
+
+
+FREE_130 = [g for g in AT_130 if g["variant"] == "free"]
+
+
+@pytest.mark.parametrize("g", FREE_130, ids=[g["variant"] for g in FREE_130])
+def test_free_from_global_memory(spx, monkeypatch, g):
+    """SPX_PBOX_LDS_CAP=1000 at L = 256 (vectors of 2048 and 4096 bytes): y and
+    the update's pending row and A_p are read from global memory, so the exact
+    ties go through k_pbox_price_f<false> and k_pbox_update_f<false>
+    (loop_layout()'s pbox_* fields govern the *_f launches too)."""
+    monkeypatch.setenv("SPX_PBOX_LDS_CAP", "1000")
+    lp, _ = _case(g)
+    with _ctx(spx, g["variant"], lp) as ctx:
+        ctx.iterate(1)
+        lay = ctx.loop_layout()
+    print(f"free 130x390 under SPX_PBOX_LDS_CAP=1000: layout {lay}")
+    assert lay["pbox_price_lds"] == 0 and lay["pbox_update_lds"] == 0, lay
     _run_and_check(spx, g)
 
 

@@ -1,5 +1,6 @@
 """CPU: exact ties in the dual, boxed dual, long-step, bounded primal and
-phase-1 loops.  The numpy restatements (tests/*_ref.py, through
+phase-1 loops, and under general bounds with free columns.  The numpy
+restatements (tests/*_ref.py, through
 tests/tied_lp.py case_ref) on the integer interval-matrix LPs of
 tests/tied_lp.py against their golden file (tests/golden/tied_optima.json,
 written by tests/golden/make_golden_tied.py): the recorded passes, HiGHS's
@@ -29,12 +30,13 @@ with open(os.path.join(ROOT, "tests", "golden", "tied_optima.json")) as _f:
     GOLDEN = json.load(_f)["cases"]
 IDS = [f"{g['variant']}-{g['m']}x{g['n']}" for g in GOLDEN]
 COUNTERS = ("to_upper", "placed", "flips", "flip_passes", "max_flips", "walk_run", "p1_passes", "p1_pivots", "ninf0",
-            "ninf")
+            "ninf", "free_entered", "free_basic", "fixed_flips", "ray_col")
 
 
 def test_golden_covers_every_variant_and_shape():
     assert [(g["variant"], g["m"], g["n"]) for g in GOLDEN] == \
-        [(v, m, n) for v in tied_lp.VARIANTS for (m, n) in tied_lp.SHAPES]
+        [(v, m, n) for v in tied_lp.VARIANTS for (m, n) in tied_lp.shapes(v)]
+    assert all(tied_lp.shapes(v) == tied_lp.SHAPES for v in tied_lp.VARIANTS if v != "free_unbounded")
 
 
 @pytest.mark.parametrize("g", GOLDEN, ids=IDS)
@@ -68,6 +70,30 @@ def test_every_tie_rule_is_exercised(g):
     assert all(v >= 1 for v in g["ties"].values()), g["ties"]
     if g["variant"].startswith("long_"):
         assert g["walk_run"] >= 3 and g["flips"] > 0
+
+
+LU = [g for g in GOLDEN if g["variant"] in tied_lp.LU_VARIANTS]
+
+
+@pytest.mark.parametrize("g", LU, ids=[i for g, i in zip(GOLDEN, IDS) if g["variant"] in tied_lp.LU_VARIANTS])
+def test_free_rules_are_exercised(g):
+    """At every shape of the general-bounds variants: a free column enters and
+    one is basic at the end, a pricing tie has a free column among the tied
+    minima, a fixed column enters and flips at once; the unbounded case ends on
+    a free entering column.  The LP itself has fixed columns and free columns
+    and, at 65 x 200 and larger (7 x 20 has three free columns and one fixed),
+    lower bounds and free columns' costs of both signs."""
+    A, b, c, l, u = tied_lp.case_lp(g["variant"], g["m"], g["n"], g["seed"])
+    free = np.isneginf(l)
+    assert free.any() and np.all(np.isposinf(u[free])) and np.any(l == u)
+    if g["m"] >= 65:
+        assert np.any(c[free] > 0) and np.any(c[free] < 0) and np.any(l[~free] < 0) and np.any(l[~free] > 0)
+    assert np.all(np.isfinite(u[~free]))  # every other column, slacks included, has a finite range
+    assert g["free_entered"] > 0 and g["free_basic"] > 0 and g["fixed_flips"] > 0 and g["ties"]["free_price"] > 0
+    if g["variant"] == "free_unbounded":
+        assert g["ref_status"] == "unbounded" and free[g["ray_col"]]
+    else:
+        assert g["ref_status"] == "optimum" and g["ray_col"] == -1
 
 
 def test_exact_capacity_is_an_optimum():

@@ -15,7 +15,8 @@ unimodularity) can change one bit: the first-index tie rules of
 include/simplex.h are the only thing left that decides a pass.
 
 Layout as in the other *_ref.py files: A is m x n with the slack identity in
-its last m columns, maximise c.x, 0 <= x <= u (u has n entries, +inf = none).
+its last m columns, maximise c.x, 0 <= x <= u (u has n entries, +inf = none);
+tied_lu has general bounds l <= x <= u (l_j = -inf and u_j = +inf: free).
 All values are float64 integers.
 """
 import numpy as np
@@ -25,6 +26,7 @@ import dual_long_ref
 import dual_ref
 import dual_se_ref
 import primal_box_ref
+import primal_lu_ref
 import primal_phase1_ref
 
 # the traced shapes of dual_ref.SHAPES
@@ -40,11 +42,23 @@ VARIANTS = {
     "pbox": ("price", "ratio", "flip"),
     "phase1": ("price", "ratio", "flip", "p1_price", "p1_ratio", "p1_flip"),
     "phase1_infeasible": ("p1_price", "p1_ratio", "p1_flip"),
+    "free": ("price", "ratio", "flip", "free_price"),
+    "free_unbounded": ("price", "free_price"),
 }
+# the general-bounds variants (l <= x <= u: case_lp returns (A, b, c, l, u)); free_unbounded has one case only
+LU_VARIANTS = ("free", "free_unbounded")
+UNBOUNDED_SHAPES = [(65, 200)]
+
+
+def shapes(variant):
+    """The shapes at which the golden file holds a case of the variant."""
+    return UNBOUNDED_SHAPES if variant == "free_unbounded" else SHAPES
 
 
 def case_lp(variant, m, n, seed, mixed=False):
-    """(A, b, c, u) of one golden case."""
+    """(A, b, c, u) of one golden case; (A, b, c, l, u) for the LU_VARIANTS."""
+    if variant in LU_VARIANTS:
+        return tied_lu(m, n, seed, disjoint=variant == "free")
     if variant.startswith("dual_"):
         return tied_covering(m, n, seed, False)
     if variant.startswith(("box_", "long_")):
@@ -56,6 +70,8 @@ def case_lp(variant, m, n, seed, mixed=False):
 
 def case_ref(variant, lp, **kw):
     """The numpy reference of the variant's loop on (A, b, c, u)."""
+    if variant in LU_VARIANTS:
+        return primal_lu_ref.primal_simplex_lu(*lp, **kw)
     A, b, c, u = lp
     rule = dual_box_ref.STEEPEST if variant.endswith("steepest") else dual_box_ref.DANTZIG
     if variant == "dual_dantzig":
@@ -144,6 +160,64 @@ def tied_general(m, n, seed, infeasible=False):
     if infeasible:
         b = np.where(ge, b - 40.0, b)
     return A, b, c, u
+
+
+def tied_lu(m, n, seed, disjoint=True):
+    """tied_general with general integer bounds l <= x <= u, returned as (A, b,
+    c, l, u).  Structural column j: j % 5 == 2 is free with a cost in {-3..3};
+    else j % 11 == 3 is fixed at an integer in {-2..2}; else it has a finite
+    integer range (tied_general's u_j, or 1..3 where that is +inf) and, with
+    probability 1/3, a lower bound in {-2..2} that its range sits on.  Every
+    slack gets an upper bound in {1..4}: all rows are ranged.  With `disjoint`
+    the free columns' runs of rows are replaced by pairwise disjoint runs (1..4
+    rows each, in the rows' own signs): a free column then cannot cancel
+    against another column along its run, and with every other column and every
+    row bounded the LP is bounded.  Without it the free columns keep
+    tied_general's overlapping runs and the LP is almost always unbounded.  A
+    is still an interval matrix with rows negated next to the identity, so
+    totally unimodular.  b = A x0 for an integer x0 within the bounds (a free
+    column's x0 in {-2..2}, the slacks' within theirs): feasible, and all of b,
+    c, l, u are integers."""
+    ns = n - m
+    A, _, c, u = tied_general(m, n, seed)
+    r = np.random.default_rng(seed + 8500)
+    A = A.copy()
+    c = c.copy()
+    u = u.copy()
+    j = np.arange(ns)
+    is_free = j % 5 == 2
+    is_fixed = ~is_free & (j % 11 == 3)
+    rng_ = np.where(np.isfinite(u[:ns]), u[:ns], r.integers(1, 4, ns).astype(np.float64))
+    lo = r.integers(-2, 3, ns).astype(np.float64)
+    has_lo = r.uniform(0, 1, ns) < 1.0 / 3.0
+    fx = r.integers(-2, 3, ns).astype(np.float64)
+    cf = r.integers(-3, 4, ns).astype(np.float64)
+    su = r.integers(1, 5, m).astype(np.float64)
+    nf = int(is_free.sum())
+    start = np.sort(r.choice(m, size=nf, replace=False))
+    ln = r.integers(1, 5, nf)
+    order = r.permutation(nf)
+    xf = r.integers(-2, 3, ns).astype(np.float64)
+    frac = r.uniform(0, 1, n)
+    l = np.zeros(n)
+    l[:ns] = np.where(is_fixed, fx, np.where(has_lo, lo, 0.0))
+    u[:ns] = np.where(is_fixed, fx, l[:ns] + rng_)
+    x0 = np.empty(n)
+    x0[:ns] = np.where(is_free, xf, l[:ns] + np.floor(frac[:ns] * (u[:ns] - l[:ns] + 1.0)))
+    x0[ns:] = np.floor(frac[ns:] * (su + 1.0))
+    l[:ns][is_free] = -np.inf
+    u[:ns][is_free] = np.inf
+    u[ns:] = su
+    c[:ns][is_free] = cf[is_free]
+    if disjoint:
+        sign = A[:, :ns].sum(axis=1)  # a >= row's entries are -1
+        sign = np.where(sign < 0, -1.0, 1.0)
+        end = np.minimum(np.append(start[1:], m), start + ln)
+        for k, col in enumerate(np.flatnonzero(is_free)):
+            a, e = start[order[k]], end[order[k]]
+            A[:, col] = 0.0
+            A[a:e, col] = sign[a:e]
+    return A, A @ x0, c, l, u
 
 
 def exact_capacity():
