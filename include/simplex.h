@@ -591,6 +591,43 @@ int spx_set_primal_weight_init(spx_ctx* ctx, int32_t mode);
  * SPX_PRIMAL_PRICING_DANTZIG or outside SPX_ALGO_PRIMAL_BOX. */
 int spx_refresh_primal_weights(spx_ctx* ctx);
 
+/* Sensitivity ranging at the optimum: how far one cost
+ * coefficient or one right-hand side may move, everything else fixed, before
+ * the optimal basis changes, and what blocks it.  Conventions are the bounded
+ * loops': maximise c.x, d = y.A - c, sigma_k = +1 for a non-basic column at its
+ * lower bound and -1 at its upper bound, optimal means sigma_k d_k >= 0; tol =
+ * opts.piv_tol, s_k = max(sigma_k d_k, 0).  Every result is a non-negative delta
+ * (c_j may go down by down[j] and up by up[j]), +inf where nothing blocks, with
+ * the index of what blocks (-1: nothing).  The index arrays may be NULL.
+ *
+ * spx_ranging_cost, n entries each.  Non-basic column j at lower: up = s_j, down
+ * = +inf; at upper: down = s_j, up = +inf; free: both 0; the blocking column is
+ * j itself.  Basic in row i: with T_ik = (row i of B^-1).A_k over the non-basic
+ * k and g_k = sigma_k T_ik, up = min s_k / -g_k over g_k < -tol and down = min
+ * s_k / g_k over g_k > tol; a free non-basic k with |T_ik| > tol blocks both at
+ * 0; block_* is the entering column k, the smallest k on equal ratios.
+ *
+ * spx_ranging_rhs, m entries each.  With beta = column r of B^-1, x_i the basic
+ * values clamped into [0, ub_B[i]] (general bounds: the shifted problem's values
+ * and ranges): beta_i > tol blocks down at x_i / beta_i and, ub_B[i] finite, up at
+ * (ub_B[i] - x_i) / beta_i; beta_i < -tol blocks up at x_i / -beta_i and, ub_B[i]
+ * finite, down at (ub_B[i] - x_i) / -beta_i; a row whose basic column is free
+ * never blocks.  leave_* = 2 row + side of the leaving row, side 1 = it leaves to
+ * its upper bound; the smallest 2 row + side on equal ratios.
+ *
+ * Both run under SPX_ALGO_DUAL and SPX_ALGO_PRIMAL_BOX, one rank, explicit
+ * replicated B^-1, with any bounds and pricing rule those loops take.
+ * SPX_ERR_STATE, with nothing changed, unless the context's last status is
+ * SPX_STATUS_OPTIMUM_FOUND and nothing was set since (spx_set_rhs / _cost /
+ * _bounds / _bounds_lu / _basis / _algorithm and spx_reset all clear it), under
+ * SPX_ALGO_PRIMAL (switch with spx_set_algorithm and solve), with more than one
+ * rank or row-sharded B^-1.  A call changes nothing a later pass reads: basis,
+ * placements, x_b, y, B^-1 and its pending pivot, steepest-edge weights and their
+ * pending recurrence, pivot count and status are kept.  Buffers are allocated
+ * by the first call; a context that never asks allocates and launches nothing. */
+int spx_ranging_cost(spx_ctx* ctx, double* down, double* up, int64_t* block_down, int64_t* block_up);
+int spx_ranging_rhs(spx_ctx* ctx, double* down, double* up, int64_t* leave_down, int64_t* leave_up);
+
 /* Phase-1 counters of the bounded primal loop, kept on the device by the kernel
  * that commits the pass: out[0] phase-1 passes since spx_create or spx_reset
  * (flip passes included), out[1] phase-1 pivots, out[2] rows out of their
@@ -715,6 +752,12 @@ int spx_pbox_vtb_times(spx_ctx* ctx, double* ms, int64_t* launches);
  * spx_refresh_primal_weights; B^-1 brought current, the product, the slack
  * norms and the sum) since the last call (resets). */
 int spx_pbox_wexact_times(spx_ctx* ctx, double* ms, int64_t* launches);
+
+/* With SPX_FLAG_TIMING: total device milliseconds and count, since the last call
+ * (resets), of [0] the cost rangings (reduced costs, B^-1 brought current, the
+ * gather, the product and the merge) and [1] the right-hand-side rangings (B^-1
+ * brought current, the stream and the merge). */
+int spx_ranging_times(spx_ctx* ctx, double ms[2], int64_t launches[2]);
 
 /* With SPX_FLAG_TIMING: device milliseconds summed since the last call (resets)
  * of out[0] the pricing kernel, out[1] pricing + the cross-rank MINLOC

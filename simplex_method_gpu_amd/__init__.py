@@ -17,6 +17,7 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass
 from enum import IntEnum
+from typing import NamedTuple
 
 import numpy as np
 
@@ -29,7 +30,8 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST",
            "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX",
            "FLAG_PRIMAL_PHASE1", "PRIMAL_PRICING_DANTZIG", "PRIMAL_PRICING_STEEPEST", "FLAG_PRIMAL_STEEPEST",
-           "PRIMAL_WEIGHTS_REFERENCE", "PRIMAL_WEIGHTS_EXACT", "FLAG_PRIMAL_EXACT_WEIGHTS"]
+           "PRIMAL_WEIGHTS_REFERENCE", "PRIMAL_WEIGHTS_EXACT", "FLAG_PRIMAL_EXACT_WEIGHTS",
+           "CostRanging", "RhsRanging"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -86,6 +88,22 @@ class SolveResult:
     x_b: np.ndarray
     b_ixs: np.ndarray
     pivots: int
+
+
+class CostRanging(NamedTuple):
+    """Context.cost_ranging(): non-negative deltas and the blocking (entering) columns."""
+    down: np.ndarray
+    up: np.ndarray
+    block_down: np.ndarray
+    block_up: np.ndarray
+
+
+class RhsRanging(NamedTuple):
+    """Context.rhs_ranging(): non-negative deltas and 2 row + side of the leaving rows."""
+    down: np.ndarray
+    up: np.ndarray
+    leave_down: np.ndarray
+    leave_up: np.ndarray
 
 
 def _ptr(a: np.ndarray | None):
@@ -565,6 +583,32 @@ class Context:
         ms, k = ctypes.c_double(), ctypes.c_int64()
         check(self._L.spx_pbox_wexact_times(self._h, ctypes.byref(ms), ctypes.byref(k)))
         return ms.value, k.value
+
+    def cost_ranging(self) -> "CostRanging":
+        """At an optimum of ALGO_DUAL / ALGO_PRIMAL_BOX: how far each c_j may go
+        down and up before the basis changes, and the column that then enters
+        (-1: nothing blocks, the delta is +inf); n entries each (spx_ranging_cost)."""
+        n = self.n
+        r = CostRanging(np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64))
+        check(self._L.spx_ranging_cost(self._h, _ptr(r.down), _ptr(r.up), _ptr(r.block_down), _ptr(r.block_up)))
+        return r
+
+    def rhs_ranging(self) -> "RhsRanging":
+        """At an optimum of ALGO_DUAL / ALGO_PRIMAL_BOX: how far each b_r may go
+        down and up before a basic variable reaches a bound, and 2 row + side of
+        the row that then leaves (side 1: to its upper bound; -1: nothing blocks);
+        m entries each (spx_ranging_rhs)."""
+        m = self.m
+        r = RhsRanging(np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64))
+        check(self._L.spx_ranging_rhs(self._h, _ptr(r.down), _ptr(r.up), _ptr(r.leave_down), _ptr(r.leave_up)))
+        return r
+
+    def ranging_times(self):
+        """((cost ms, rhs ms), (cost calls, rhs calls)) of the rangings since the
+        last call (timing=True; spx_ranging_times)."""
+        ms, k = (ctypes.c_double * 2)(), (ctypes.c_int64 * 2)()
+        check(self._L.spx_ranging_times(self._h, ms, k))
+        return (ms[0], ms[1]), (k[0], k[1])
 
     def wg_times(self):
         """Per-pass clocks of the last two compact window passes (stamps=True,

@@ -75,6 +75,9 @@ SIGNATURES = {
     "spx_set_primal_weight_init": (ctypes.c_int, [_p, _i32]),
     "spx_refresh_primal_weights": (ctypes.c_int, [_p]),
     "spx_pbox_wexact_times": (ctypes.c_int, [_p, _p, _p]),
+    "spx_ranging_cost": (ctypes.c_int, [_p, _p, _p, _p, _p]),
+    "spx_ranging_rhs": (ctypes.c_int, [_p, _p, _p, _p, _p]),
+    "spx_ranging_times": (ctypes.c_int, [_p, _p, _p]),
     "spx_group_iterate": (ctypes.c_int, [_p, _i32, _i64, _p, _p]),
     "spx_group_sync": (ctypes.c_int, [_p, _i32]),
     "spx_solve": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _p]),

@@ -62,6 +62,13 @@
 //                  in --bounds' format, "-inf" = a free column (--primal-box with
 //                  Dantzig pricing); z and x are in the caller's variables;
 //                  without --dual or --primal-box it is refused by name (exit 1)
+//   --ranging PREFIX  after a --dual or --primal-box solve that ends at the
+//                  optimum: sensitivity ranging (spx_ranging_cost / _rhs, DESIGN.md
+//                  §7k) written to PREFIX.cost.txt (one line per column: down up
+//                  block_down block_up) and PREFIX.rhs.txt (one line per row: down
+//                  up leave_down leave_up), "%.17g %.17g %lld %lld"; any other
+//                  status prints the library's refusal (exit 1); without --dual or
+//                  --primal-box it is refused by name (exit 1)
 //   --tableau      window tableau (SPX_FLAG_TABLEAU): T_w = B_w A
 //                  kept in HBM, no per-pivot A / B^-1 stream
 //   --mps          the input is an MPS file (mps_io.h): converted to the
@@ -107,7 +114,7 @@ static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
                  " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--primal-weights reference|exact]]"
-                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F]"
+                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F] [--ranging PREFIX]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -119,7 +126,7 @@ int main(int argc, char* argv[]) {
     int device = -1;
     bool iter_lines = true, json = false, gen = false, solve = true;
     int threads = 0;
-    std::string write_bin, write_text, bounds_path, lower_path;
+    std::string write_bin, write_text, bounds_path, lower_path, ranging_prefix;
     int64_t gm = 0, gn = 0;
     uint64_t gseed = 0;
     const char* path = nullptr;
@@ -165,6 +172,7 @@ int main(int argc, char* argv[]) {
         else if (s == "--dual") dual = true;
         else if (s == "--primal-box") primal_box = true;
         else if (s == "--phase1") phase1 = true;
+        else if (s == "--ranging") { need(1); ranging_prefix = argv[++a]; }
         else if (s == "--bounds") { need(1); bounds_path = argv[++a]; }
         else if (s == "--lower") { need(1); lower_path = argv[++a]; }
         else if (s == "--dual-pricing") {
@@ -226,6 +234,10 @@ int main(int argc, char* argv[]) {
     }
     if (!lower_path.empty() && !primal_box && !dual) {
         std::cerr << "--lower needs --dual or --primal-box: lower bounds are the bounded loops'\n";
+        return 1;
+    }
+    if (!ranging_prefix.empty() && !primal_box && !dual) {
+        std::cerr << "--ranging needs --dual or --primal-box: ranging describes an optimum of the bounded loops\n";
         return 1;
     }
     if (primal_pricing_given && !primal_box) {
@@ -363,6 +375,32 @@ int main(int argc, char* argv[]) {
     if (primal_box) spx_get_primal_flips(ctx, pflips);
     int64_t ph1[4] = {0, 0, 0, 0};
     if (phase1) spx_get_primal_phase1(ctx, ph1);
+    if (!ranging_prefix.empty()) {  // PREFIX.cost.txt (n lines) and PREFIX.rhs.txt (m lines): down up index index
+        std::vector<double> dn((size_t)n), up((size_t)n);
+        std::vector<int64_t> kd((size_t)n), ku((size_t)n);
+        auto write = [&](const std::string& file, int64_t count) {
+            std::FILE* f = std::fopen(file.c_str(), "w");
+            if (!f) {
+                std::cerr << "--ranging: cannot write " << file << "\n";
+                return false;
+            }
+            for (int64_t k = 0; k < count; ++k)
+                std::fprintf(f, "%.17g %.17g %lld %lld\n", dn[(size_t)k], up[(size_t)k], (long long)kd[(size_t)k],
+                             (long long)ku[(size_t)k]);
+            return std::fclose(f) == 0;
+        };
+        rc = spx_ranging_cost(ctx, dn.data(), up.data(), kd.data(), ku.data());
+        bool ok = rc == SPX_OK && write(ranging_prefix + ".cost.txt", n);
+        if (ok) {
+            rc = spx_ranging_rhs(ctx, dn.data(), up.data(), kd.data(), ku.data());
+            ok = rc == SPX_OK && write(ranging_prefix + ".rhs.txt", m);
+        }
+        if (!ok) {
+            if (rc != SPX_OK) std::cerr << "--ranging failed (" << rc << "): " << spx_last_error() << "\n";
+            spx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+    }
     spx_destroy(ctx);
     const TimePoint t_dealloc_end = Clock::now();
 

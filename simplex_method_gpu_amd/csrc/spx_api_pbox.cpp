@@ -151,7 +151,7 @@ int pbox_wexact_setup(spx_ctx* x) {
     if (s.wx.parts) return SPX_OK;
     s.wxcfg = pbox_wexact_geometry(x->m, x->n, x->L);
     HIP_TRY(pbox_wexact_prepare());
-    SPX_TRY(x->alloc(&s.wx_S, (size_t)x->m * (size_t)x->L));
+    SPX_TRY(pbox_binv_copy(x));
     SPX_TRY(x->alloc(&s.wx.sparts, s.wxcfg.sparts));
     SPX_TRY(x->alloc(&s.wx.parts, s.wxcfg.parts));
     s.wx.S = s.wx_S;
@@ -321,6 +321,11 @@ int pbox_on_reset(spx_ctx* x) {
     x->pbox.se_stale = true;
     x->pbox.warm = false;  // the slack basis again
     return SPX_OK;
+}
+
+int pbox_binv_copy(spx_ctx* x) {
+    if (x->pbox.wx_S) return SPX_OK;
+    return x->alloc(&x->pbox.wx_S, (size_t)x->m * (size_t)x->L);
 }
 
 void pbox_weights_lost(spx_ctx* x) { x->pbox.se_stale = true; }

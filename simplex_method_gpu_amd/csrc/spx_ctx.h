@@ -1,5 +1,5 @@
 // spx_ctx.h — what the host translation units behind include/simplex.h share
-// (spx_api.cpp, spx_api_dual.cpp, spx_api_pbox.cpp): the context, the error plumbing and the few
+// (spx_api.cpp, spx_api_dual.cpp, spx_api_pbox.cpp, spx_api_ranging.cpp): the context, the error plumbing and the few
 // helpers one unit calls in the other.  Internal: not installed, not part of
 // the ABI.
 #pragma once
@@ -16,6 +16,7 @@
 #include "spx_kernels.h"
 #include "spx_loop.h"
 #include "spx_pbox.h"
+#include "spx_ranging.h"
 #include "spx_reinv.h"
 
 namespace spx_host {
@@ -130,7 +131,9 @@ struct DualState {
 //    DESIGN.md §7i): wx.parts != nullptr  <=>  pbox_wexact_setup ran (the partial
 //    buffers and wx_S, an m x L copy of the true B^-1, allocated by the first
 //    exact recomputation; a context in REFERENCE mode that never refreshes
-//    allocates and launches none of it).  winit says what a restart does for a
+//    allocates and launches none of it).  wx_S is shared with ranging
+//    (RangingState), whichever asks first allocates it (pbox_binv_copy); both
+//    overwrite it whole before they read it.  winit says what a restart does for a
 //    warm basis; warm: spx_set_basis was called since create / the last reset, so
 //    the slack basis is `!warm && pivots == 0`, where a restart is
 //    k_pbox_se_init's in both modes.
@@ -164,6 +167,22 @@ struct PboxState {
     // *_f kernels, the rule is Dantzig, and with phase1 off the device's ninf is 0.
     spx::PboxFreeArgs fr{};
     int8_t* fr_flags = nullptr;  // n (fr.is_free)
+};
+
+// Sensitivity ranging (spx_ranging.h; everything that reads or writes it is in
+// spx_api_ranging.cpp).  args.cparts != nullptr  <=>  ranging_setup
+// ran: every buffer of RngArgs but S (PboxState::wx_S, shared) and cfg are set,
+// by the first spx_ranging_cost / spx_ranging_rhs; a context that never asks
+// allocates and launches none of it.  Nothing here outlives a call but the
+// buffers: every call recomputes from the context's current state, and writes
+// nothing the loops read.
+struct RangingState {
+    spx::RngArgs args{};
+    spx::RngCfg cfg{};
+    double* d = nullptr;         // n reduced costs
+    int8_t* free_flags = nullptr;  // n (args.is_free while the context holds a free column)
+    std::vector<hipEvent_t> ev[2];  // timing: pairs around a cost [0] / right-hand-side [1] ranging (spx_ranging_times)
+    size_t n_ev[2] = {0, 0};
 };
 
 struct spx_ctx {
@@ -282,6 +301,7 @@ struct spx_ctx {
     int32_t algo = SPX_ALGO_PRIMAL;  // the loop spx_iterate runs
     DualState dual;                  // the dual one's state (spx_api_dual.cpp)
     PboxState pbox;                  // the bounded primal one's (spx_api_pbox.cpp)
+    RangingState rng;                // sensitivity ranging (spx_api_ranging.cpp)
 
     template <typename T>
     int alloc(T** p, size_t count, unsigned ext_flags = ~0u) {
@@ -353,5 +373,6 @@ void pbox_weights_lost(spx_ctx* x);  // the basis was set from outside or anothe
 void pbox_basis_set(spx_ctx* x);     // spx_set_basis: the basis is no longer known to be the slack basis
 int pbox_on_reinvert(spx_ctx* x);  // B^-1, x_b and y rebuilt: y current, the rows classified again
 int pbox_fresh_y(spx_ctx* x);      // before anything outside the loop reads y: y = c_B B^-1 if phase 1 left it stale
+int pbox_binv_copy(spx_ctx* x);    // PboxState::wx_S, the m x L buffer a true B^-1 is materialised into, on first use
 
 }  // namespace spx_host

@@ -86,6 +86,16 @@ alternating:
 with the ratios of the kernel times and of the pass rates to p1_parent, and
 p1_parent_again over p1_parent as the session's run-to-run spread.
 
+--ranging measures sensitivity ranging instead, one child process
+per --kernel-shape: boxed_primal's LP solved to the optimum under steepest edge,
+then, after one untimed round, five rounds of spx_refresh_primal_weights,
+spx_ranging_cost and spx_ranging_rhs, alternating, with their device times
+(spx_pbox_wexact_times, spx_ranging_times), the ratio of the fastest cost ranging
+to the fastest exact weight start, and the rates they amount to.  With --k >= 252
+the bounded primal loop of a context that never ranges follows (role pbox, twice),
+alternating with --parent-root (a built checkout of the parent commit: its package
+and its libsimplex.so) when one is given.
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
     python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
@@ -95,6 +105,8 @@ p1_parent_again over p1_parent as the session's run-to-run spread.
                                --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5 --kernel-shape 4096 16384 5
                                [--out profiles/pbox_wexact.json]
     python tools/pbox_bench.py --free --parent-lib PATH [--out profiles/pbox_lu_c3.json]
+    python tools/pbox_bench.py --ranging --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5
+                               --kernel-shape 4096 16384 5 [--parent-root DIR] [--out profiles/ranging_c3.json]
 """
 import argparse
 import json
@@ -104,7 +116,7 @@ import sys
 import time
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.environ.get("SPX_BENCH_ROOT") or ROOT)  # (a child of --parent-root: that checkout's package)
 sys.path.insert(1, os.path.join(ROOT, "tests"))
 
 PEAK = 8.0e12  # MI355X HBM bytes/s the fractions are quoted against
@@ -553,8 +565,55 @@ def run_wexact_kernel(a):
             "se_passes_timed": passes, "start_in_se_passes": round(best * 1e3 / pass_us, 1)}
 
 
-def child(a, role, pricing="dantzig", se_lds=None, lib=None):
+def run_ranging_kernel(a):
+    """One shape (the first --kernel-shape): boxed_primal's LP solved to the optimum
+    under steepest edge, then five rounds of spx_refresh_primal_weights,
+    spx_ranging_cost and spx_ranging_rhs, alternating, with their device times."""
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    m, n, seed = a.kernel_shape[0]
+    A, b, c, u = primal_box_ref.boxed_primal(m, n, seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    with spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u, timing=True,
+                     primal_pricing=spx.PRIMAL_PRICING_STEEPEST) as ctx:
+        t0 = time.perf_counter()
+        r = ctx.solve()
+        solve_s = time.perf_counter() - t0
+        if r.status != spx.SolveStatus.OptimumFound:
+            raise SystemExit(f"{m}x{n}: the solve ended with {r.status!r}")
+        ctx.refresh_primal_weights()  # first launches: untimed
+        ctx.cost_ranging()
+        ctx.rhs_ranging()
+        ctx.wexact_times()
+        ctx.ranging_times()
+        wx, cost, rhs = [], [], []
+        for _ in range(5):
+            ctx.refresh_primal_weights()
+            wx.append(round(ctx.wexact_times()[0], 4))
+            g = ctx.cost_ranging()
+            h = ctx.rhs_ranging()
+            (tc, tr), _ = ctx.ranging_times()
+            cost.append(round(tc, 4))
+            rhs.append(round(tr, 4))
+        nb_slack = int(np.sum(~np.isin(np.arange(n - m, n), r.b_ixs)))
+    flops = 2.0 * m * m * (n - m)
+    return {"m": m, "n": n, "seed": seed, "pivots": r.pivots, "solve_s": round(solve_s, 3), "nonbasic_slacks": nb_slack,
+            "wexact_ms": wx, "cost_ms": cost, "rhs_ms": rhs, "wexact_ms_best": min(wx), "cost_ms_best": min(cost),
+            "rhs_ms_best": min(rhs), "cost_over_wexact": round(min(cost) / min(wx), 3),
+            "cost_fp64_TFLOPs": round(flops / (min(cost) * 1e-3) / 1e12, 2),
+            "rhs_binv_TBps": round(2.0 * 8.0 * m * m / (min(rhs) * 1e-3) / 1e12, 3),  # materialise + one stream
+            "finite_cost_limits": int(np.isfinite(g.down).sum() + np.isfinite(g.up).sum()),
+            "finite_rhs_limits": int(np.isfinite(h.down).sum() + np.isfinite(h.up).sum())}
+
+
+def child(a, role, pricing="dantzig", se_lds=None, lib=None, root=None):
     env = dict(os.environ)
+    if root is not None:
+        env["SPX_BENCH_ROOT"] = os.path.abspath(root)
     if se_lds is not None:
         env["SPX_PBOX_SE_LDS"] = str(se_lds)
     if lib is not None:
@@ -600,14 +659,45 @@ def main():
     ap.add_argument("--parent-lib", default=None, help="with --free: libsimplex.so built from the parent commit")
     ap.add_argument("--role", default=None,
                     choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se",
-                             "warm_resolve", "wexact_kernel", "p1_free", "p1_parent"])
+                             "warm_resolve", "wexact_kernel", "p1_free", "p1_parent", "ranging_kernel"])
+    ap.add_argument("--parent-root", default=None,
+                    help="with --ranging: a built checkout of the parent commit (its package and its libsimplex.so)")
+    ap.add_argument("--ranging", action="store_true",
+                    help="sensitivity ranging against the exact weight start instead (DESIGN.md 7k)")
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
         run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
                "pbox_flag": run_pbox_flag, "p1_dense": run_p1_dense, "p1_sparse": run_p1_sparse,
                "pbox_se": run_pbox_se, "warm_resolve": run_warm_resolve, "wexact_kernel": run_wexact_kernel,
-               "p1_free": run_p1_free, "p1_parent": run_p1_parent}[a.role]
+               "p1_free": run_p1_free, "p1_parent": run_p1_parent, "ranging_kernel": run_ranging_kernel}[a.role]
         print(json.dumps(run(a)), flush=True)
+        return
+    if a.ranging:
+        import copy
+
+        res = {"k": a.k, "warm": a.warm, "kernel": []}
+        for shape in a.kernel_shape:
+            one = copy.copy(a)
+            one.solve_shape, one.kernel_shape = [], [shape]
+            res["kernel"].append(child(one, "ranging_kernel", "steepest"))
+            sys.stderr.write(f"ranging {shape}: {json.dumps(res['kernel'][-1])}\n")
+            sys.stderr.flush()
+        if a.k >= 252:  # the loop of a context that never ranges, against the parent build when one is given
+            roots = (("parent", a.parent_root), ("this", None)) if a.parent_root else (("this", None),)
+            for again in ("", "_again"):
+                for name, root in roots:
+                    key = f"pbox_{name}{again}"
+                    res[key] = child(a, "pbox", root=root)
+                    sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+                    sys.stderr.flush()
+            if a.parent_root:
+                base = res["pbox_parent"]["it_per_s"]
+                res["it_per_s_over_parent"] = {k: round(res[k]["it_per_s"] / base, 4)
+                                               for k in ("pbox_this", "pbox_parent_again", "pbox_this_again")}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
         return
     if a.warm_resolve:
         import copy
