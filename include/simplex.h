@@ -820,7 +820,11 @@ int spx_loop_times(spx_ctx* ctx, double out[SPX_LOOP_FIELDS], int64_t* passes);
 /* Geometry and algorithmic bytes.  bytes_price: one pricing launch on this
  * rank (8*(m+1)*local non-basic columns), bytes_update: the B^-1 bytes per
  * pivot — 16*m*m for the explicit rank-1 update, or
- * 8*m*m*(1 + 2/(window-1)) for the eta window (stream + amortised fold). */
+ * 8*m*m*(1 + 2/(window-1)) for the eta window (stream + amortised fold).
+ * With compact pricing (spx_config [16]) bytes_price is the mean pricing
+ * launch of a window under the anchor period P (spx_dispatch_stats [11]): the
+ * compact passes, and one dense stream per P windows; the dw carry's
+ * 8*n*(window+2) bytes per carried window join the fold in bytes_update. */
 int spx_info(spx_ctx* ctx, int64_t* m, int64_t* n, int64_t* ld,
              int64_t* local_nonbasic, double* bytes_price, double* bytes_update);
 
@@ -842,7 +846,9 @@ int spx_info(spx_ctx* ctx, int64_t* m, int64_t* n, int64_t* ld,
  * after its first price from the listed rows of A (1: compact pricing, one
  * rank over the compact operand, Dantzig or Devex; SPX_DENSE_PRICE=1 turns it
  * off) or stream A (0: also once the list has outgrown the stored rows,
- * SPX_CPRICE_CAP). */
+ * SPX_CPRICE_CAP).  With [16] = 1 the first pass of a window is compact too
+ * wherever dw was carried across the fold (spx_dispatch_stats [10], [11];
+ * SPX_DW_ANCHOR). */
 #define SPX_CONFIG_FIELDS 17
 int spx_config(spx_ctx* ctx, int32_t out[SPX_CONFIG_FIELDS]);
 
@@ -888,9 +894,20 @@ int spx_ftran_cols(spx_ctx* ctx, int32_t* cols);
  * switched to two-kernel passes and made those pivots that way), [9] times
  * the batch hipGraph was built (captured, instantiated and uploaded; 0 or 1
  * per context, rebuilt once after spx_mbox_attach).  A context that prices
- * compactly (spx_config [16]) builds the batch twice in that one go, once per
- * pricing mode, so that a solve crossing into dense pricing builds nothing. */
-#define SPX_DISPATCH_FIELDS 10
+ * compactly (spx_config [16]) builds every batch it can replay in that one go
+ * (dense pricing, compact pricing opening with an anchor, compact pricing
+ * carrying dw), so that a solve crossing into dense pricing builds nothing.
+ * [10] compact-priced windows opened by an anchor: the dense pricing pass that
+ * also stores dw[j] = y_w.A_j - c_j, with k_dw_basic.  The first window, the
+ * one after a reset, rebuild, reinversion, spx_set_basis, state readback or
+ * switch of pricing mode, and every P-th fold since the last anchor open so;
+ * every other fold carries dw to the new y_w from the stored Wt rows and
+ * opens its window with a compact pass.  [11] that period P (default 32;
+ * SPX_DW_ANCHOR=N sets it: 1 = every fold anchors, nothing is carried; 0 =
+ * no fold anchors, reported as -1), or 0 where dw is not carried (dense
+ * pricing, the dense fold, P = 1).  A setting, not a count: spx_config keeps
+ * its 17 fields under this ABI version, so the period is reported here. */
+#define SPX_DISPATCH_FIELDS 12
 int spx_dispatch_stats(spx_ctx* ctx, int64_t out[SPX_DISPATCH_FIELDS]);
 
 /* Capture, instantiate and upload the batch hipGraph now, so that no later

@@ -693,11 +693,13 @@ class Context:
         ``graph_builds`` counts the times the library stopped to build its
         batch graph, not the graphs: a context that prices compactly
         (``config()["compact_price"]``) captures the batch once per pricing
-        mode in that one stop, and reports 1."""
-        out = (ctypes.c_int64 * 10)()
+        mode in that one stop, and reports 1.  ``dw_anchors`` counts the
+        compact-priced windows opened by the dense pass that stores dw;
+        ``dw_carry`` is the anchor period (a setting: ``config()`` has it too)."""
+        out = (ctypes.c_int64 * 12)()
         check(self._L.spx_dispatch_stats(self._h, out))
         keys = ("eager_passes", "graph_launches", "graph_passes", "persistent_launches", "persistent_passes",
-                "folds", "window_pos", "window", "persist_fallbacks", "graph_builds")
+                "folds", "window_pos", "window", "persist_fallbacks", "graph_builds", "dw_anchors", "dw_carry")
         return dict(zip(keys, list(out)))
 
     def config(self):
@@ -708,6 +710,9 @@ class Context:
                 "graph_batch", "persistent", "loop_block", "tableau", "loop_grid", "defer_tail", "compact_fold",
                 "ftran_rows_per_wave", "mbox_fused", "compact_price")
         cfg = dict(zip(keys, list(out)))
+        # the dw anchor period P (0: dw is not carried, -1: carried and never
+        # re-anchored); spx_dispatch_stats reports it, spx_config keeps 17 fields
+        cfg["dw_carry"] = self.dispatch_stats()["dw_carry"]
         cfg["dual_pricing"] = self._dual_pricing  # (the library keeps it outside spx_config)
         cfg["primal_pricing"] = self._primal_pricing
         cfg["dual_ratio"] = self._dual_ratio

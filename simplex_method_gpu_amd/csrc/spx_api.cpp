@@ -529,7 +529,7 @@ int do_reset(spx_ctx* x) {
     x->status = SPX_STATUS_MAX_ITER;
     x->stepped_price = false;
     x->nw = 0;
-    x->dw_ok = false;
+    x->dwc.invalidate();
     x->s_list = 0;
     x->cp_now = x->cp_ok;
     return SPX_OK;
@@ -574,18 +574,23 @@ int enqueue_pass(spx_ctx* x, bool timed) {
         if (timed) SPX_TRY(fold_events(x, &f0, &f1));
         if (x->defer_tail) HIP_TRY(launch_apply_tail(x->P, x->stream));  // the fold reads the pivot's state
         if (f0) HIP_TRY(hipEventRecord(f0, x->stream));
-        HIP_TRY(launch_fold(x->P, x->P.win, x->cus, x->stream));
+        // compact pricing: the fold carries a valid dw to the new y_w, except
+        // every P-th one since the last anchor (x->dwc)
+        const bool carry = x->cp_now && x->P.cfold && x->dwc.fold();
+        if (!carry) x->dwc.invalidate();
+        HIP_TRY(launch_fold(x->P, x->P.win, x->cus, x->stream, carry));
         if (f1) HIP_TRY(hipEventRecord(f1, x->stream));
-        x->dw_ok = false;
     }
-    // compact pricing: the first pass after a fold, reset or rebuild is the
-    // dense stream that also stores dw (tau <= 0 there); the window's other
-    // passes price from AS and dw.  Where dw is stale in mid-window (the
-    // stepping API made pivots since the fold) the plain dense pass runs until
-    // the next fold.  Decided from the window position alone, so the same
+    // compact pricing: where dw is not valid, the first pass after a fold,
+    // reset or rebuild is the dense stream that also stores it (tau <= 0
+    // there): an anchor.  A window's other passes, and all of them after a
+    // fold that carried dw, price from AS and dw.  Where dw is stale in
+    // mid-window (the stepping API made pivots since the fold) the plain
+    // dense pass runs until the next fold.  Decided from the window position,
+    // the folds since the last anchor and dw's validity alone, so the same
     // passes are dense however the calls are chunked or dispatched
-    const bool cp_open = x->cp_now && !x->dw_ok && (fold || x->nw <= 1);
-    const bool cp_pass = x->cp_now && x->dw_ok;
+    const bool cp_open = x->cp_now && !x->dwc.ok && (fold || x->nw <= 1);
+    const bool cp_pass = x->cp_now && x->dwc.ok;
     advance_window(x, fold);
     // steepest edge: after the fold, before pricing (k_se_part skipped when the
     // previous pass's FTRAN left its sums and no fold came between)
@@ -599,7 +604,7 @@ int enqueue_pass(spx_ctx* x, bool timed) {
     HIP_TRY(launch_price(Pp, cp_pass ? x->ccfg : (cp_open ? x->dcfg : x->pcfg), x->stream, p0, p1));
     if (cp_open) {
         HIP_TRY(launch_dw_basic(Pp, x->stream));
-        x->dw_ok = true;
+        x->dwc.anchor();
     }
     if (x->use_comm) {
         if (x->mbox_ready) {
@@ -622,25 +627,33 @@ int enqueue_pass(spx_ctx* x, bool timed) {
     return SPX_OK;
 }
 
-// (the batch of the current pricing mode, x->cp_now: each mode has its graph)
-int build_graph(spx_ctx* x) {
-    hipGraphExec_t& gexec = x->cp_now ? x->graph_exec_c : x->graph_exec;
-    hipGraph_t& gkeep = x->cp_now ? x->graph_c : x->graph;
+// (the batch of the current pricing mode, x->cp_now: each mode has its graph,
+// and compact pricing two: the batch whose first fold leaves dw stale, so its
+// window opens with an anchor, and, carry_batch, the one whose folds all
+// carry dw)
+int build_graph(spx_ctx* x, bool carry_batch = false) {
+    hipGraphExec_t& gexec = !x->cp_now ? x->graph_exec : (carry_batch ? x->graph_exec_k : x->graph_exec_c);
+    hipGraph_t& gkeep = !x->cp_now ? x->graph : (carry_batch ? x->graph_k : x->graph_c);
     if (gexec || x->batch <= 0) return SPX_OK;
     if (x->use_comm && !x->comm_ready && !x->mbox_ready)
         return fail(SPX_ERR_STATE, "nranks > 1 but neither spx_attach_comm nor spx_mbox_attach was called");
     HIP_TRY(hipStreamBeginCapture(x->stream, hipStreamCaptureModeThreadLocal));
     int rc = SPX_OK;
     const int nw_keep = x->nw;
-    const bool dw_keep = x->dw_ok;
+    const spx_host::DwCarry dw_keep = x->dwc;
     if (x->P.win) x->nw = x->P.win;  // a batch starts with a fold (see iterate)
+    // (captured as the rule decides from this state: stale, or valid and
+    // never due for an anchor)
+    x->dwc.ok = carry_batch;
+    x->dwc.since = 0;
+    if (carry_batch) x->dwc.period = 0;
     x->capturing = true;
     x->graph_folds = 0;
     for (int i = 0; i < x->batch && rc == SPX_OK; ++i) rc = enqueue_pass(x, false);
     x->capturing = false;
     x->se_chain = false;  // (nothing captured has run)
     x->nw = nw_keep;
-    x->dw_ok = dw_keep;
+    x->dwc = dw_keep;
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(x->stream, &g);
     hipError_t ei = hipSuccess;
@@ -666,10 +679,15 @@ int build_graph(spx_ctx* x) {
     return SPX_OK;
 }
 
-// both batch graphs of a context that can price compactly (a solve crosses
-// into dense pricing when its list outgrows AS): nothing is captured later,
-// inside somebody's timed region.  One build in spx_dispatch_stats' count:
-// it counts the times the library stopped to build, not the graphs
+// does any fold of this context carry dw (compact pricing, the compact fold,
+// an anchor period other than 1)
+bool dw_carries(const spx_ctx* x) { return x->cp_ok && x->P.cfold && x->dwc.period != 1; }
+
+// every batch graph of a context that can price compactly (a solve crosses
+// into dense pricing when its list outgrows AS; its windows open with an
+// anchor or carry dw): nothing is captured later, inside somebody's timed
+// region.  One build in spx_dispatch_stats' count: it counts the times the
+// library stopped to build, not the graphs
 int build_graphs(spx_ctx* x) {
     if (!x->cp_ok) return build_graph(x);
     const bool keep = x->cp_now;
@@ -678,6 +696,7 @@ int build_graphs(spx_ctx* x) {
     for (int mode = 1; mode >= 0 && rc == SPX_OK; --mode) {
         x->cp_now = mode != 0;
         rc = build_graph(x);
+        if (rc == SPX_OK && mode != 0 && dw_carries(x)) rc = build_graph(x, true);
     }
     x->cp_now = keep;
     if (x->n_graph_builds > built) x->n_graph_builds = built + 1;
@@ -852,7 +871,7 @@ int iterate_raw(spx_ctx* x, int64_t k) {
         const int64_t chunk = cp ? std::min(left, room) : left;
         if (cp != x->cp_now) {
             x->cp_now = cp;
-            x->dw_ok = false;
+            x->dwc.invalidate();
         }
         const int64_t before = x->pivots;
         SPX_TRY(iterate_passes(x, chunk));
@@ -875,14 +894,29 @@ int iterate_passes(spx_ctx* x, int64_t k) {
             for (int64_t i = 0; i < lead; ++i) SPX_TRY(enqueue_pass(x, x->timing));
             left -= lead;
             SPX_TRY(build_graph(x));
-            hipGraphExec_t gexec = x->cp_now ? x->graph_exec_c : x->graph_exec;
+            if (x->cp_now && dw_carries(x)) SPX_TRY(build_graph(x, true));
             const int64_t reps = left / x->batch;
-            for (int64_t i = 0; i < reps; ++i) HIP_TRY(hipGraphLaunch(gexec, x->stream));
-            if (reps > 0 && x->cp_now) x->dw_ok = true;  // (the batch's last window; the next pass folds)
+            for (int64_t i = 0; i < reps; ++i) {
+                // compact pricing: the batch that decides its folds as the
+                // rule does from here (x->dwc); where an anchor falls due
+                // inside a batch of several windows neither does, and the
+                // window is enqueued pass by pass
+                hipGraphExec_t gexec = x->graph_exec;
+                if (x->cp_now) {
+                    const bool ca = x->P.cfold && x->graph_exec_k && x->dwc.fits_carry_batch(x->graph_folds);
+                    gexec = ca ? x->graph_exec_k : (x->dwc.fits_anchor_batch() ? x->graph_exec_c : nullptr);
+                }
+                if (!gexec) {
+                    for (int64_t w = 0; w < x->batch; ++w) SPX_TRY(enqueue_pass(x, x->timing));
+                    continue;
+                }
+                HIP_TRY(hipGraphLaunch(gexec, x->stream));
+                if (x->cp_now) x->dwc.replay(x->graph_folds);
+                ++x->n_graph_launch;
+                x->n_graph_pass += x->batch;
+                x->n_folds += x->graph_folds;
+            }
             x->se_chain = false;
-            x->n_graph_launch += reps;
-            x->n_graph_pass += reps * x->batch;
-            x->n_folds += reps * x->graph_folds;
             left -= reps * x->batch;  // a batch of whole windows leaves nw == KW again
         }
     }
@@ -982,7 +1016,7 @@ int reinvert_basis(spx_ctx* x, const int64_t* basis) {
     }
     SPX_TRY(tab_rebuild(x, false));
     x->nw = 0;
-    x->dw_ok = false;
+    x->dwc.invalidate();
     dual_on_reinvert(x);
     SPX_TRY(pbox_on_reinvert(x));
     return read_state(x);
@@ -1148,6 +1182,9 @@ int cprice_setup(spx_ctx* x) {
     P.as_cap = (int32_t)cap;
     P.AS = static_cast<double*>(d);
     x->cp_ok = x->cp_now = true;
+    // dw is carried across the compact fold (k_as_rows); the dense fold
+    // rebuilds the list and leaves dw stale, so there every fold anchors
+    x->dwc.period = P.cfold ? spx_host::dw_period_from(std::getenv("SPX_DW_ANCHOR")) : 1;
     return SPX_OK;
 }
 
@@ -1237,7 +1274,7 @@ int flush(spx_ctx* x) {
         HIP_TRY(launch_fold(x->P, 2, x->cus, x->stream));
         HIP_TRY(launch_tab_binv(x->P, x->stream));  // tableau without k_fold: B_w from T_w
         x->nw = std::min(x->nw, 1);
-        x->dw_ok = false;
+        x->dwc.invalidate();
     }
     HIP_TRY(launch_flush(x->P, x->stream));
     return SPX_OK;
@@ -1326,6 +1363,8 @@ void spx_destroy(spx_ctx* x) {
     if (x->graph) (void)hipGraphDestroy(x->graph);
     if (x->graph_exec_c) (void)hipGraphExecDestroy(x->graph_exec_c);
     if (x->graph_c) (void)hipGraphDestroy(x->graph_c);
+    if (x->graph_exec_k) (void)hipGraphExecDestroy(x->graph_exec_k);
+    if (x->graph_k) (void)hipGraphDestroy(x->graph_k);
     for (hipEvent_t e : {x->ev_sent, x->ev_recv, x->ev_sent2, x->ev_recv2})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_price) (void)hipEventDestroy(e);
@@ -1607,6 +1646,7 @@ int spx_group_iterate(spx_ctx** cs, int32_t G, int64_t k, int32_t* status, int64
                 const bool fold = fold_due(x);
                 if (fold && x->defer_tail) HIP_TRY(launch_apply_tail(x->P, x->stream));
                 if (fold) HIP_TRY(launch_fold(x->P, x->P.win, x->cus, x->stream));
+                if (fold) x->dwc.invalidate();  // (group passes price densely and carry nothing)
                 advance_window(x, fold);
                 // steepest edge: after the fold, before pricing (as enqueue_pass)
                 HIP_TRY(launch_se_prep(x->P, x->stream, (x->se_fuse && x->se_chain && !fold) ? x->ucfg.grid : 0));
@@ -1847,7 +1887,7 @@ int spx_price(spx_ctx* x, int64_t* p, double* min_e, int32_t* optimal) {
     SPX_TRY(set_limit(x, x->pivots + 1));
     const bool fold = fold_due(x);
     if (fold) HIP_TRY(launch_fold(x->P, x->P.win, x->cus, x->stream));
-    if (fold) x->dw_ok = false;
+    if (fold) x->dwc.invalidate();
     ++x->n_eager;
     x->n_folds += fold ? 1 : 0;
     HIP_TRY(launch_se_prep(x->P, x->stream));
@@ -1914,6 +1954,8 @@ int spx_dispatch_stats(spx_ctx* x, int64_t out[SPX_DISPATCH_FIELDS]) {
     out[7] = x->P.win;
     out[8] = x->n_persist_fallback;
     out[9] = x->n_graph_builds;
+    out[10] = x->dwc.anchors;
+    out[11] = (x->cp_ok && x->cp_now && x->dwc.period != 1) ? (x->dwc.period > 0 ? x->dwc.period : -1) : 0;
     return SPX_OK;
 }
 
@@ -2040,13 +2082,14 @@ int spx_info(spx_ctx* x, int64_t* m, int64_t* n, int64_t* ld, int64_t* local_nb,
     }
     if (bp) *bp = 8.0 * (double)(x->m + 1) * (double)streamed;
     if (bp && x->cp_ok && x->cp_now && x->P.win > 2) {
-        // compact pricing: the mean launch of a window -- KW - 2 compact passes
-        // (per priced column its S entries of AS, dw[j], A[q, j], the mean Wt
-        // row and the new Wt entry) and the dense pass that opens it
+        // compact pricing: the mean launch of a window -- compact passes (per
+        // priced column its S entries of AS, dw[j], A[q, j], the mean Wt row
+        // and the new Wt entry) and, in the one window in P that opens with an
+        // anchor, the dense pass (spx_dwcarry.h)
         const double kw = (double)x->P.win;
         const double per_col = 8.0 * ((double)x->s_list + 2.0 + 0.5 * (kw - 1.0) + 1.0);
         const double compact = per_col * (double)x->st_host->nb_count;
-        *bp = ((kw - 2.0) * compact + *bp) / (kw - 1.0);
+        *bp = spx_host::dw_mean_price_bytes(*bp, compact, x->P.win, x->dwc.period);
     }
     // update bytes per pivot: B^-1 read + write, or (eta window) the B_w
     // FTRAN stream (its non-unit columns with the compact operand) plus the
@@ -2056,7 +2099,11 @@ int spx_info(spx_ctx* x, int64_t* m, int64_t* n, int64_t* ld, int64_t* local_nb,
     const double md = (double)x->m;
     // the fold per window: dense -- B_w read + written; compact (k_cfold) --
     // the operand's columns read, written and scattered into B_w, U read
-    const double fold = (x->P.bc && x->P.cfold) ? 8.0 * md * (3.0 * cols + x->P.win) : 16.0 * md * md;
+    double fold = (x->P.bc && x->P.cfold) ? 8.0 * md * (3.0 * cols + x->P.win) : 16.0 * md * md;
+    // ... and where the fold carries dw (all but one window in P), dw read and
+    // written and the Wt rows read
+    if (x->cp_now && dw_carries(x) && x->P.win > 2)
+        fold += spx_host::dw_carry_bytes(x->n, x->P.win) * (x->dwc.period > 0 ? 1.0 - 1.0 / x->dwc.period : 1.0);
     if (bu) *bu = x->P.win ? 8.0 * md * (double)cols + fold / (x->P.win - 1) : 16.0 * md * md;
     return SPX_OK;
 }

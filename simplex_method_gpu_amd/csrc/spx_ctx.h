@@ -13,6 +13,7 @@
 #include "../../include/simplex.h"
 #include "spx_device.h"
 #include "spx_dual.h"
+#include "spx_dwcarry.h"
 #include "spx_kernels.h"
 #include "spx_loop.h"
 #include "spx_pbox.h"
@@ -233,22 +234,29 @@ struct spx_ctx {
 
     // compact pricing (Params::AS).  cp_ok: allocated and applicable; cp_now:
     // the passes being enqueued price compactly (decided per chunk of an
-    // iterate call from the list length, iterate_raw); dw_ok: dw belongs to
-    // the current y_w (false after every fold, rebuild and readback flush:
-    // the next pass is then the dense one that stores it).  ccfg / dcfg: the
-    // compact launch and the dense launch that stores dw; s_list: bc_n[0] as
-    // of the last readback (bcn_host: its pinned mirror)
-    bool cp_ok = false, cp_now = false, dw_ok = false;
+    // iterate call from the list length, iterate_raw); dwc.ok: dw belongs to
+    // the current y_w (false after a rebuild, a readback flush, a switch of
+    // pricing mode and every fold that does not carry it: the next window
+    // then opens with the dense pass that stores it, an anchor; dwc decides
+    // which folds carry, spx_dwcarry.h).  ccfg / dcfg: the compact launch and
+    // the dense launch that stores dw; s_list: bc_n[0] as of the last
+    // readback (bcn_host: its pinned mirror)
+    bool cp_ok = false, cp_now = false;
+    spx_host::DwCarry dwc{};
     spx::PriceCfg ccfg{}, dcfg{};
     int32_t s_list = 0;
     int32_t* bcn_host = nullptr;
 
     // graph replay of `batch` passes (graph_c / graph_exec_c: the batch with
-    // compact pricing; both are captured by spx_prepare)
+    // compact pricing whose first window opens with an anchor; graph_k /
+    // graph_exec_k: the one whose folds all carry dw; all are captured by
+    // spx_prepare)
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec_c = nullptr;
     hipGraph_t graph_c = nullptr;
+    hipGraphExec_t graph_exec_k = nullptr;
+    hipGraph_t graph_k = nullptr;
     int batch = 0;
 
     // in-process group exchange

@@ -371,10 +371,15 @@ struct Params {
     // is constant inside a window: the window's first pass is the dense stream
     // (k_price<.., DW>) and stores it in dw[j] (n entries; k_dw_basic adds the
     // basic columns, which may leave inside the window); the other passes
-    // (k_price WM 6) price from AS, dw and the Wt rows.  bc_n[5] = 1 while dw
-    // belongs to the current y_w (set by the dense pass, cleared by
-    // k_bc_list, i.e. by every fold and rebuild); a compact pass that finds
-    // it 0, or S > as_cap, stops with ST_CPRICE_STATE.  nullptr: dense pricing.
+    // (k_price WM 6) price from AS, dw and the Wt rows.  A loop fold carries
+    // dw to the new y_w instead (k_as_rows: dw[j] += sum_t SY[t] Wt[j][t]),
+    // and the window it opens has no dense pass; the host anchors (the dense
+    // pass again) every few folds (spx_dwcarry.h).  bc_n[5] = 1 while dw
+    // belongs to the current y_w: set by the dense pass; k_bc_list, i.e.
+    // every fold and rebuild, clears it, or makes it 2 where a valid dw is
+    // about to be carried, and k_as_order makes that 1 again after the carry.
+    // A compact pass that finds it not 1, or S > as_cap, stops with
+    // ST_CPRICE_STATE.  nullptr: dense pricing.
     double* AS;
     int64_t as_ld;
     int32_t as_cap;

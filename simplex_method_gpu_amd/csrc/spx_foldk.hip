@@ -98,7 +98,9 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_fold(Params P, int min_nw) {
 // ---------------------------------------------------------------------------
 // min_nw > 0 (the compact fold): only when that fold runs (k_fold's test),
 // recording S and the pitch before the append in bc_n[3] / bc_n[4]
-__global__ __launch_bounds__(1024) void k_bc_list(Params P, int min_nw) {
+// carry (compact pricing, a loop fold): dw is carried across this fold, so a
+// dw that belongs to the y_w being folded away is marked 2 for k_as_rows
+__global__ __launch_bounds__(1024) void k_bc_list(Params P, int min_nw, int carry) {
     __shared__ int s_w[16];
     __shared__ int s_base;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -110,7 +112,10 @@ __global__ __launch_bounds__(1024) void k_bc_list(Params P, int min_nw) {
         s_base = P.bc_n[0];
         P.bc_n[3] = P.bc_n[0];
         P.bc_n[4] = P.bc_n[1];
-        P.bc_n[5] = 0;  // compact pricing: y_w is about to change (or B_w was rebuilt): dw is stale
+        // compact pricing: y_w is about to change (or B_w was rebuilt): dw is
+        // stale, unless this fold carries one that was valid (2, turned back
+        // into 1 by k_as_order once k_as_rows has carried every column)
+        P.bc_n[5] = (carry && min_nw > 0 && P.bc_n[5] == 1) ? 2 : 0;
     }
     __syncthreads();
     for (int64_t k0 = 0; k0 < P.m; k0 += 1024) {
@@ -148,22 +153,41 @@ __global__ __launch_bounds__(1024) void k_bc_list(Params P, int min_nw) {
 // bc_n[0] = 0, so it copies every row.  One thread per (column, new row):
 // the threads of a column read its scattered elements and store one run.
 // Rows past as_cap are not copied (a compact pass stops before reading them).
-__global__ __launch_bounds__(256) void k_as_rows(Params P, int min_nw) {
+// The dw carry (carry != 0 and k_bc_list found dw valid: bc_n[5] == 2): the
+// fold about to run makes y_w += sum_{t<nf} SY[t] r_t, and Wt[j][t] = r_t . A_j
+// is stored for every column (the non-basic ones by the pricing pass after
+// pivot t, the basic ones by its FTRAN pass), so
+//   dw[j] += sum_{t<nf} SY[t] Wt[j][t]
+// is y_w . A_j - c_j for the new y_w without a stream of A.  The column's wave
+// has lane t take the product of pivot t (rounded on its own), then the
+// butterfly: an order no grid, dispatch or chunking enters.  Before k_cfold,
+// whose last workgroup rewrites SY[0] and the window count.
+__global__ __launch_bounds__(256) void k_as_rows(Params P, int min_nw, int carry) {
+    int nw = 0;
     if (min_nw > 0) {
-        const int nw = P.st->nw;
+        nw = P.st->nw;
         if (nw < min_nw || nw < 2) return;
     }
     const int S0 = P.bc_n[3];
     const int S = P.bc_n[0] < P.as_cap ? P.bc_n[0] : P.as_cap;
     const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j >= P.n) return;
+    if (carry && min_nw > 0 && P.bc_n[5] == 2) {  // (uniform: the whole wave sums)
+        const int lane = (int)(threadIdx.x & 63);
+        const int KW = P.win, nf = nw - 1;
+        double v = 0.0;
+        if (lane < nf && lane < KW) v = mul_nc(P.SY[lane], P.Wt[j * KW + lane]);
+        v = wave_sum(v);
+        if (lane == 0) P.dw[j] += v;
+    }
     for (int c = S0 + (int)(threadIdx.x & 63); c < S; c += 64)
         P.AS[j * P.as_ld + c] = P.A[j * P.L + P.rlist[c]];
 }
 // ... and the order its sum runs in (spx_device.h): rank of every list
 // position under the key (lane of the dense stream, row), by counting (one
 // workgroup; S^2 / 1024 compares per thread, S <= as_cap <= 4096)
-__global__ __launch_bounds__(1024) void k_as_order(Params P, int min_nw) {
+// (the kernel after k_as_rows: marks a carried dw valid for the new y_w)
+__global__ __launch_bounds__(1024) void k_as_order(Params P, int min_nw, int carry) {
     __shared__ int s_row[4096];
     if (min_nw > 0) {
         const int nw = P.st->nw;
@@ -185,11 +209,12 @@ __global__ __launch_bounds__(1024) void k_as_order(Params P, int min_nw) {
         for (int d = 0; d < S; ++d) off += ((s_row[d] >> 1) & 63) < tid ? 1 : 0;
         P.as_off[tid] = off;
     }
+    if (carry && min_nw > 0 && tid == 0 && P.bc_n[5] == 2) P.bc_n[5] = 1;
 }
-static void launch_as_rows(const Params& P, int min_nw, hipStream_t s) {
+static void launch_as_rows(const Params& P, int min_nw, int carry, hipStream_t s) {
     if (!P.AS) return;
-    hipLaunchKernelGGL(k_as_rows, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, s, P, min_nw);
-    hipLaunchKernelGGL(k_as_order, dim3(1), dim3(1024), 0, s, P, min_nw);
+    hipLaunchKernelGGL(k_as_rows, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, s, P, min_nw, carry);
+    hipLaunchKernelGGL(k_as_order, dim3(1), dim3(1024), 0, s, P, min_nw, carry);
 }
 
 constexpr int BC_ROWS = 4;  // rows per k_bc_gather workgroup
@@ -207,8 +232,8 @@ __global__ __launch_bounds__(256) void k_bc_gather(Params P) {
 // after a dense fold, SPX_DENSE_FOLD=1)
 hipError_t launch_compact(const Params& P, hipStream_t s) {
     if (!P.bc) return hipSuccess;
-    hipLaunchKernelGGL(k_bc_list, dim3(1), dim3(1024), 0, s, P, 0);
-    launch_as_rows(P, 0, s);
+    hipLaunchKernelGGL(k_bc_list, dim3(1), dim3(1024), 0, s, P, 0, 0);
+    launch_as_rows(P, 0, 0, s);
     hipLaunchKernelGGL(k_bc_gather, dim3((unsigned)((P.m + BC_ROWS - 1) / BC_ROWS)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
@@ -504,10 +529,12 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_cfold(Params P, int min_nw) {
 }
 
 // compact fold: k_bc_list (the window's leaving rows join the list) then
-// k_cfold over the listed columns only (P.bc, one workgroup per CU)
-hipError_t launch_cfold(const Params& P, int min_nw, int cus, hipStream_t s) {
-    hipLaunchKernelGGL(k_bc_list, dim3(1), dim3(1024), 0, s, P, min_nw);
-    launch_as_rows(P, min_nw, s);
+// k_cfold over the listed columns only (P.bc, one workgroup per CU); carry:
+// dw follows y_w across the fold (k_as_rows)
+hipError_t launch_cfold(const Params& P, int min_nw, int cus, hipStream_t s, bool carry) {
+    const int cy = (carry && P.AS) ? 1 : 0;
+    hipLaunchKernelGGL(k_bc_list, dim3(1), dim3(1024), 0, s, P, min_nw, cy);
+    launch_as_rows(P, min_nw, cy, s);
     // every column group of the list needs a workgroup (m > 16,384: more
     // groups than CUs)
     const int64_t ngmax = P.L / 64;
@@ -523,8 +550,8 @@ hipError_t launch_cfold(const Params& P, int min_nw, int cus, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_fold(const Params& P, int min_nw, int cus, hipStream_t s) {
-    if (P.bc && P.cfold) return launch_cfold(P, min_nw, cus, s);  // the listed columns only
+hipError_t launch_fold(const Params& P, int min_nw, int cus, hipStream_t s, bool carry) {
+    if (P.bc && P.cfold) return launch_cfold(P, min_nw, cus, s, carry);  // the listed columns only
     if (P.tab) {  // T_w and dw first: k_fold resets the window
         const hipError_t e = launch_tab_fold(P, min_nw, cus, s);
         if (e != hipSuccess) return e;

@@ -83,7 +83,9 @@ hipError_t launch_tail(const Params& P, int nparts, hipStream_t s);
 hipError_t launch_materialize(const Params& P, double* out, hipStream_t s);
 hipError_t launch_reduced_costs(const Params& P, double* e, hipStream_t s);
 hipError_t launch_objective(const Params& P, hipStream_t s);
-hipError_t launch_fold(const Params& P, int min_nw, int cus, hipStream_t s);
+// carry (compact pricing, the compact fold): dw[j] += sum_t SY[t] Wt[j][t]
+// before the fold changes y_w, and stays valid (bc_n[5]) if it was
+hipError_t launch_fold(const Params& P, int min_nw, int cus, hipStream_t s, bool carry = false);
 // steepest edge (P.steep): weights at the slack basis; B_w^T alpha, U^T alpha
 // and gamma_p of the pending pivot before a pricing pass
 hipError_t launch_se_init(const Params& P, hipStream_t s);
