@@ -882,6 +882,15 @@ int spx_loop_layout(spx_ctx* ctx, int32_t out[SPX_LOOP_LAYOUT_FIELDS]);
  * the columns of rows whose slack has left the basis. */
 int spx_ftran_cols(spx_ctx* ctx, int32_t* cols);
 
+/* Compact pricing's row form (DESIGN.md §4 "Compact pricing"): out[0] = the
+ * longest list of rows whose columns a compact pass reads as coalesced rows
+ * handed to the lanes through LDS (SPX_CPRICE_ROWS, 512 by default, clamped
+ * to the rows of the compact copy of A; 0 = every pass gathers term by term,
+ * as a pass with a longer list does), out[1] = the bytes of LDS each wave of
+ * the pass holds for it.  Both 0 where the context does not price compactly.
+ * Either form computes the same bits. */
+int spx_cprice_rows(spx_ctx* ctx, int32_t out[2]);
+
 /* What the loop has enqueued since spx_create (monotone counters, so a
  * caller can difference them around a timed region): out[0] passes launched
  * eagerly (step-wise spx_price/spx_pivot included), [1] captured-hipGraph

@@ -688,6 +688,15 @@ class Context:
         check(self._L.spx_ftran_cols(self._h, ctypes.byref(v)))
         return v.value
 
+    def cprice_rows(self):
+        """Compact pricing's row form (spx_cprice_rows): ``rows`` is the longest
+        list whose columns a pass reads as coalesced rows through LDS
+        (``SPX_CPRICE_ROWS``; 0: every pass gathers), ``slot_bytes`` the LDS
+        each wave holds for it.  Both 0 without compact pricing."""
+        out = (ctypes.c_int32 * 2)()
+        check(self._L.spx_cprice_rows(self._h, out))
+        return {"rows": out[0], "slot_bytes": out[1]}
+
     def dispatch_stats(self):
         """Monotone counts of what the loop enqueued (spx_dispatch_stats).
         ``graph_builds`` counts the times the library stopped to build its

@@ -52,6 +52,7 @@ SIGNATURES = {
     "spx_comm_info": (ctypes.c_int, [_p, _p, _p]),
     "spx_mbox_export": (ctypes.c_int, [_p, _p]),
     "spx_ftran_cols": (ctypes.c_int, [_p, _p]),
+    "spx_cprice_rows": (ctypes.c_int, [_p, _p]),
     "spx_mbox_attach": (ctypes.c_int, [_p, _p]),
     "spx_reset": (ctypes.c_int, [_p]),
     "spx_reinvert": (ctypes.c_int, [_p]),

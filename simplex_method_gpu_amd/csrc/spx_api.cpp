@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "spx_cprows.h"
 #include "spx_ctx.h"
 #include "spx_tableau.h"
 
@@ -1172,6 +1173,21 @@ int cprice_setup(spx_ctx* x) {
     int per_cu = 0, per_cu_d = 0;
     HIP_TRY(price_prepare(cc, &per_cu));
     HIP_TRY(price_prepare(x->dcfg, &per_cu_d));  // (its LDS attribute)
+    // the row form's slot of every wave behind them (spx_cprows.h), as long as
+    // the slots take no workgroup off a CU: the grid and the waves per SIMD
+    // stay what they are without them.  Where cf / cpos / crow are large (16
+    // bytes a stored row: 64 KB at m = 16384) the limit steps down a tier
+    // (512 -> 256 -> 128 -> 0) until the workgroups per CU are those again
+    const size_t lds_base = cc.lds_bytes;
+    P.cp_rows = spx_cprows::limit_from(std::getenv("SPX_CPRICE_ROWS"), cap);
+    for (;;) {
+        int with_slots = per_cu;
+        cc.lds_bytes = lds_base + spx_cprows::lds_bytes(cc.block / 64, P.cp_rows);
+        cc.wm = P.cp_rows > 0 ? 7 : 6;  // (7: the kernel that has the row form; 6: the gather form alone)
+        if (P.cp_rows > 0) HIP_TRY(price_prepare(cc, &with_slots));
+        if (P.cp_rows == 0 || with_slots >= per_cu) break;
+        P.cp_rows = spx_cprows::tier_below(P.cp_rows);
+    }
     // one wave per column; every workgroup the CUs hold at once, within the
     // partial slots setup_common allocated
     const int waves = cc.block / 64;
@@ -2115,6 +2131,13 @@ int spx_ftran_cols(spx_ctx* x, int32_t* cols) {
         HIP_TRY(hipStreamSynchronize(x->stream));
         HIP_TRY(hipMemcpy(cols, x->P.bc_n, sizeof(int32_t), hipMemcpyDeviceToHost));
     }
+    return SPX_OK;
+}
+
+int spx_cprice_rows(spx_ctx* x, int32_t out[2]) {
+    if (!x || !out) return fail(SPX_ERR_ARG, "NULL argument");
+    out[0] = x->cp_ok ? x->P.cp_rows : 0;
+    out[1] = x->cp_ok ? (int32_t)(spx_cprows::slot_doubles(x->P.cp_rows) * sizeof(double)) : 0;
     return SPX_OK;
 }
 

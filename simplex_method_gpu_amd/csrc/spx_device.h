@@ -383,7 +383,10 @@ struct Params {
     double* AS;
     int64_t as_ld;
     int32_t as_cap;
-    int32_t pad_as;
+    // the longest list whose columns are read in the row form (spx_cprows.h;
+    // SPX_CPRICE_ROWS, 0 = the gather form everywhere); the pass's dynamic LDS
+    // holds a slot of slot_doubles(cp_rows) per wave behind cf / cpos / crow
+    int32_t cp_rows;
     int32_t* as_ord;
     int32_t* as_off;
 };

@@ -8,6 +8,7 @@
 
 #include "spx_device.h"
 #include "spx_common.h"
+#include "spx_cprows.h"
 #include "spx_handoff.h"
 #include "spx_kernels.h"
 #include "spx_tabdev.h"
@@ -77,6 +78,12 @@ __device__ __forceinline__ int best_wave(const PricePartial* red) {
 // it 0.5 us per pass); WM 2 always carries it
 // WM 6 = compact pricing (P.AS, spx_device.h): no A stream; a column's base
 // row dot comes from the listed rows of A, y_w . A_j - c_j from dw[j].
+// WM 7 = WM 6 with the row form of the column loop (spx_cprows.h) for lists
+// within the row limit, the gather form for the others.  An instantiation of
+// its own: compiled beside the row form, the whole pass (its prologue as
+// well) is allocated and scheduled differently and the gather form runs 1.6
+// us slower at C3, so a context without the row form (SPX_CPRICE_ROWS=0)
+// launches WM 6, whose code stays what it was.
 // DW: the dense pass (WM 1 / 2) that opens a compact-priced window: it also
 // stores dw[j] for every column it prices and marks dw valid (its own
 // instantiations, so the plain dense pass keeps its code)
@@ -85,7 +92,8 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
     DevState* st = P.st;
     constexpr int WAVES = BLOCK / 64;
     constexpr bool WIN = WM != 0;
-    constexpr bool CP = WM == 6;
+    constexpr bool CP = WM == 6 || WM == 7;
+    constexpr bool CPR = WM == 7;  // compact pricing with the row form beside the gather form
     static_assert(!DW || WM == 1 || WM == 2, "dw is stored by the dense window passes");
     constexpr bool LDS_R = WM == 1 || WM == 4;
     constexpr bool SE = WM == 4 || WM == 5;
@@ -646,66 +654,237 @@ __global__ __launch_bounds__(BLOCK) void k_price(Params P) {
             rc0[u] = par ? 0.0 : cv;
             rc1[u] = par ? cv : 0.0;
         }
-        // Two columns in flight: a column's operands are requested while the
-        // one before it is summed, and its list entry a column earlier still
-        // (indices clamped into the list: every load is unconditional)
-        double av[KR], wv = 0.0, dv = 0.0, aqj = 0.0;
-        auto request = [&](int64_t jj, double (&xa)[KR], double& xw, double& xd, double& xq) {
-            const double* as = P.AS + jj * ald;
-            const double* aq = P.A + jj * L + qq;
-            xw = (pend && lane < tau) ? P.Wt[jj * KW + lane] : 0.0;
-            xd = lane == 0 ? P.dw[jj] : 0.0;
-#pragma unroll
-            for (int u = 0; u < KR; ++u) xa[u] = *(rp[u] < 0 ? aq : as + rp[u]);
-            xq = qrem ? *aq : 0.0;
-        };
-        const int ilast = nlist > 0 ? nlist - 1 : 0;
-        int64_t jn = nbl(idx0 + stride < nlist ? idx0 + stride : ilast);
-        if (idx0 < nlist) request(j0, av, wv, dv, aqj);
-        int64_t jc = j0;
-        for (int idx = idx0; idx < nlist; idx += stride) {
-            const int64_t j = jc;
-            const double* as = P.AS + j * ald;
-            const int64_t jn2 = nbl(idx + 2 * stride < nlist ? idx + 2 * stride : ilast);
-            double avn[KR], wvn = 0.0, dvn = 0.0, aqn = 0.0;
-            const bool more = idx + stride < nlist;
-            if (more) request(jn, avn, wvn, dvn, aqn);
-            double b0 = 0.0, b1 = 0.0;
-#pragma unroll
-            for (int u = 0; u < KR; ++u) {
-                b0 = fma(av[u], rc0[u], b0);
-                b1 = fma(av[u], rc1[u], b1);
-            }
-            bool qdone = !qrem;
-            auto unit_term = [&]() {
-                if (qq & 1) b1 = fma(aqj, 1.0, b1);
-                else b0 = fma(aqj, 1.0, b0);
-                qdone = true;
+        if constexpr (CPR) {
+            // Row form (spx_cprows.h): a column's listed entries are one contiguous
+            // run of AS, so the wave reads it as NC coalesced chunks (lane l takes
+            // entries l + 64 t, indices past the list re-read entry 0), stores the
+            // chunks to its private LDS slot and every lane takes its terms from
+            // there: av[u] = slot[rp[u]], a long run's rest slot[cpos[i]].  The
+            // same operands enter the same fma chain in the same order as in the
+            // gather form below, so the bits are its bits.  The slot belongs to
+            // one wave, whose LDS instructions execute in program order: the store,
+            // the reads and the next column's store need no workgroup barrier
+            // (wave_barrier keeps the compiler from moving one across another).
+            // D columns in flight: once column k's operands have arrived and its
+            // row is in the slot, column k + D - 1 is requested into the registers
+            // that held it, and column k is summed from the slot while D - 1
+            // requests fly.  Every request is unconditional (a column past the
+            // wave's last one re-reads the list's last column; a lane without a
+            // Wt, dw or unit entry reads one and drops it when the column is
+            // summed): the wait for a column then counts the loads issued behind
+            // it and leaves them in flight, where a request behind a branch makes
+            // that count zero, i.e. a wait for every load.  For the same reason
+            // the list entries of the wave's next 64 columns are one load (lane l:
+            // the wave's column l) read by lane index, not a load per column whose
+            // wait would cover the operands in flight.
+            // (A re-read column may be one another wave is pricing, whose Wt entry
+            // that wave is storing: the value read is dropped, never summed.  The
+            // pipeline drains and refills at every 64th column of a wave: one more
+            // round trip per 64 columns.)
+            // (DV: Devex.  Its weight load sits in consider; compiled into the
+            // Dantzig loop behind a branch, the wait for that load's register at
+            // the branch's end is a wait for every operand in flight.)
+            // consider's last line, its argmin update, alone: what consider does
+            // under Dantzig.  (Calling one such lambda from consider as well
+            // changed the code of every dense instantiation, which is to stay
+            // instruction for instruction what it was.)
+            auto consider_plain = [&](int64_t j, double e, double wn) {
+                if (argmin_better(e, j, best, bj)) { best = e; bj = j; bw = wn; be = e; }
             };
-            for (int i = iR; i < i1; ++i) {
-                const int r = crow[i];
-                if (!qdone && r > (int)qq) unit_term();
-                const double a = as[cpos[i]];
-                if (r & 1) b1 = fma(a, cf[i], b1);
-                else b0 = fma(a, cf[i], b0);
-            }
-            if (!qdone) unit_term();
-            double sa = fma(syl, wv, dv);
-            double wn = fma(uq, wv, b0 + b1);
-            wave_sum2(sa, wn);
-            if (pend && lane == 0) P.Wt[j * KW + tau] = wn;
-            const double e = pend ? fma(syp, wn, sa) : sa;
-            consider(j, e, wn, 0.0);
-            if (more) {
+            auto run_rows = [&](auto nc_t, auto dv_t) {
+                constexpr int NC = decltype(nc_t)::value;
+                constexpr bool DV = decltype(dv_t)::value;
+                constexpr int D = spx_cprows::depth(NC);
+                constexpr int MASK = 64 * NC - 1;
+                if (idx0 >= nlist) return;
+                double* slot = reinterpret_cast<double*>(crow + capp) + wave * spx_cprows::slot_doubles(P.cp_rows);
+                const int lim = min(cp_S, (int)ald);
+                // the register terms' places in the slot; the unit entry (position
+                // -1) is the slot's entry past the row, where the unit lane puts
+                // its A[q, j]
+                int pu[KR];
 #pragma unroll
-                for (int u = 0; u < KR; ++u) av[u] = avn[u];
-                wv = wvn;
-                dv = dvn;
-                aqj = aqn;
-            }
-            jc = jn;
-            jn = jn2;
+                for (int u = 0; u < KR; ++u) pu[u] = rp[u] < 0 ? 64 * NC : (rp[u] & MASK);
+                const bool has_w = pend && lane < tau;
+                const int wl = has_w ? lane : 0;
+                // dw[j] (lane 0 adds it) and A[q, j] (the unit lane's term) share a
+                // register: lane 0 loads dw[j], every other lane A[q, j]; a unit
+                // lane 0 takes its A[q, j] from lane 1
+                constexpr int R = D - 1;  // operand buffers: the columns requested ahead
+                double xr[R][NC], xw[R], xo[R];
+                int jr[R];
+                auto request = [&](int64_t jj, double (&r)[NC], double& w, double& o) {
+                    const double* as = P.AS + jj * ald;
+                    w = P.Wt[jj * KW + wl];
+                    o = *(lane == 0 ? P.dw + jj : P.A + jj * L + qq);
+#pragma unroll
+                    for (int t = 0; t < NC; ++t) {
+                        const int i = lane + 64 * t;
+                        r[t] = as[i < lim ? i : 0];
+                    }
+                };
+                const int ilast = nlist - 1;
+                auto list64 = [&](int k0) -> int {  // lane l: the list entry of the wave's column k0 + l
+                    const int64_t i = (int64_t)idx0 + ((int64_t)k0 + lane) * stride;
+                    return (int)nbl(i < nlist ? (int)i : ilast);
+                };
+                int jl = 0, idx = idx0, k = 0;  // the wave's column k0 + k at list index idx
+                auto step = [&](auto d_t) {
+                    constexpr int d = decltype(d_t)::value;
+                    const int64_t j = jr[d];
+                    const double wv = has_w ? xw[d] : 0.0;
+                    const double dv = lane == 0 ? xo[d] : 0.0;
+                    const double aqj = unitq ? (lane == 0 ? readlane_d(xo[d], 1) : xo[d]) : 0.0;
+                    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                    for (int t = 0; t < NC; ++t) slot[lane + 64 * t] = xr[d][t];
+                    if (unitq) slot[64 * NC] = aqj;
+                    __builtin_amdgcn_wave_barrier();
+                    jr[d] = __builtin_amdgcn_readlane(jl, min(k + R, 63));
+                    request(jr[d], xr[d], xw[d], xo[d]);
+                    double av[KR];
+#pragma unroll
+                    for (int u = 0; u < KR; ++u) av[u] = slot[pu[u]];
+                    double b0 = 0.0, b1 = 0.0;
+#pragma unroll
+                    for (int u = 0; u < KR; ++u) {
+                        b0 = fma(av[u], rc0[u], b0);
+                        b1 = fma(av[u], rc1[u], b1);
+                    }
+                    bool qdone = !qrem;
+                    auto unit_term = [&]() {
+                        if (qq & 1) b1 = fma(aqj, 1.0, b1);
+                        else b0 = fma(aqj, 1.0, b0);
+                        qdone = true;
+                    };
+                    for (int i = iR; i < i1; ++i) {
+                        const int r = crow[i];
+                        if (!qdone && r > (int)qq) unit_term();
+                        const double a = slot[cpos[i] & MASK];
+                        if (r & 1) b1 = fma(a, cf[i], b1);
+                        else b0 = fma(a, cf[i], b0);
+                    }
+                    if (!qdone) unit_term();
+                    __builtin_amdgcn_wave_barrier();
+                    double sa = fma(syl, wv, dv);
+                    double wn = fma(uq, wv, b0 + b1);
+                    wave_sum2(sa, wn);
+                    if (pend && lane == 0) P.Wt[j * KW + tau] = wn;
+                    const double e_j = pend ? fma(syp, wn, sa) : sa;
+                    if constexpr (DV) consider(j, e_j, wn, 0.0);
+                    else consider_plain(j, e_j, wn);
+                    idx += stride;
+                    ++k;
+                };
+                // 64 columns of the wave per list load; the pipeline drains at its
+                // end (the requests past it re-read its last column)
+                int k0 = 0;
+                while (idx < nlist) {
+                    jl = list64(k0);
+                    k0 += 64;
+#pragma unroll
+                    for (int d = 0; d < R; ++d) {
+                        jr[d] = __builtin_amdgcn_readlane(jl, d);
+                        request(jr[d], xr[d], xw[d], xo[d]);
+                    }
+                    // (whole rounds of R columns in a loop without a branch, the
+                    // rest behind it: a step behind a condition inside the loop
+                    // has the compiler copy the operands in flight where the paths
+                    // join, which waits for them)
+                    const int64_t left = ((int64_t)nlist - idx + stride - 1) / stride;
+                    const int ng = (int)(left < 64 ? left : 64);
+                    k = 0;
+                    while (k + R <= ng) {
+                        step(std::integral_constant<int, 0>());
+                        if constexpr (R == 3) {
+                            step(std::integral_constant<int, 1>());
+                            step(std::integral_constant<int, 2>());
+                        } else {
+                            static_assert(R == 1, "one or three columns requested ahead");
+                        }
+                    }
+                    if constexpr (R == 3) {
+                        const int rem = ng - k;
+                        if (rem >= 1) step(std::integral_constant<int, 0>());
+                        if (rem >= 2) step(std::integral_constant<int, 1>());
+                    }
+                }
+            };
+            const int cp_nc = spx_cprows::chunks(cp_S, P.cp_rows);
+            const bool cp_dv = P.devex != 0;
+            if (cp_nc == 2 && !cp_dv) run_rows(std::integral_constant<int, 2>(), std::false_type());
+            else if (cp_nc == 4 && !cp_dv) run_rows(std::integral_constant<int, 4>(), std::false_type());
+            else if (cp_nc == 8 && !cp_dv) run_rows(std::integral_constant<int, 8>(), std::false_type());
+            else if (cp_nc == 2) run_rows(std::integral_constant<int, 2>(), std::true_type());
+            else if (cp_nc == 4) run_rows(std::integral_constant<int, 4>(), std::true_type());
+            else if (cp_nc == 8) run_rows(std::integral_constant<int, 8>(), std::true_type());
+            // (a jump, not a condition around the gather form: WM 6 then compiles
+            // to the code it had)
+            if (cp_nc != 0) goto cp_priced;
         }
+        {
+            // Two columns in flight: a column's operands are requested while the
+            // one before it is summed, and its list entry a column earlier still
+            // (indices clamped into the list: every load is unconditional)
+            double av[KR], wv = 0.0, dv = 0.0, aqj = 0.0;
+            auto request = [&](int64_t jj, double (&xa)[KR], double& xw, double& xd, double& xq) {
+                const double* as = P.AS + jj * ald;
+                const double* aq = P.A + jj * L + qq;
+                xw = (pend && lane < tau) ? P.Wt[jj * KW + lane] : 0.0;
+                xd = lane == 0 ? P.dw[jj] : 0.0;
+#pragma unroll
+                for (int u = 0; u < KR; ++u) xa[u] = *(rp[u] < 0 ? aq : as + rp[u]);
+                xq = qrem ? *aq : 0.0;
+            };
+            const int ilast = nlist > 0 ? nlist - 1 : 0;
+            int64_t jn = nbl(idx0 + stride < nlist ? idx0 + stride : ilast);
+            if (idx0 < nlist) request(j0, av, wv, dv, aqj);
+            int64_t jc = j0;
+            for (int idx = idx0; idx < nlist; idx += stride) {
+                const int64_t j = jc;
+                const double* as = P.AS + j * ald;
+                const int64_t jn2 = nbl(idx + 2 * stride < nlist ? idx + 2 * stride : ilast);
+                double avn[KR], wvn = 0.0, dvn = 0.0, aqn = 0.0;
+                const bool more = idx + stride < nlist;
+                if (more) request(jn, avn, wvn, dvn, aqn);
+                double b0 = 0.0, b1 = 0.0;
+#pragma unroll
+                for (int u = 0; u < KR; ++u) {
+                    b0 = fma(av[u], rc0[u], b0);
+                    b1 = fma(av[u], rc1[u], b1);
+                }
+                bool qdone = !qrem;
+                auto unit_term = [&]() {
+                    if (qq & 1) b1 = fma(aqj, 1.0, b1);
+                    else b0 = fma(aqj, 1.0, b0);
+                    qdone = true;
+                };
+                for (int i = iR; i < i1; ++i) {
+                    const int r = crow[i];
+                    if (!qdone && r > (int)qq) unit_term();
+                    const double a = as[cpos[i]];
+                    if (r & 1) b1 = fma(a, cf[i], b1);
+                    else b0 = fma(a, cf[i], b0);
+                }
+                if (!qdone) unit_term();
+                double sa = fma(syl, wv, dv);
+                double wn = fma(uq, wv, b0 + b1);
+                wave_sum2(sa, wn);
+                if (pend && lane == 0) P.Wt[j * KW + tau] = wn;
+                const double e = pend ? fma(syp, wn, sa) : sa;
+                consider(j, e, wn, 0.0);
+                if (more) {
+#pragma unroll
+                    for (int u = 0; u < KR; ++u) av[u] = avn[u];
+                    wv = wvn;
+                    dv = dvn;
+                    aqj = aqn;
+                }
+                jc = jn;
+                jn = jn2;
+            }
+        }
+        [[maybe_unused]] cp_priced:;
     } else {
     // The first CH chunks of every column are loaded before the previous
     // column's reduction (and, for the first column, before the LDS fill), so
@@ -1216,6 +1395,7 @@ static hipError_t price_dispatch(const PriceCfg& c, const Params* P, hipStream_t
         return hipErrorInvalidValue;
     }
     if (c.wm == 6) SPX_PV(false, 6);
+    if (c.wm == 7) SPX_PV(false, 7);
     if (c.wm == 0) {
         if (c.lds_y) SPX_PV(true, 0);
         SPX_PV(false, 0);
