@@ -205,8 +205,12 @@ typedef struct spx_opts {
  *         readback of y and every spx_set_algorithm in between.  Pivots, the
  *         trace, refactor_every, spx_iterate(k) and spx_get_primal_flips count
  *         both phases.  With phase 1 on and a feasible entry the loop launches
- *         exactly the passes it launches without.  Still out: a long-step phase
- *         1, phase 1 under SPX_ALGO_PRIMAL. */
+ *         exactly the passes it launches without.  Phase 1 prices with
+ *         Dantzig's rule, or with the steepest-edge weights where the loop's
+ *         rule is steepest edge and spx_set_primal_phase_one_pricing says so
+ *         (below).  Still out: a long-step phase 1, phase 1 under
+ *         SPX_ALGO_PRIMAL, a rule that differs between the phases, free columns
+ *         under steepest edge. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
 #define SPX_ALGO_PRIMAL_BOX 2
@@ -260,7 +264,17 @@ typedef struct spx_opts {
  *           weights.  Not together with phase 1 (SPX_FLAG_PRIMAL_PHASE1 /
  *           spx_set_primal_phase1): spx_create refuses the two flags with
  *           SPX_ERR_ARG, and whichever setter arrives second returns
- *           SPX_ERR_STATE. */
+ *           SPX_ERR_STATE -- unless phase 1's own rule was set to STEEPEST first
+ *           (SPX_FLAG_PRIMAL_PHASE1_STEEPEST / spx_set_primal_phase_one_pricing,
+ *           DESIGN.md §7l).  Then a pass that starts with ninf > 0 stays the
+ *           phase-1 pass described above (w, y1, d_j without a cost term, the
+ *           candidates, the phase-aware ratio test, flips, INFEASIBLE, no y
+ *           update) except that p = argmin of -d_j^2 / gamma_j over the
+ *           candidates, first column on ties; every pivot of either phase
+ *           applies the update above, a flip changes no weight, and the switch
+ *           to phase 2 keeps the weights (no restart).  The weights start as
+ *           without phase 1; neither start depends on feasibility.  Free columns
+ *           stay refused under steepest edge. */
 #define SPX_PRIMAL_PRICING_DANTZIG  0
 #define SPX_PRIMAL_PRICING_STEEPEST 1
 
@@ -415,7 +429,18 @@ typedef struct spx_opts {
                                          rule SPX_PRIMAL_PRICING_STEEPEST (default
                                          DANTZIG); accepted and inert under the other
                                          algorithms; SPX_ERR_ARG together with
-                                         SPX_FLAG_PRIMAL_PHASE1                       */
+                                         SPX_FLAG_PRIMAL_PHASE1 unless
+                                         SPX_FLAG_PRIMAL_PHASE1_STEEPEST is set too   */
+
+#define SPX_FLAG_PRIMAL_PHASE1_STEEPEST 65536 /* the bounded primal loop's phase 1 prices with
+                                         the steepest-edge weights where the loop's rule
+                                         is SPX_PRIMAL_PRICING_STEEPEST
+                                         (spx_set_primal_phase_one_pricing; default
+                                         DANTZIG, under which SPX_FLAG_PRIMAL_PHASE1 with
+                                         SPX_FLAG_PRIMAL_STEEPEST stays refused); with it
+                                         the three flags together are accepted; accepted
+                                         and inert without the other two and under the
+                                         other algorithms                             */
 
 #define SPX_FLAG_PRIMAL_EXACT_WEIGHTS 32768 /* the bounded primal loop restarts its
                                          steepest-edge weights for a warm basis at
@@ -569,8 +594,24 @@ int spx_set_primal_phase1(spx_ctx* ctx, int32_t on);
 /* Entering rule of the bounded primal loop (SPX_PRIMAL_PRICING_*), between any
  * two calls and under any algorithm; takes effect with the next bounded primal
  * pass.  A change of rule restarts the steepest-edge weights.  SPX_ERR_ARG for
- * NULL or an unknown rule; SPX_ERR_STATE for STEEPEST while phase 1 is on. */
+ * NULL or an unknown rule; SPX_ERR_STATE for STEEPEST while phase 1 is on
+ * (unless spx_set_primal_phase_one_pricing chose STEEPEST for phase 1). */
 int spx_set_primal_pricing(spx_ctx* ctx, int32_t rule);
+
+/* Entering rule of the bounded primal loop's phase-1 passes where the loop's
+ * rule is steepest edge: SPX_PRIMAL_PRICING_DANTZIG (the default: phase 1 and
+ * steepest edge stay refused together, as above) or SPX_PRIMAL_PRICING_STEEPEST
+ * (SPX_FLAG_PRIMAL_PHASE1_STEEPEST at spx_create).  Between any
+ * two calls and under any algorithm.  Consulted only when phase 1 is on and the
+ * loop's rule is STEEPEST; otherwise accepted and inert (a loop whose rule is
+ * Dantzig prices both phases with Dantzig).  With it at STEEPEST,
+ * spx_set_primal_phase1(on) under steepest edge and
+ * spx_set_primal_pricing(STEEPEST) under phase 1 are accepted.  It restarts no
+ * weights.  SPX_ERR_ARG for NULL or an unknown rule; SPX_ERR_STATE for DANTZIG
+ * while phase 1 is on and the loop's rule is STEEPEST (the call would re-create
+ * the refused state: switch one of the two off first).  (The name spells the
+ * digit out: the bindings' header scan reads [a-z_] names.) */
+int spx_set_primal_phase_one_pricing(spx_ctx* ctx, int32_t rule);
 
 /* Steepest-edge weights w[0..n) of the current basis, by column: the non-basic
  * entries are live (1 + ||B^-1 A_j||^2 as the recurrence keeps it, a pending
@@ -744,7 +785,9 @@ int spx_kernel_times(spx_ctx* ctx, double* price_ms, int64_t* price_launches,
  * the four-step passes since the last call (resets); a step that found nothing
  * to do (phase 2, y current) is counted with its near-zero time.  Under
  * SPX_PRIMAL_PRICING_STEEPEST the same counters carry the tau = alpha^T B^-1
- * step of every pass (a pass without a pivot with its near-zero time). */
+ * step of every pass (a pass without a pivot with its near-zero time); a
+ * phase-1 pass under steepest edge (spx_set_primal_phase_one_pricing) has both
+ * steps and counts two. */
 int spx_pbox_vtb_times(spx_ctx* ctx, double* ms, int64_t* launches);
 
 /* With SPX_FLAG_TIMING: total device milliseconds and count of the exact weight

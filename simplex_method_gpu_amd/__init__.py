@@ -30,7 +30,7 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "DUAL_PRICING_DANTZIG", "DUAL_PRICING_STEEPEST", "FLAG_DUAL_STEEPEST",
            "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX",
            "FLAG_PRIMAL_PHASE1", "PRIMAL_PRICING_DANTZIG", "PRIMAL_PRICING_STEEPEST", "FLAG_PRIMAL_STEEPEST",
-           "PRIMAL_WEIGHTS_REFERENCE", "PRIMAL_WEIGHTS_EXACT", "FLAG_PRIMAL_EXACT_WEIGHTS",
+           "PRIMAL_WEIGHTS_REFERENCE", "PRIMAL_WEIGHTS_EXACT", "FLAG_PRIMAL_EXACT_WEIGHTS", "FLAG_PRIMAL_PHASE1_STEEPEST",
            "CostRanging", "RhsRanging"]
 
 FLAG_TIMING = 1
@@ -70,6 +70,8 @@ FLAG_PRIMAL_STEEPEST = 16384  # the bounded primal loop starts with exact steepe
 # SPX_PRIMAL_WEIGHTS_*): the reference framework 1 + ||A_j||^2, or the exact 1 + ||B^-1 A_j||^2
 PRIMAL_WEIGHTS_REFERENCE, PRIMAL_WEIGHTS_EXACT = 0, 1
 FLAG_PRIMAL_EXACT_WEIGHTS = 32768  # the steepest-edge weights of a warm basis restart at the exact norms
+# phase 1 prices with the steepest-edge weights where the loop's rule is steepest edge (default: the two are refused)
+FLAG_PRIMAL_PHASE1_STEEPEST = 65536
 
 
 class SolveStatus(IntEnum):
@@ -203,7 +205,8 @@ class Context:
                  dual_pricing: int = DUAL_PRICING_DANTZIG, upper=None,
                  dual_ratio: int = DUAL_RATIO_TEXTBOOK, primal_phase1: bool = False,
                  primal_pricing: int = PRIMAL_PRICING_DANTZIG,
-                 primal_weights: int = PRIMAL_WEIGHTS_REFERENCE, lower=None):
+                 primal_weights: int = PRIMAL_WEIGHTS_REFERENCE, lower=None,
+                 primal_phase1_pricing: int = PRIMAL_PRICING_DANTZIG):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -229,6 +232,9 @@ class Context:
         if primal_weights not in (PRIMAL_WEIGHTS_REFERENCE, PRIMAL_WEIGHTS_EXACT):
             raise ValueError("primal_weights must be PRIMAL_WEIGHTS_REFERENCE or PRIMAL_WEIGHTS_EXACT")
         self._primal_weights = primal_weights
+        if primal_phase1_pricing not in (PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST):
+            raise ValueError("primal_phase1_pricing must be PRIMAL_PRICING_DANTZIG or PRIMAL_PRICING_STEEPEST")
+        self._primal_phase1_pricing = primal_phase1_pricing
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
@@ -239,7 +245,8 @@ class Context:
                    | (FLAG_DUAL_LONG_STEP if dual_ratio == DUAL_RATIO_LONG_STEP else 0)
                    | (FLAG_PRIMAL_PHASE1 if primal_phase1 else 0)
                    | (FLAG_PRIMAL_STEEPEST if primal_pricing == PRIMAL_PRICING_STEEPEST else 0)
-                   | (FLAG_PRIMAL_EXACT_WEIGHTS if primal_weights == PRIMAL_WEIGHTS_EXACT else 0))
+                   | (FLAG_PRIMAL_EXACT_WEIGHTS if primal_weights == PRIMAL_WEIGHTS_EXACT else 0)
+                   | (FLAG_PRIMAL_PHASE1_STEEPEST if primal_phase1_pricing == PRIMAL_PRICING_STEEPEST else 0))
         h = ctypes.c_void_p()
         if A_cols is not None:
             A_cols = np.ascontiguousarray(A_cols, dtype=np.float64)
@@ -410,6 +417,15 @@ class Context:
         PRIMAL_PRICING_STEEPEST.  A change of rule restarts the weights."""
         check(self._L.spx_set_primal_pricing(self._h, rule))
         self._primal_pricing = rule
+
+    def set_primal_phase1_pricing(self, rule: int):
+        """Entering rule of the phase-1 passes where the loop's rule is
+        steepest edge (spx_set_primal_phase_one_pricing): PRIMAL_PRICING_DANTZIG
+        (the default: phase 1 and steepest edge are refused together) or
+        PRIMAL_PRICING_STEEPEST (phase 1 keys its candidates with the weights).
+        Inert unless phase 1 is on and the rule is steepest edge."""
+        check(self._L.spx_set_primal_phase_one_pricing(self._h, rule))
+        self._primal_phase1_pricing = rule
 
     def primal_weights(self):
         """Steepest-edge weights of the bounded primal loop by column, n entries
@@ -726,6 +742,7 @@ class Context:
         cfg["primal_pricing"] = self._primal_pricing
         cfg["dual_ratio"] = self._dual_ratio
         cfg["primal_weights"] = self._primal_weights
+        cfg["primal_phase1_pricing"] = self._primal_phase1_pricing
         return cfg
 
     def loop_layout(self):

@@ -46,7 +46,14 @@
 //   --primal-pricing R  entering rule of --primal-box: dantzig (default) | steepest
 //                  (exact steepest edge, SPX_PRIMAL_PRICING_STEEPEST); without
 //                  --primal-box it is refused with the usage message (exit 1);
-//                  not with --phase1 (the library's refusal is printed)
+//                  not with --phase1 (the library's refusal is printed) unless
+//                  --phase1-pricing steepest is given
+//   --phase1-pricing R  entering rule of --phase1's passes under --primal-pricing
+//                  steepest: dantzig (default: the combination is refused) |
+//                  steepest (SPX_FLAG_PRIMAL_PHASE1_STEEPEST: phase 1 keys its
+//                  candidates with the steepest-edge weights);
+//                  inert without --phase1 or under --primal-pricing dantzig;
+//                  without --primal-box it is refused by name (exit 1)
 //   --primal-weights W  how the steepest-edge weights of --primal-box restart
 //                  for a warm basis: reference (default) | exact
 //                  (SPX_FLAG_PRIMAL_EXACT_WEIGHTS); shown in --json.  The CLI
@@ -113,7 +120,7 @@ static void print_elapsed_time(const char* msg, double dur) {
 static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
-                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--primal-weights reference|exact]]"
+                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--phase1-pricing dantzig|steepest] [--primal-weights reference|exact]]"
                  " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F] [--ranging PREFIX]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
@@ -136,6 +143,7 @@ int main(int argc, char* argv[]) {
     bool mps_in = false, tableau = false, dual = false, dual_steepest = false, dual_long = false, primal_box = false, phase1 = false;
     bool primal_pricing_given = false, primal_steepest = false;
     bool primal_weights_given = false, primal_exact = false;
+    bool phase1_pricing_given = false, phase1_steepest = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -187,6 +195,16 @@ int main(int argc, char* argv[]) {
             if (r != "dantzig" && r != "steepest") { usage(); return 1; }
             primal_pricing_given = true;
             primal_steepest = r == "steepest";
+        }
+        else if (s == "--phase1-pricing") {
+            need(1);
+            const std::string r = argv[++a];
+            if (r != "dantzig" && r != "steepest") {
+                std::cerr << "--phase1-pricing " << r << ": dantzig or steepest\n";
+                return 1;
+            }
+            phase1_pricing_given = true;
+            phase1_steepest = r == "steepest";
         }
         else if (s == "--primal-weights") {
             need(1);
@@ -243,6 +261,10 @@ int main(int argc, char* argv[]) {
     if (primal_pricing_given && !primal_box) {
         std::cerr << "--primal-pricing needs --primal-box: it is the bounded primal loop's entering rule\n";
         usage();
+        return 1;
+    }
+    if (phase1_pricing_given && !primal_box) {
+        std::cerr << "--phase1-pricing needs --primal-box: it is the rule of the bounded primal loop's phase 1\n";
         return 1;
     }
     if (primal_weights_given && !primal_box) {
@@ -312,6 +334,7 @@ int main(int argc, char* argv[]) {
     if (phase1) o.flags |= SPX_FLAG_PRIMAL_PHASE1;
     if (primal_steepest) o.flags |= SPX_FLAG_PRIMAL_STEEPEST;
     if (primal_exact) o.flags |= SPX_FLAG_PRIMAL_EXACT_WEIGHTS;
+    if (phase1_steepest) o.flags |= SPX_FLAG_PRIMAL_PHASE1_STEEPEST;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)

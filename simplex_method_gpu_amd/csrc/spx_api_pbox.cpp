@@ -227,6 +227,9 @@ int vtb_events(spx_ctx* x, hipEvent_t* v0, hipEvent_t* v1) {
 // Steepest edge: a pass is price_se -> update -> step_se -> tau,
 // after the weights were restarted where nobody kept them; the pending weight
 // update lives on the device with its own operands, so nothing here tracks it.
+// Steepest edge through phase 1 (opt-in): while the host last saw
+// ninf > 0 or y stale the pass is vtb -> price_se1 -> update1 -> step_se1 -> tau;
+// the same readback brings §7h's four-step pass back, with the weights it finds.
 int iterate_pbox(spx_ctx* x, int64_t k) {
     SPX_TRY(pbox_setup(x));
     if (!x->pbox.checked) SPX_TRY(pbox_check_entry(x));
@@ -237,11 +240,15 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
         return fail(SPX_ERR_STATE, "free columns do not run with steepest-edge pricing");
     PboxArgs se_args = s.args;
     if (steep) {
-        if (s.phase1)
+        if (s.phase1 && s.p1rule != SPX_PRIMAL_PRICING_STEEPEST)  // (create and the setters refuse the state)
             return fail(SPX_ERR_STATE, "steepest-edge pricing does not run with the bounded primal loop's phase 1");
         SPX_TRY(pbox_se_setup(x));
+        if (s.phase1 && !s.se1_ready) {
+            HIP_TRY(pbox_se1_prepare(x->P, s.secfg));
+            s.se1_ready = true;
+        }
         SPX_TRY(pbox_se_restart(x));
-        se_args.price_grid = s.secfg.price_grid;  // k_pbox_update merges this pass's partials
+        se_args.price_grid = s.secfg.price_grid;  // k_pbox_update / k_pbox_update1 merges this pass's partials
     } else {
         s.se_stale = true;  // a Dantzig pass keeps no weights
     }
@@ -252,6 +259,23 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
         for (int64_t i = 0; i < round; ++i) {
             hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
             if (x->timing) SPX_TRY(pass_events(x, &p0, &p1, &u0, &u1));
+            if (steep && s.phase1 && (s.ninf > 0 || s.y_stale)) {
+                // vtb -> price_se1 -> update1 -> step_se1 -> tau: the phase is the device's
+                s.y_dirty = true;
+                hipEvent_t v0 = nullptr, v1 = nullptr, t0 = nullptr, t1 = nullptr;
+                if (x->timing) {
+                    SPX_TRY(vtb_events(x, &v0, &v1));
+                    SPX_TRY(vtb_events(x, &t0, &t1));
+                }
+                HIP_TRY(launch_pbox_vtb(x->P, s.p1, s.cfg, x->stream, v0, v1));
+                HIP_TRY(launch_pbox_price_se1(x->P, se_args, s.p1, s.se, s.secfg, x->stream, p0, p1));
+                if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
+                HIP_TRY(launch_pbox_update1(x->P, se_args, s.p1, s.cfg, x->stream, u0, u1));
+                HIP_TRY(launch_pbox_step_se1(x->P, se_args, s.p1, s.se, x->stream));
+                HIP_TRY(launch_pbox_tau(x->P, s.se, s.cfg, x->stream, t0, t1));
+                ++x->n_eager;
+                continue;
+            }
             if (steep) {  // price -> update -> step -> tau
                 hipEvent_t v0 = nullptr, v1 = nullptr;
                 if (x->timing) SPX_TRY(vtb_events(x, &v0, &v1));
@@ -338,7 +362,8 @@ int pbox_on_create(spx_ctx* x) {
     x->pbox.phase1 = (x->opts.flags & SPX_FLAG_PRIMAL_PHASE1) != 0;
     x->pbox.rule = (x->opts.flags & SPX_FLAG_PRIMAL_STEEPEST) ? SPX_PRIMAL_PRICING_STEEPEST : SPX_PRIMAL_PRICING_DANTZIG;
     x->pbox.winit = (x->opts.flags & SPX_FLAG_PRIMAL_EXACT_WEIGHTS) ? SPX_PRIMAL_WEIGHTS_EXACT : SPX_PRIMAL_WEIGHTS_REFERENCE;
-    if (x->pbox.phase1 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+    x->pbox.p1rule = (x->opts.flags & SPX_FLAG_PRIMAL_PHASE1_STEEPEST) ? SPX_PRIMAL_PRICING_STEEPEST : SPX_PRIMAL_PRICING_DANTZIG;
+    if (x->pbox.phase1 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.p1rule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_ARG, "SPX_FLAG_PRIMAL_STEEPEST with SPX_FLAG_PRIMAL_PHASE1: steepest-edge pricing does not "
                     "run during the bounded primal loop's phase 1");
     return SPX_OK;
@@ -396,7 +421,7 @@ int spx_get_primal_flips(spx_ctx* x, int64_t out[2]) {
 int spx_set_primal_phase1(spx_ctx* x, int32_t on) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (x->stepped_price) return fail(SPX_ERR_STATE, "spx_set_primal_phase1 between spx_price and spx_pivot");
-    if (on && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+    if (on && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.p1rule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_STATE, "spx_set_primal_phase1: phase 1 does not run with steepest-edge pricing "
                     "(spx_set_primal_pricing); set SPX_PRIMAL_PRICING_DANTZIG first");
     SPX_TRY(pbox_fresh_y(x));
@@ -409,7 +434,7 @@ int spx_set_primal_pricing(spx_ctx* x, int32_t rule) {
     if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
     if (rule != SPX_PRIMAL_PRICING_DANTZIG && rule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_ARG, "bad primal pricing rule %d", rule);
-    if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.phase1)
+    if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.phase1 && x->pbox.p1rule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_STATE, "spx_set_primal_pricing: steepest-edge pricing does not run with the bounded primal "
                     "loop's phase 1 (spx_set_primal_phase1); switch phase 1 off first");
     if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->dual.nfree > 0)
@@ -417,6 +442,18 @@ int spx_set_primal_pricing(spx_ctx* x, int32_t rule) {
                     "them, spx_set_bounds_lu)", (long long)x->dual.nfree);
     if (rule != x->pbox.rule) x->pbox.se_stale = true;  // a change of rule restarts the weights
     x->pbox.rule = rule;
+    return SPX_OK;
+}
+
+int spx_set_primal_phase_one_pricing(spx_ctx* x, int32_t rule) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (rule != SPX_PRIMAL_PRICING_DANTZIG && rule != SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_ARG, "bad primal phase-1 pricing rule %d", rule);
+    if (rule == SPX_PRIMAL_PRICING_DANTZIG && x->pbox.phase1 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "spx_set_primal_phase_one_pricing: SPX_PRIMAL_PRICING_DANTZIG in phase 1 does not run "
+                    "with steepest-edge pricing (spx_set_primal_pricing) while phase 1 is on (spx_set_primal_phase1); "
+                    "switch phase 1 off or set SPX_PRIMAL_PRICING_DANTZIG first");
+    x->pbox.p1rule = rule;  // (the weights do not depend on the phase: nothing restarts)
     return SPX_OK;
 }
 

@@ -150,6 +150,10 @@ struct PboxState {
     std::vector<hipEvent_t> ev_vtb;  // timing: pairs around k_pbox_vtb + k_pbox_vtb_sum, or k_pbox_tau + _sum (spx_pbox_vtb_times)
     size_t n_vtb = 0;
     int32_t rule = SPX_PRIMAL_PRICING_DANTZIG;  // entering rule (spx_set_primal_pricing)
+    // phase 1's rule (spx_set_primal_phase_one_pricing), consulted only while phase1 && rule ==
+    // STEEPEST: that state exists only with p1rule == STEEPEST (create and the three setters refuse it otherwise)
+    int32_t p1rule = SPX_PRIMAL_PRICING_DANTZIG;
+    bool se1_ready = false;  // pbox_se1_prepare ran
     spx::PboxSeArgs se{};
     spx::PboxSeCfg secfg{};
     bool se_stale = true;

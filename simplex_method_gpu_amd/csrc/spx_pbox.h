@@ -1,7 +1,7 @@
 // spx_pbox.h — the bounded primal simplex loop's kernels (spx_pbox.hip): 0 <= x
 // <= u, one rank, explicit B^-1 (Params::win == 0, in-place storage), Dantzig
 // entering column, or exact steepest edge (the *_se kernels at the end of this
-// file).  DESIGN.md §7e.
+// file; through phase 1 with the *_se1 kernels, §7l).  DESIGN.md §7e.
 //
 // A pass at iteration it is three launches on the context's stream; the kernel
 // boundaries are the only ordering between them:
@@ -264,6 +264,37 @@ hipError_t launch_pbox_price_se(const Params& P, const PboxArgs& D, const PboxSe
 hipError_t launch_pbox_step_se(const Params& P, const PboxArgs& D, const PboxSeArgs& E, hipStream_t s);
 hipError_t launch_pbox_tau(const Params& P, const PboxSeArgs& E, const PboxCfg& c, hipStream_t s, hipEvent_t e0,
                            hipEvent_t e1);
+
+// Steepest edge through phase 1 (opt-in, spx_set_primal_phase_one_pricing).
+// The weights depend on the basis alone, so a phase-1 pass keys its candidates
+// with them and every pivot of either phase records the same update.  A pass
+// enqueued while the host last saw ninf > 0 or y stale is five steps, ordered by
+// kernel boundaries only:
+//   k_pbox_vtb + k_pbox_vtb_sum   as in a phase-1 Dantzig pass (yp, or y at the switch).
+//   k_pbox_price_se1 k_pbox_price_se with the phase read from PboxPhase::ninf:
+//                  phase 1 takes yp as its first operand and no c_j, phase 2 y
+//                  and c_j; rho.A_j, tau.A_j, the recurrence under the pending
+//                  word, the one owner's store of gamma_j, the skipped leaving
+//                  column, the per-lane order and the three LDS layouts
+//                  (PboxSeCfg::lds_vecs) are k_pbox_price_se's.  No apply-only
+//                  mode: a weight readback launches k_pbox_price_se.
+//   k_pbox_update1 unchanged, on the steepest-edge pricing grid (it merges on
+//                  (key, column) only).
+//   k_pbox_step_se1  k_pbox_step1's decisions and commit (classification, ninf,
+//                  y_stale, the counters) with k_pbox_step_se's extras on a
+//                  pivot: gamma_p in the same fixed order, gamma_leave, the
+//                  record with its own rho, pend and need_tau.  pend is cleared
+//                  by a flip, ST_INFEASIBLE, ST_BREAKDOWN, ST_UNBOUNDED and an
+//                  optimum; a pass cut off by the limit leaves it.
+//   k_pbox_tau + k_pbox_tau_sum   unchanged.
+// With ninf == 0 and y current the two kernels do the arithmetic of
+// k_pbox_price_se and k_pbox_step_se, so a batch enqueued in phase 1 runs on
+// through the switch; the host returns to §7h's four-step pass afterwards.
+hipError_t pbox_se1_prepare(const Params& P, const PboxSeCfg& c);  // the LDS sizes of the staged instantiations
+hipError_t launch_pbox_price_se1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
+                                 const PboxSeCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+hipError_t launch_pbox_step_se1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
+                                hipStream_t s);
 
 // Exact weights of a warm basis (spx_pbox_wexact.hip): gamma_j =
 // 1 + ||B^-1 A_j||^2 for every column on nb_list, from W.S = the true B^-1 of the

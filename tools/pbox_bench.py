@@ -96,6 +96,23 @@ the bounded primal loop of a context that never ranges follows (role pbox, twice
 alternating with --parent-root (a built checkout of the parent commit: its package
 and its libsimplex.so) when one is given.
 
+--phase1 --primal-pricing steepest --phase1-pricing steepest measures steepest
+edge through phase 1 instead, one child per side, the sides
+alternating:
+  p1_dense      as above: the phase-1 Dantzig pass (k_pbox_vtb, k_pbox_price1, ...)
+  p1_se         the same LP with the three flags: the phase-1 steepest-edge pass
+                (k_pbox_vtb, k_pbox_price_se1, k_pbox_update1, k_pbox_step_se1,
+                k_pbox_tau); price_us is k_pbox_price_se1's, vtb_us the mean of the
+                k_pbox_vtb and the k_pbox_tau step (two event pairs per pass)
+  pbox_se       as above: the phase-2 steepest-edge pass (k_pbox_price_se) of a
+                context that never opted in; with --parent-lib also pbox_se_parent
+                and pbox_parent, the same two sides on a build of the parent commit
+  p1_dense_again, p1_se_again, pbox_se_again (, pbox_se_parent_again, pbox_parent_again)
+The pricing kernels are compared by algorithmic bandwidth (bytes_price / time):
+the sides stream different numbers of non-basic slack columns.  With --solve,
+whole solves of boxed_general at every --solve-shape from the slack basis,
+Dantzig phase 1 / steepest / Dantzig / steepest, each with the CPU certificate.
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
     python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
@@ -105,6 +122,8 @@ and its libsimplex.so) when one is given.
                                --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5 --kernel-shape 4096 16384 5
                                [--out profiles/pbox_wexact.json]
     python tools/pbox_bench.py --free --parent-lib PATH [--out profiles/pbox_lu_c3.json]
+    python tools/pbox_bench.py --phase1 --primal-pricing steepest --phase1-pricing steepest [--parent-lib PATH]
+                               [--solve --solve-shape 1024 4096 4] [--out profiles/pbox_p1se_c3.json]
     python tools/pbox_bench.py --ranging --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5
                                --kernel-shape 4096 16384 5 [--parent-root DIR] [--out profiles/ranging_c3.json]
 """
@@ -316,6 +335,9 @@ def measure_phase1(make_ctx, k, warm, chunk, want_phase2, warm2=0):
         if npass:
             L, m = info["ld"], info["m"]
             vtb_us, price_us, update_us = 1e3 * tv / nv, 1e3 * tp / npass, 1e3 * tu / npass
+            bytes_price = 0.5 * (info["bytes_price"] + ctx.info()["bytes_price"])
+            res.update({"bytes_price": bytes_price, "price_TBps": round(bytes_price / (price_us * 1e-6) / 1e12, 3),
+                        "vtb_pairs_per_pass": round(nv / npass, 3)})
             rows = 0.5 * (n0 + ph[3])
             bytes_vtb = 8.0 * L * rows
             bytes_dense = 8.0 * L * m
@@ -357,6 +379,75 @@ def run_p1_dense(a):
     del A
     return measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
                                                      primal_phase1=True, timing=timing), a.k, a.warm, a.k, False)
+
+
+def run_p1_se(a):
+    """p1_dense's LP with steepest edge through phase 1."""
+    import numpy as np
+
+    import primal_phase1_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = primal_phase1_ref.boxed_general(a.m, a.n, a.seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    S = spx.PRIMAL_PRICING_STEEPEST
+    return measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                                                     primal_phase1=True, primal_pricing=S, primal_phase1_pricing=S,
+                                                     timing=timing), a.k, a.warm, a.k, False)
+
+
+def _parent_bindings():
+    """A build of the parent commit (SPX_LIB) lacks the entry point this package binds since."""
+    from simplex_method_gpu_amd import _lib
+
+    _lib.SIGNATURES.pop("spx_set_primal_phase_one_pricing")
+
+
+def run_pbox_se_parent(a):
+    _parent_bindings()
+    return run_pbox_se(a)
+
+
+def run_pbox_parent(a):
+    _parent_bindings()
+    return run_pbox(a)
+
+
+def run_solve_p1(a):
+    """Whole solves of boxed_general from the slack basis through phase 1, under
+    Dantzig or under steepest edge in both phases."""
+    import numpy as np
+
+    import primal_phase1_ref
+    import simplex_method_gpu_amd as spx
+
+    out = []
+    steep = a.primal_pricing == "steepest"
+    rule = spx.PRIMAL_PRICING_STEEPEST if steep else spx.PRIMAL_PRICING_DANTZIG
+    for (m, n, seed) in [tuple(s) for s in a.solve_shape]:
+        A, b, c, u = primal_phase1_ref.boxed_general(m, n, seed)
+        with spx.Context(np.ascontiguousarray(A.T), b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                         refactor_every=a.refactor, primal_phase1=True, primal_pricing=rule,
+                         primal_phase1_pricing=rule) as ctx:
+            ctx.iterate(20)  # (first-launch costs)
+            ctx.reset()
+            t0 = time.perf_counter()
+            r = ctx.solve()
+            dt = time.perf_counter() - t0
+            x, up = ctx.primal()
+            fl = ctx.primal_flips()
+            ph = ctx.primal_phase1()
+        rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "primal_pricing": a.primal_pricing,
+               "phase1_pricing": a.primal_pricing, "status": int(r.status), "pivots": r.pivots, "z": r.z,
+               "seconds": round(dt, 4), "it_per_s": round(r.pivots / dt, 1), "flip_passes": fl[0], "to_upper": fl[1],
+               "phase1_passes": ph[0], "phase1_pivots": ph[1], "phase1_rows": ph[2]}
+        if int(r.status) == 1:
+            viol, dviol, zc = primal_phase1_ref.certificate(A, b, c, u, r.b_ixs, up)
+            rec.update({"cert_bound_violation": viol, "cert_dual_violation": dviol,
+                        "cert_z_rel": abs(zc - r.z) / abs(zc), "cert_ok": bool(viol <= 1e-9 and dviol <= 1e-7)})
+        out.append(rec)
+    return out
 
 
 def run_p1_free(a):
@@ -651,6 +742,8 @@ def main():
     ap.add_argument("--sparse-chunk", type=int, default=10, help="p1_sparse: pivots per timed chunk")
     ap.add_argument("--primal-pricing", default="dantzig", choices=["dantzig", "steepest"],
                     help="steepest: the steepest-edge sides against the Dantzig loop instead (DESIGN.md 7h)")
+    ap.add_argument("--phase1-pricing", default="dantzig", choices=["dantzig", "steepest"],
+                    help="with --phase1 --primal-pricing steepest: steepest edge through phase 1 (DESIGN.md 7l)")
     ap.add_argument("--warm-resolve", action="store_true",
                     help="the exact weight start of a warm basis instead (DESIGN.md 7i)")
     ap.add_argument("--kernel-shape", type=int, nargs=3, action="append", default=[], metavar=("M", "N", "SEED"),
@@ -659,7 +752,8 @@ def main():
     ap.add_argument("--parent-lib", default=None, help="with --free: libsimplex.so built from the parent commit")
     ap.add_argument("--role", default=None,
                     choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se",
-                             "warm_resolve", "wexact_kernel", "p1_free", "p1_parent", "ranging_kernel"])
+                             "warm_resolve", "wexact_kernel", "p1_free", "p1_parent", "ranging_kernel", "p1_se",
+                             "pbox_se_parent", "pbox_parent", "solve_p1"])
     ap.add_argument("--parent-root", default=None,
                     help="with --ranging: a built checkout of the parent commit (its package and its libsimplex.so)")
     ap.add_argument("--ranging", action="store_true",
@@ -669,7 +763,9 @@ def main():
         run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
                "pbox_flag": run_pbox_flag, "p1_dense": run_p1_dense, "p1_sparse": run_p1_sparse,
                "pbox_se": run_pbox_se, "warm_resolve": run_warm_resolve, "wexact_kernel": run_wexact_kernel,
-               "p1_free": run_p1_free, "p1_parent": run_p1_parent, "ranging_kernel": run_ranging_kernel}[a.role]
+               "p1_free": run_p1_free, "p1_parent": run_p1_parent, "ranging_kernel": run_ranging_kernel,
+               "p1_se": run_p1_se, "pbox_se_parent": run_pbox_se_parent, "pbox_parent": run_pbox_parent,
+               "solve_p1": run_solve_p1}[a.role]
         print(json.dumps(run(a)), flush=True)
         return
     if a.ranging:
@@ -718,6 +814,52 @@ def main():
     if a.k < 252:
         ap.error("--k: at least 252 timed pivots")
     res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "seed": a.seed}
+    if a.phase1 and a.primal_pricing == "steepest":
+        if a.phase1_pricing != "steepest":
+            ap.error("--phase1 --primal-pricing steepest needs --phase1-pricing steepest (the library refuses it otherwise)")
+        if a.parent_lib and not os.path.exists(a.parent_lib):
+            ap.error("--parent-lib: no such file")
+        sides = [("p1_dense", "p1_dense"), ("p1_se", "p1_se"), ("pbox_se", "pbox_se")]
+        if a.parent_lib:
+            sides += [("pbox_se_parent", "pbox_se_parent"), ("pbox", "pbox"), ("pbox_parent", "pbox_parent")]
+        for again in ("", "_again"):
+            for key, role in sides:
+                res[key + again] = child(a, role, "steepest" if "se" in role else "dantzig",
+                                         lib=a.parent_lib if role.endswith("_parent") else None)
+                sys.stderr.write(f"{key + again}: {json.dumps(res[key + again])}\n")
+                sys.stderr.flush()
+        d, q, w = res["p1_dense"], res["p1_se"], res["pbox_se"]
+        res["p1_se_over_p1_dense"] = {k: round(q[k] / d[k], 3) for k in ("passes_per_s", "price_us", "update_us")}
+        res["p1_se_over_pbox_se"] = {"pass_rate": round(q["passes_per_s"] / w["it_per_s"], 3),
+                                     "price_TBps": round(q["price_TBps"] / w["price_TBps"], 4),
+                                     "price_TBps_again": round(res["p1_se_again"]["price_TBps"]
+                                                               / res["pbox_se_again"]["price_TBps"], 4)}
+        res["again_over_first"] = {k: round(res[k + "_again"][f] / res[k][f], 4)
+                                   for k, f in (("p1_dense", "passes_per_s"), ("p1_se", "passes_per_s"),
+                                                ("pbox_se", "it_per_s"))}
+        if a.parent_lib:
+            res["this_over_parent_it_per_s"] = {f"{k}{ag}": round(res[k + ag]["it_per_s"] / res[k + "_parent" + ag]["it_per_s"], 4)
+                                                for k in ("pbox_se", "pbox") for ag in ("", "_again")}
+            res["parent_again_over_parent_it_per_s"] = {k: round(res[k + "_parent_again"]["it_per_s"]
+                                                                 / res[k + "_parent"]["it_per_s"], 4) for k in ("pbox_se", "pbox")}
+        if a.solve and a.solve_shape:
+            runs = [child(a, "solve_p1", rule) for rule in ("dantzig", "steepest", "dantzig", "steepest")]
+            res["solve"] = []
+            for i in range(len(a.solve_shape)):
+                dz, se = runs[0][i], runs[1][i]
+                res["solve"].append({"dantzig": dz, "steepest": se, "dantzig_again": runs[2][i],
+                                     "steepest_again": runs[3][i],
+                                     "pivot_ratio": round(dz["pivots"] / se["pivots"], 2),
+                                     "time_ratio": round(dz["seconds"] / se["seconds"], 2),
+                                     "accepted": bool(all(runs[j + 1][i]["pivots"] < runs[j][i]["pivots"]
+                                                          and runs[j + 1][i]["seconds"] < runs[j][i]["seconds"]
+                                                          for j in (0, 2))
+                                                      and all(r[i].get("cert_ok") for r in runs))})
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
     if a.primal_pricing == "steepest":
         for key, role, lds in (("pbox", "pbox", None), ("pbox_se", "pbox_se", None), ("pbox_se_lds1", "pbox_se", 1),
                                ("pbox_se_lds0", "pbox_se", 0), ("pbox_again", "pbox", None),
