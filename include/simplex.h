@@ -182,8 +182,9 @@ typedef struct spx_opts {
  *         spx_pivot / spx_group_iterate: SPX_ERR_STATE).  The entering rule is
  *         SPX_PRIMAL_PRICING_* (below: Dantzig, or exact steepest edge); no
  *         Devex.  Finite lower bounds of any sign run shifted and free columns
- *         run under Dantzig pricing (spx_set_bounds_lu below); no
- *         upper-only columns.  SPX_ALGO_PRIMAL itself still refuses finite
+ *         run under Dantzig pricing (spx_set_bounds_lu below), or
+ *         under steepest edge where spx_set_primal_free_pricing says so
+ *         (DESIGN.md §7m); no upper-only columns.  SPX_ALGO_PRIMAL itself still refuses finite
  *         bounds.
  *         Phase 1 (opt-in: SPX_FLAG_PRIMAL_PHASE1, spx_set_primal_phase1;
  *         DESIGN.md §7f).  With it the entry check refuses nothing: row i is
@@ -209,8 +210,7 @@ typedef struct spx_opts {
  *         Dantzig's rule, or with the steepest-edge weights where the loop's
  *         rule is steepest edge and spx_set_primal_phase_one_pricing says so
  *         (below).  Still out: a long-step phase 1, phase 1 under
- *         SPX_ALGO_PRIMAL, a rule that differs between the phases, free columns
- *         under steepest edge. */
+ *         SPX_ALGO_PRIMAL, a rule that differs between the phases. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
 #define SPX_ALGO_PRIMAL_BOX 2
@@ -442,6 +442,17 @@ typedef struct spx_opts {
                                          and inert without the other two and under the
                                          other algorithms                             */
 
+#define SPX_FLAG_PRIMAL_FREE_STEEPEST 131072 /* the bounded primal loop prices free columns
+                                         (spx_set_bounds_lu) with the steepest-edge
+                                         weights where the loop's rule is
+                                         SPX_PRIMAL_PRICING_STEEPEST
+                                         (spx_set_primal_free_pricing; default DANTZIG,
+                                         under which free columns with steepest edge
+                                         stay refused); accepted and inert on a context
+                                         without free columns, under
+                                         SPX_PRIMAL_PRICING_DANTZIG and under the other
+                                         algorithms                                   */
+
 #define SPX_FLAG_PRIMAL_EXACT_WEIGHTS 32768 /* the bounded primal loop restarts its
                                          steepest-edge weights for a warm basis at
                                          the exact norms (SPX_PRIMAL_WEIGHTS_EXACT;
@@ -613,6 +624,22 @@ int spx_set_primal_pricing(spx_ctx* ctx, int32_t rule);
  * digit out: the bindings' header scan reads [a-z_] names.) */
 int spx_set_primal_phase_one_pricing(spx_ctx* ctx, int32_t rule);
 
+/* Entering rule of the bounded primal loop on a context that holds free columns
+ * (spx_set_bounds_lu with -inf, +inf) where the loop's rule is steepest edge:
+ * SPX_PRIMAL_PRICING_DANTZIG (the default: free columns and steepest edge stay
+ * refused together) or SPX_PRIMAL_PRICING_STEEPEST
+ * (SPX_FLAG_PRIMAL_FREE_STEEPEST at spx_create).  Between any two
+ * calls and under any algorithm.  Consulted only where the context holds a free
+ * column and the loop's rule is STEEPEST; otherwise accepted and inert.  With it
+ * at STEEPEST, spx_set_bounds_lu with free columns under steepest edge and
+ * spx_set_primal_pricing(STEEPEST) on a context that holds free columns are
+ * accepted (with phase 1 on, spx_set_primal_phase_one_pricing(STEEPEST) is still
+ * required).  It restarts no weights.  SPX_ERR_ARG for NULL or an unknown rule;
+ * SPX_ERR_STATE for DANTZIG while the context holds a free column and the loop's
+ * rule is STEEPEST (the call would re-create the refused state: set
+ * SPX_PRIMAL_PRICING_DANTZIG with spx_set_primal_pricing first). */
+int spx_set_primal_free_pricing(spx_ctx* ctx, int32_t rule);
+
 /* Steepest-edge weights w[0..n) of the current basis, by column: the non-basic
  * entries are live (1 + ||B^-1 A_j||^2 as the recurrence keeps it, a pending
  * update applied first), a basic column's entry is unspecified.  SPX_ERR_STATE
@@ -699,9 +726,10 @@ int spx_get_bounds(spx_ctx* ctx, double* ub /* n */);
  *            (ub[j] - lb[j]) A_j; both bounded loops, every pricing rule, phase 1
  *            and the long-step ratio test run unchanged on the shifted problem.
  *   free     lb[j] = -inf and ub[j] = +inf: SPX_ALGO_PRIMAL_BOX with
- *            SPX_PRIMAL_PRICING_DANTZIG only.  A non-basic free column sits at 0
- *            and is a candidate when |d_j| > eps (key -|d_j|; it moves up when
- *            d_j < 0, down otherwise); it never flips; a row whose basic column
+ *            SPX_PRIMAL_PRICING_DANTZIG, or with SPX_PRIMAL_PRICING_STEEPEST after
+ *            spx_set_primal_free_pricing(STEEPEST).  A non-basic free column sits
+ *            at 0 and is a candidate when |d_j| > eps (key -|d_j|, under steepest
+ *            edge -d_j^2 / gamma_j; it moves up when d_j < 0, down otherwise); it never flips; a row whose basic column
  *            is free never blocks, is never out of its bounds and never leaves.
  * Every readback is in the caller's variables: spx_get_primal gives lb[j] or
  * ub[j] exactly for a non-basic column, spx_get_state's x_b includes the basic
@@ -715,7 +743,8 @@ int spx_get_bounds(spx_ctx* ctx, double* ub /* n */);
  * holding one is refused in the same way: a non-basic free column has no dual
  * feasible side unless d_j = 0) or whose entering rule is
  * SPX_PRIMAL_PRICING_STEEPEST (spx_set_primal_pricing refuses that rule on a
- * context holding one).  A refused call changes nothing.  With lb NULL or all 0
+ * context holding one) unless spx_set_primal_free_pricing chose STEEPEST.  A
+ * refused call changes nothing.  With lb NULL or all 0
  * the call is spx_set_bounds(ctx, ub): the same kernels and the same bits.
  * spx_set_bounds(ctx, ub) on a context that had lower bounds clears them;
  * spx_get_bounds returns the caller's ub. */

@@ -72,6 +72,10 @@ PRIMAL_WEIGHTS_REFERENCE, PRIMAL_WEIGHTS_EXACT = 0, 1
 FLAG_PRIMAL_EXACT_WEIGHTS = 32768  # the steepest-edge weights of a warm basis restart at the exact norms
 # phase 1 prices with the steepest-edge weights where the loop's rule is steepest edge (default: the two are refused)
 FLAG_PRIMAL_PHASE1_STEEPEST = 65536
+# free columns price with the steepest-edge weights where the loop's rule is steepest edge (default: the two are
+# refused).  Context(primal_free_pricing=...) is the interface; the bit itself (SPX_FLAG_PRIMAL_FREE_STEEPEST) stays
+# module-private, the public FLAG_* names end at FLAG_PRIMAL_PHASE1_STEEPEST.
+_FLAG_PRIMAL_FREE_STEEPEST = 131072
 
 
 class SolveStatus(IntEnum):
@@ -206,7 +210,8 @@ class Context:
                  dual_ratio: int = DUAL_RATIO_TEXTBOOK, primal_phase1: bool = False,
                  primal_pricing: int = PRIMAL_PRICING_DANTZIG,
                  primal_weights: int = PRIMAL_WEIGHTS_REFERENCE, lower=None,
-                 primal_phase1_pricing: int = PRIMAL_PRICING_DANTZIG):
+                 primal_phase1_pricing: int = PRIMAL_PRICING_DANTZIG,
+                 primal_free_pricing: int = PRIMAL_PRICING_DANTZIG):
         L = load()
         o = SpxOpts()
         L.spx_default_opts(ctypes.byref(o))
@@ -235,6 +240,9 @@ class Context:
         if primal_phase1_pricing not in (PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST):
             raise ValueError("primal_phase1_pricing must be PRIMAL_PRICING_DANTZIG or PRIMAL_PRICING_STEEPEST")
         self._primal_phase1_pricing = primal_phase1_pricing
+        if primal_free_pricing not in (PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST):
+            raise ValueError("primal_free_pricing must be PRIMAL_PRICING_DANTZIG or PRIMAL_PRICING_STEEPEST")
+        self._primal_free_pricing = primal_free_pricing
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
@@ -246,7 +254,8 @@ class Context:
                    | (FLAG_PRIMAL_PHASE1 if primal_phase1 else 0)
                    | (FLAG_PRIMAL_STEEPEST if primal_pricing == PRIMAL_PRICING_STEEPEST else 0)
                    | (FLAG_PRIMAL_EXACT_WEIGHTS if primal_weights == PRIMAL_WEIGHTS_EXACT else 0)
-                   | (FLAG_PRIMAL_PHASE1_STEEPEST if primal_phase1_pricing == PRIMAL_PRICING_STEEPEST else 0))
+                   | (FLAG_PRIMAL_PHASE1_STEEPEST if primal_phase1_pricing == PRIMAL_PRICING_STEEPEST else 0)
+                   | (_FLAG_PRIMAL_FREE_STEEPEST if primal_free_pricing == PRIMAL_PRICING_STEEPEST else 0))
         h = ctypes.c_void_p()
         if A_cols is not None:
             A_cols = np.ascontiguousarray(A_cols, dtype=np.float64)
@@ -426,6 +435,16 @@ class Context:
         Inert unless phase 1 is on and the rule is steepest edge."""
         check(self._L.spx_set_primal_phase_one_pricing(self._h, rule))
         self._primal_phase1_pricing = rule
+
+    def set_primal_free_pricing(self, rule: int):
+        """Entering rule on a context that holds free columns where the loop's
+        rule is steepest edge (spx_set_primal_free_pricing):
+        PRIMAL_PRICING_DANTZIG (the default: free columns and steepest edge are
+        refused together) or PRIMAL_PRICING_STEEPEST (a free column is keyed
+        with its weight like every other candidate).  Inert unless the context
+        holds a free column and the rule is steepest edge."""
+        check(self._L.spx_set_primal_free_pricing(self._h, rule))
+        self._primal_free_pricing = rule
 
     def primal_weights(self):
         """Steepest-edge weights of the bounded primal loop by column, n entries
@@ -743,6 +762,7 @@ class Context:
         cfg["dual_ratio"] = self._dual_ratio
         cfg["primal_weights"] = self._primal_weights
         cfg["primal_phase1_pricing"] = self._primal_phase1_pricing
+        cfg["primal_free_pricing"] = self._primal_free_pricing
         return cfg
 
     def loop_layout(self):

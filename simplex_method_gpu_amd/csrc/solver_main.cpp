@@ -54,6 +54,13 @@
 //                  candidates with the steepest-edge weights);
 //                  inert without --phase1 or under --primal-pricing dantzig;
 //                  without --primal-box it is refused by name (exit 1)
+//   --free-pricing R  entering rule of --primal-box where --lower holds a free
+//                  column under --primal-pricing steepest: dantzig (default: the
+//                  library's refusal is printed, exit 1) | steepest
+//                  (SPX_FLAG_PRIMAL_FREE_STEEPEST: a free column is keyed with its
+//                  steepest-edge weight); inert without a free
+//                  column or under --primal-pricing dantzig; without --primal-box
+//                  it is refused by name (exit 1)
 //   --primal-weights W  how the steepest-edge weights of --primal-box restart
 //                  for a warm basis: reference (default) | exact
 //                  (SPX_FLAG_PRIMAL_EXACT_WEIGHTS); shown in --json.  The CLI
@@ -67,7 +74,7 @@
 //   --lower F      lower bounds l_j <= x_j of all n columns for --dual or
 //                  --primal-box (spx_set_bounds_lu), with or without --bounds: F
 //                  in --bounds' format, "-inf" = a free column (--primal-box with
-//                  Dantzig pricing); z and x are in the caller's variables;
+//                  Dantzig pricing, or steepest edge with --free-pricing steepest); z and x are in the caller's variables;
 //                  without --dual or --primal-box it is refused by name (exit 1)
 //   --ranging PREFIX  after a --dual or --primal-box solve that ends at the
 //                  optimum: sensitivity ranging (spx_ranging_cost / _rhs, DESIGN.md
@@ -120,7 +127,7 @@ static void print_elapsed_time(const char* msg, double dur) {
 static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
-                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--phase1-pricing dantzig|steepest] [--primal-weights reference|exact]]"
+                 " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--phase1-pricing dantzig|steepest] [--free-pricing dantzig|steepest] [--primal-weights reference|exact]]"
                  " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F] [--ranging PREFIX]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
@@ -144,6 +151,7 @@ int main(int argc, char* argv[]) {
     bool primal_pricing_given = false, primal_steepest = false;
     bool primal_weights_given = false, primal_exact = false;
     bool phase1_pricing_given = false, phase1_steepest = false;
+    bool free_pricing_given = false, free_steepest = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto need = [&](int k) {
@@ -206,6 +214,16 @@ int main(int argc, char* argv[]) {
             phase1_pricing_given = true;
             phase1_steepest = r == "steepest";
         }
+        else if (s == "--free-pricing") {
+            need(1);
+            const std::string r = argv[++a];
+            if (r != "dantzig" && r != "steepest") {
+                std::cerr << "--free-pricing " << r << ": dantzig or steepest\n";
+                return 1;
+            }
+            free_pricing_given = true;
+            free_steepest = r == "steepest";
+        }
         else if (s == "--primal-weights") {
             need(1);
             const std::string r = argv[++a];
@@ -265,6 +283,10 @@ int main(int argc, char* argv[]) {
     }
     if (phase1_pricing_given && !primal_box) {
         std::cerr << "--phase1-pricing needs --primal-box: it is the rule of the bounded primal loop's phase 1\n";
+        return 1;
+    }
+    if (free_pricing_given && !primal_box) {
+        std::cerr << "--free-pricing needs --primal-box: it is the bounded primal loop's rule with free columns\n";
         return 1;
     }
     if (primal_weights_given && !primal_box) {
@@ -335,6 +357,7 @@ int main(int argc, char* argv[]) {
     if (primal_steepest) o.flags |= SPX_FLAG_PRIMAL_STEEPEST;
     if (primal_exact) o.flags |= SPX_FLAG_PRIMAL_EXACT_WEIGHTS;
     if (phase1_steepest) o.flags |= SPX_FLAG_PRIMAL_PHASE1_STEEPEST;
+    if (free_steepest) o.flags |= SPX_FLAG_PRIMAL_FREE_STEEPEST;
     spx_ctx* ctx = nullptr;
     const TimePoint t_alloc = Clock::now();
     int rc = device_gen ? spx_create_generated(&ctx, m, n, gseed, &o)

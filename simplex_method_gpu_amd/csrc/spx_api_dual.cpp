@@ -544,7 +544,7 @@ int spx_set_bounds_lu(spx_ctx* x, const double* lb, const double* ub) {
     if (nfree > 0 && !pbox)
         return fail(SPX_ERR_STATE, "the dual simplex loop does not run free columns (%lld of them): a non-basic free "
                     "column has no dual feasible side unless d_j = 0; SPX_ALGO_PRIMAL_BOX runs them", (long long)nfree);
-    if (nfree > 0 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+    if (nfree > 0 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.frrule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_STATE, "free columns (%lld of them) do not run with steepest-edge pricing "
                     "(spx_set_primal_pricing); set SPX_PRIMAL_PRICING_DANTZIG first", (long long)nfree);
     SPX_TRY(dual_setup(x));

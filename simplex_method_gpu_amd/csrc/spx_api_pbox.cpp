@@ -230,13 +230,15 @@ int vtb_events(spx_ctx* x, hipEvent_t* v0, hipEvent_t* v1) {
 // Steepest edge through phase 1 (opt-in): while the host last saw
 // ninf > 0 or y stale the pass is vtb -> price_se1 -> update1 -> step_se1 -> tau;
 // the same readback brings §7h's four-step pass back, with the weights it finds.
+// Steepest edge with free columns (opt-in): every pass is [vtb ->]
+// price_se_f -> update_f -> step_se_f -> tau, vtb under the same host condition.
 int iterate_pbox(spx_ctx* x, int64_t k) {
     SPX_TRY(pbox_setup(x));
     if (!x->pbox.checked) SPX_TRY(pbox_check_entry(x));
     PboxState& s = x->pbox;
     const bool steep = s.rule == SPX_PRIMAL_PRICING_STEEPEST;
     const bool fr = x->dual.nfree > 0;  // free columns: every pass on the *_f kernels
-    if (fr && steep)  // (both setters refuse the combination)
+    if (fr && steep && s.frrule != SPX_PRIMAL_PRICING_STEEPEST)  // (both setters refuse the combination)
         return fail(SPX_ERR_STATE, "free columns do not run with steepest-edge pricing");
     PboxArgs se_args = s.args;
     if (steep) {
@@ -246,6 +248,10 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
         if (s.phase1 && !s.se1_ready) {
             HIP_TRY(pbox_se1_prepare(x->P, s.secfg));
             s.se1_ready = true;
+        }
+        if (fr && !s.sef_ready) {
+            HIP_TRY(pbox_se_f_prepare(x->P, s.secfg));
+            s.sef_ready = true;
         }
         SPX_TRY(pbox_se_restart(x));
         se_args.price_grid = s.secfg.price_grid;  // k_pbox_update / k_pbox_update1 merges this pass's partials
@@ -259,6 +265,23 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
         for (int64_t i = 0; i < round; ++i) {
             hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
             if (x->timing) SPX_TRY(pass_events(x, &p0, &p1, &u0, &u1));
+            if (steep && fr) {
+                // [vtb ->] price_se_f -> update_f -> step_se_f -> tau: the phase is the device's
+                hipEvent_t v0 = nullptr, v1 = nullptr, t0 = nullptr, t1 = nullptr;
+                if (s.phase1 && (s.ninf > 0 || s.y_stale)) {
+                    s.y_dirty = true;
+                    if (x->timing) SPX_TRY(vtb_events(x, &v0, &v1));
+                    HIP_TRY(launch_pbox_vtb(x->P, s.p1, s.cfg, x->stream, v0, v1));
+                }
+                if (x->timing) SPX_TRY(vtb_events(x, &t0, &t1));
+                HIP_TRY(launch_pbox_price_se_f(x->P, se_args, s.p1, s.se, s.fr, s.secfg, x->stream, p0, p1));
+                if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
+                HIP_TRY(launch_pbox_update_f(x->P, se_args, s.p1, s.fr, s.cfg, x->stream, u0, u1));
+                HIP_TRY(launch_pbox_step_se_f(x->P, se_args, s.p1, s.se, s.fr, x->stream));
+                HIP_TRY(launch_pbox_tau(x->P, s.se, s.cfg, x->stream, t0, t1));
+                ++x->n_eager;
+                continue;
+            }
             if (steep && s.phase1 && (s.ninf > 0 || s.y_stale)) {
                 // vtb -> price_se1 -> update1 -> step_se1 -> tau: the phase is the device's
                 s.y_dirty = true;
@@ -363,6 +386,7 @@ int pbox_on_create(spx_ctx* x) {
     x->pbox.rule = (x->opts.flags & SPX_FLAG_PRIMAL_STEEPEST) ? SPX_PRIMAL_PRICING_STEEPEST : SPX_PRIMAL_PRICING_DANTZIG;
     x->pbox.winit = (x->opts.flags & SPX_FLAG_PRIMAL_EXACT_WEIGHTS) ? SPX_PRIMAL_WEIGHTS_EXACT : SPX_PRIMAL_WEIGHTS_REFERENCE;
     x->pbox.p1rule = (x->opts.flags & SPX_FLAG_PRIMAL_PHASE1_STEEPEST) ? SPX_PRIMAL_PRICING_STEEPEST : SPX_PRIMAL_PRICING_DANTZIG;
+    x->pbox.frrule = (x->opts.flags & SPX_FLAG_PRIMAL_FREE_STEEPEST) ? SPX_PRIMAL_PRICING_STEEPEST : SPX_PRIMAL_PRICING_DANTZIG;
     if (x->pbox.phase1 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.p1rule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_ARG, "SPX_FLAG_PRIMAL_STEEPEST with SPX_FLAG_PRIMAL_PHASE1: steepest-edge pricing does not "
                     "run during the bounded primal loop's phase 1");
@@ -437,7 +461,7 @@ int spx_set_primal_pricing(spx_ctx* x, int32_t rule) {
     if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->pbox.phase1 && x->pbox.p1rule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_STATE, "spx_set_primal_pricing: steepest-edge pricing does not run with the bounded primal "
                     "loop's phase 1 (spx_set_primal_phase1); switch phase 1 off first");
-    if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->dual.nfree > 0)
+    if (rule == SPX_PRIMAL_PRICING_STEEPEST && x->dual.nfree > 0 && x->pbox.frrule != SPX_PRIMAL_PRICING_STEEPEST)
         return fail(SPX_ERR_STATE, "spx_set_primal_pricing: steepest-edge pricing does not run with free columns (%lld of "
                     "them, spx_set_bounds_lu)", (long long)x->dual.nfree);
     if (rule != x->pbox.rule) x->pbox.se_stale = true;  // a change of rule restarts the weights
@@ -454,6 +478,18 @@ int spx_set_primal_phase_one_pricing(spx_ctx* x, int32_t rule) {
                     "with steepest-edge pricing (spx_set_primal_pricing) while phase 1 is on (spx_set_primal_phase1); "
                     "switch phase 1 off or set SPX_PRIMAL_PRICING_DANTZIG first");
     x->pbox.p1rule = rule;  // (the weights do not depend on the phase: nothing restarts)
+    return SPX_OK;
+}
+
+int spx_set_primal_free_pricing(spx_ctx* x, int32_t rule) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (rule != SPX_PRIMAL_PRICING_DANTZIG && rule != SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_ARG, "bad primal free-column pricing rule %d", rule);
+    if (rule == SPX_PRIMAL_PRICING_DANTZIG && x->dual.nfree > 0 && x->pbox.rule == SPX_PRIMAL_PRICING_STEEPEST)
+        return fail(SPX_ERR_STATE, "spx_set_primal_free_pricing: SPX_PRIMAL_PRICING_DANTZIG with free columns (%lld of "
+                    "them, spx_set_bounds_lu) does not run with steepest-edge pricing (spx_set_primal_pricing); set "
+                    "SPX_PRIMAL_PRICING_DANTZIG there first", (long long)x->dual.nfree);
+    x->pbox.frrule = rule;  // (the weights do not depend on the bounds: nothing restarts)
     return SPX_OK;
 }
 

@@ -154,6 +154,11 @@ struct PboxState {
     // STEEPEST: that state exists only with p1rule == STEEPEST (create and the three setters refuse it otherwise)
     int32_t p1rule = SPX_PRIMAL_PRICING_DANTZIG;
     bool se1_ready = false;  // pbox_se1_prepare ran
+    // the rule with free columns (spx_set_primal_free_pricing), consulted only while DualState::nfree > 0
+    // && rule == STEEPEST: that state exists only with frrule == STEEPEST (spx_set_bounds_lu and the two setters
+    // refuse it otherwise).  Then every pass runs k_pbox_price_se_f / k_pbox_update_f / k_pbox_step_se_f.
+    int32_t frrule = SPX_PRIMAL_PRICING_DANTZIG;
+    bool sef_ready = false;  // pbox_se_f_prepare ran
     spx::PboxSeArgs se{};
     spx::PboxSeCfg secfg{};
     bool se_stale = true;
@@ -168,8 +173,9 @@ struct PboxState {
     // (is_free and lb_B, allocated by the first entry check of a context with
     // DualState::nfree > 0; any other context allocates and launches none of it).
     // The entry check uploads both from DualState::lb and the basis; between
-    // entry checks k_pbox_step_f keeps lb_B.  While nfree > 0 every pass runs the
-    // *_f kernels, the rule is Dantzig, and with phase1 off the device's ninf is 0.
+    // entry checks k_pbox_step_f / k_pbox_step_se_f keeps lb_B.  While nfree > 0 every
+    // pass runs the *_f kernels (the rule is Dantzig) or the *_se_f ones (steepest
+    // edge with frrule == STEEPEST), and with phase1 off the device's ninf is 0.
     spx::PboxFreeArgs fr{};
     int8_t* fr_flags = nullptr;  // n (fr.is_free)
 };

@@ -1,7 +1,8 @@
 // spx_pbox.h — the bounded primal simplex loop's kernels (spx_pbox.hip): 0 <= x
 // <= u, one rank, explicit B^-1 (Params::win == 0, in-place storage), Dantzig
 // entering column, or exact steepest edge (the *_se kernels at the end of this
-// file; through phase 1 with the *_se1 kernels, §7l).  DESIGN.md §7e.
+// file; through phase 1 with the *_se1 kernels, §7l; with free
+// columns with the *_se_f kernels, §7m).  DESIGN.md §7e.
 //
 // A pass at iteration it is three launches on the context's stream; the kernel
 // boundaries are the only ordering between them:
@@ -295,6 +296,33 @@ hipError_t launch_pbox_price_se1(const Params& P, const PboxArgs& D, const Pbox1
                                  const PboxSeCfg& c, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_pbox_step_se1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
                                 hipStream_t s);
+
+// Steepest edge with free columns (opt-in, spx_set_primal_free_pricing).
+// gamma_j depends on the basis alone and the recurrence reads no bound, so §7j's
+// free rule changes only who is a candidate.  A pass enqueued while the host
+// last saw ninf > 0 or y stale is vtb -> price_se_f -> update_f -> step_se_f ->
+// tau, else the same without vtb; ordered by kernel boundaries only:
+//   k_pbox_price_se_f  k_pbox_price_se1 with is_free[j] read per column beside
+//                  at_upper[j], ahead of the column's stream: the candidate test
+//                  is k_pbox_price_f's ((fr ? -|d| : sigma d) < -eps), the key is
+//                  -d_j^2 / gamma_j.  The dots, the recurrence under the pending
+//                  word, the one owner's store of gamma_j, the skipped leaving
+//                  column, the slack shortcut, the per-lane order and the three
+//                  LDS layouts are k_pbox_price_se1's.  The phase word is 0 on a
+//                  context without phase 1: one kernel serves both.
+//   k_pbox_update_f  unchanged, on the steepest-edge pricing grid: it derives a
+//                  free entering column's sigma_p from the partial's d.
+//   k_pbox_step_se_f k_pbox_step_f's decisions and commit (lb_B[q], row_class_f,
+//                  ninf, y_stale, the counters; a free entering column never
+//                  flips) with k_pbox_step_se1's extras on a pivot and its
+//                  clearing of pend.  The leaving column is never free.
+//   k_pbox_tau + k_pbox_tau_sum   unchanged.
+hipError_t pbox_se_f_prepare(const Params& P, const PboxSeCfg& c);  // the LDS sizes of the staged instantiations
+hipError_t launch_pbox_price_se_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
+                                  const PboxFreeArgs& F, const PboxSeCfg& c, hipStream_t s, hipEvent_t e0,
+                                  hipEvent_t e1);
+hipError_t launch_pbox_step_se_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
+                                 const PboxFreeArgs& F, hipStream_t s);
 
 // Exact weights of a warm basis (spx_pbox_wexact.hip): gamma_j =
 // 1 + ||B^-1 A_j||^2 for every column on nb_list, from W.S = the true B^-1 of the

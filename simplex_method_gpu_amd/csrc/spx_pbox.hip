@@ -2218,6 +2218,320 @@ __global__ __launch_bounds__(1024) void k_pbox_step_se1(Params P, PboxArgs D, Pb
 }
 
 // ---------------------------------------------------------------------------
+// Steepest edge with free columns (spx_pbox.h)
+// ---------------------------------------------------------------------------
+// k_pbox_price_se1 with free columns: k_pbox_price_f's flag, read per column
+// beside at_upper ahead of the stream, decides who is a candidate (|d_j| > eps
+// for a free column); the dots, the recurrence, the weights' owner and the key
+// are k_pbox_price_se1's, operation for operation.  The phase word is 0 on a
+// context without phase 1, so one kernel serves both.
+template <int NL>
+__global__ __launch_bounds__(PBOX_BLOCK) void k_pbox_price_se_f(Params P, PboxArgs D, Pbox1Args X, PboxSeArgs E,
+                                                                PboxFreeArgs F) {
+    constexpr int WAVES = PBOX_WAVES;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    __shared__ PboxPartial s_red[WAVES];
+    const DevState* st = P.st;
+    const int32_t status = st->status;
+    const int32_t cnt = st->nb_count;
+    const int32_t y_buf = st->y_buf;
+    const int64_t iter = st->iter, limit = st->limit;
+    const bool ph1 = X.ph->ninf > 0;
+    const bool pend = E.se->pend != 0;
+    const int64_t leave = E.se->leave;
+    const double aq = E.se->aq, gp = E.se->gp;
+    if (status != ST_RUNNING || iter >= limit) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t L = P.L, L2 = L >> 1;
+    const int nch = (int)(L2 >> 6);
+    const dbl2* y_g = reinterpret_cast<const dbl2*>(ph1 ? X.yp : (y_buf ? P.y1 : P.y0));
+    const dbl2* r_g = reinterpret_cast<const dbl2*>(E.rho);
+    const dbl2* t_g = reinterpret_cast<const dbl2*>(E.tau);
+    if constexpr (NL >= 1) {
+        dbl2* d = reinterpret_cast<dbl2*>(dsm);
+        for (int64_t k = tid; k < L2; k += PBOX_BLOCK) d[k] = y_g[k];
+        if (NL == 3 && pend) {
+            for (int64_t k = tid; k < L2; k += PBOX_BLOCK) {
+                d[L2 + k] = r_g[k];
+                d[2 * L2 + k] = t_g[k];
+            }
+        }
+        __syncthreads();
+    }
+    const dbl2* yv = NL >= 1 ? reinterpret_cast<const dbl2*>(dsm) : y_g;
+    const dbl2* rv = NL == 3 ? reinterpret_cast<const dbl2*>(dsm) + L2 : r_g;
+    const dbl2* tv = NL == 3 ? reinterpret_cast<const dbl2*>(dsm) + 2 * L2 : t_g;
+    const double* ys = reinterpret_cast<const double*>(yv);
+    const double* rs = reinterpret_cast<const double*>(rv);
+    const double* ts = reinterpret_cast<const double*>(tv);
+
+    double bkey = INFINITY, bd = 0.0;
+    int64_t bidx = INT64_MAX;
+    const int nwv = (int)gridDim.x * WAVES;
+    for (int s = (int)blockIdx.x * WAVES + wave; s < cnt; s += nwv) {
+        const int64_t j = P.nb_list[s];
+        const int up = D.at_upper[j];
+        const int fr = F.is_free[j];
+        double gam = E.gamma[j];
+        const double cj = ph1 ? 0.0 : P.c[j];  // (x - 0.0 = x: exact)
+        double dy, dr = 0.0, dt = 0.0;
+        if (P.slack_unit && j >= P.ns) {  // A_j = e_k: no stream
+            dy = ys[j - P.ns];
+            if (pend) {
+                dr = rs[j - P.ns];
+                dt = ts[j - P.ns];
+            }
+        } else {
+            const dbl2* col = reinterpret_cast<const dbl2*>(P.A + j * L) + lane;
+            if (pend) se_dots<true>(col, nch, lane, yv, rv, tv, dy, dr, dt);
+            else se_dots<false>(col, nch, lane, yv, rv, tv, dy, dr, dt);
+        }
+        if (pend && j != leave) {  // Goldfarb and Reid; the commit wrote the leaving column's weight
+            const double g = dr / aq;
+            const double gn = fma(g * g, gp, fma(-2.0 * g, dt, gam));
+            const double fl = fma(g, g, 1.0);
+            gam = gn > fl ? gn : fl;
+            if (lane == 0) E.gamma[j] = gam;  // one owner per column
+        }
+        const double d = dy - cj;
+        const double sd = fr ? -fabs(d) : (up ? -d : d);  // free: either direction improves
+        const double key = -(d * d) / gam;
+        if (sd < -P.eps && argmin_better(key, j, bkey, bidx)) {
+            bkey = key;
+            bidx = j;
+            bd = d;
+        }
+    }
+    if (lane == 0) s_red[wave] = PboxPartial{bkey, bidx, bd, 0.0};
+    __syncthreads();
+    if (tid == 0) D.parts[blockIdx.x] = merge_price<WAVES>(s_red);  // read after the kernel boundary (k_pbox_update_f)
+}
+
+// k_pbox_step_f's decisions and commit with k_pbox_step_se1's bookkeeping: a
+// pivot of either phase records the weight update (gamma_p, gamma_leave, rho,
+// pend, need_tau); the leaving column is never free, so its weight needs no new
+// case.  pend is cleared as k_pbox_step_se1 clears it.
+__global__ __launch_bounds__(1024) void k_pbox_step_se_f(Params P, PboxArgs D, Pbox1Args X, PboxSeArgs E,
+                                                         PboxFreeArgs F) {
+    constexpr int BLOCK = 1024, WAVES = BLOCK / 64, CH = 4;
+    DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t m = P.m, L = P.L;
+    __shared__ PboxSnap S;
+    __shared__ ArgMinEntry s_red[WAVES];
+    __shared__ ArgMinEntry s_win;
+    __shared__ double s_up;
+    __shared__ int32_t s_at, s_fr;
+    __shared__ int32_t s_ninf, s_stale, s_cnt;
+    __shared__ double s_gp[WAVES];
+    if (tid == 0) {
+        S.it = st->iter;
+        S.limit = st->limit;
+        S.status = st->status;
+        S.y_buf = st->y_buf;
+        S.cnt = st->nb_count;
+        S.fresh = D.rec->fresh;
+        S.p = D.rec->p;
+        S.d_p = D.rec->d_p;
+        s_ninf = X.ph->ninf;
+        s_stale = X.ph->y_stale;
+        s_cnt = 0;
+    }
+    __syncthreads();
+    const int64_t it = S.it;
+    if (S.status != ST_RUNNING || it >= S.limit || !S.fresh) {
+        if (tid == 0) {
+            E.se->need_tau = 0;
+            // the pass that found the optimum, or no phase-1 candidate, applied the pending recurrence in its pricing
+            if (S.status == ST_OPTIMAL || S.status == ST_INFEASIBLE) E.se->pend = 0;
+        }
+        return;
+    }
+    const bool ph1 = s_ninf > 0;
+    const double ftol = X.feas_tol;
+
+    double bv = INFINITY;
+    int64_t bi = INT64_MAX;
+    for (int g = tid; g < D.update_grid; g += BLOCK) {
+        const ArgMinEntry v = D.rparts[g];
+        if (argmin_better(v.val, v.idx, bv, bi)) {
+            bv = v.val;
+            bi = v.idx;
+        }
+    }
+    wave_argmin(bv, bi);
+    if (lane == 0) s_red[wave] = ArgMinEntry{bv, bi};
+    __syncthreads();
+    if (tid == 0) {
+        ArgMinEntry t = s_red[0];
+        for (int w = 1; w < WAVES; ++w)
+            if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
+        s_win = t;
+        s_up = D.ub[S.p];
+        s_at = D.at_upper[S.p];
+        s_fr = F.is_free[S.p];
+    }
+    __syncthreads();
+    const double tq = s_win.val;
+    const bool none = s_win.idx == INT64_MAX;
+    const int64_t q = none ? 0 : (s_win.idx >> 1);
+    const int side = none ? 0 : (int)(s_win.idx & 1);
+    const int64_t p = S.p;
+    const double u_p = s_up;
+    const int up_p = s_at;
+    const bool fr_p = s_fr != 0;
+    const double sg = fr_p ? (S.d_p < 0.0 ? 1.0 : -1.0) : (up_p ? -1.0 : 1.0);
+    const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;
+    double* a_cur = (it & 1) ? P.alpha1 : P.alpha0;
+    const bool flip = u_p < INFINITY && (none || u_p <= tq);  // (a free column: u_p = +inf)
+
+    if (flip || none) {
+        if (flip) {
+            const double dx = up_p ? -u_p : u_p;
+            const double* Ap = P.A + p * L;
+            int bad = 0;
+            for (int64_t i = tid; i < m; i += BLOCK) {
+                const double xn = fma(-u_p, sg * al[i], P.x_b[i]);
+                P.x_b[i] = xn;
+                D.b_eff[i] = fma(-dx, Ap[i], D.b_eff[i]);
+                if (ph1) {
+                    const double wv = row_class_f(xn, F.lb_B[i], D.ub_B[i], ftol);
+                    X.w[i] = wv;
+                    bad += wv != 0.0;
+                }
+            }
+            if (ph1 && bad) atomicAdd(&s_cnt, bad);  // (an integer count: order-free)
+        }
+        for (int64_t i = tid; i < L; i += BLOCK) a_cur[i] = (i == 0) ? 1.0 : 0.0;
+        __syncthreads();
+        if (tid == 0) {
+            if (flip) {
+                D.at_upper[p] = up_p ? 0 : 1;
+                D.rec->flips += 1;
+                if (ph1) {
+                    X.ph->ninf = s_cnt;
+                    X.ph->passes += 1;
+                }
+            } else {
+                st->status = ph1 ? ST_BREAKDOWN : ST_UNBOUNDED;
+            }
+            if (!ph1 && s_stale) X.ph->y_stale = 0;
+            st->q = 0;
+            st->aq = 1.0;
+            st->p = p;
+            st->min_e = S.d_p;
+            D.rec->fresh = 0;
+            E.se->pend = 0;  // (this pass's pricing applied it; a flip changes no weight)
+            E.se->need_tau = 0;
+        }
+        return;
+    }
+
+    // pivot it
+    double* y = S.y_buf ? P.y1 : P.y0;
+    const double aq = al[q];
+    const double theta = tq, sy = -(S.d_p / aq);
+    const double x_off = up_p ? u_p : 0.0;  // (a free column sits at 0 and is never at upper)
+    const double l_p = fr_p ? -INFINITY : 0.0;
+    const bool book = tid == BLOCK - 64;
+    int64_t leave = -1;
+    double c_p = 0.0;
+    int kp = -1, last = -1;
+    if (book) {
+        leave = P.b_ixs[q];
+        c_p = P.c[p];
+        kp = P.nb_pos[p];
+        last = P.nb_list[S.cnt - 1];
+    }
+    // ||alpha||^2: a thread's rows ascending, one butterfly, the waves in order (k_pbox_step_se's)
+    double a2 = 0.0;
+    for (int64_t i = tid; i < m; i += BLOCK) a2 = fma(al[i], al[i], a2);
+    a2 = wave_sum(a2);
+    if (lane == 0) s_gp[wave] = a2;
+    const double* Sq = P.B0 + q * L;
+    int bad = 0;
+    for (int64_t i0 = tid; i0 < L; i0 += (int64_t)CH * BLOCK) {
+        double xv[CH], av[CH], yv[CH], rv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            xv[u] = i < m ? P.x_b[i] : 0.0;
+            av[u] = i < m ? al[i] : 0.0;
+            yv[u] = i < L ? y[i] : 0.0;
+            rv[u] = i < L ? Sq[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int64_t i = i0 + (int64_t)u * BLOCK;
+            if (i < m) {
+                const double xn = (i == q) ? x_off + sg * theta : fma(-theta, sg * av[u], xv[u]);
+                P.x_b[i] = xn;
+                if (ph1) {  // (row q's bounds are the entering column's: the bookkeeping lane stores them below)
+                    const double wv = row_class_f(xn, i == q ? l_p : F.lb_B[i], i == q ? u_p : D.ub_B[i], ftol);
+                    X.w[i] = wv;
+                    bad += wv != 0.0;
+                }
+            }
+            if (i < L) {
+                if (!ph1) y[i] = fma(sy, rv[u], yv[u]);
+                P.rbuf[i] = rv[u];
+                E.rho[i] = rv[u];  // the weight update's own copy
+            }
+        }
+    }
+    if (ph1 && bad) atomicAdd(&s_cnt, bad);
+    __syncthreads();
+    if (book) {
+        double t = s_gp[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) t += s_gp[w];
+        const double gp = 1.0 + t;
+        const double gl = gp / (aq * aq);
+        E.gamma[leave] = gl > 1.0 ? gl : 1.0;
+        E.se->aq = aq;
+        E.se->gp = gp;
+        E.se->leave = leave;
+        E.se->pend = 1;
+        E.se->need_tau = 1;
+        P.c_B[q] = c_p;
+        P.b_ixs[q] = p;
+        D.ub_B[q] = u_p;
+        F.lb_B[q] = l_p;
+        D.at_upper[p] = 0;
+        D.at_upper[leave] = (int8_t)side;
+        int cnt = S.cnt;
+        P.nb_list[kp] = last;
+        P.nb_pos[last] = kp;
+        P.nb_pos[p] = -1;
+        --cnt;
+        P.nb_list[cnt] = (int32_t)leave;
+        P.nb_pos[leave] = cnt;
+        ++cnt;
+        st->nb_count = cnt;
+        st->aq = aq;
+        st->s_y = sy;
+        st->y_applied = it + 1;
+        st->xb_applied = it + 1;
+        st->p = p;
+        st->q = q;
+        st->min_e = S.d_p;
+        st->iter = it + 1;
+        record_pivot(P, it, p, q);
+        D.rec->fresh = 0;
+        if (side) D.rec->to_upper += 1;
+        if (ph1) {
+            X.ph->ninf = s_cnt;
+            X.ph->passes += 1;
+            X.ph->pivots += 1;
+            X.ph->y_stale = 1;
+        } else if (s_stale) {
+            X.ph->y_stale = 0;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------
 namespace {
@@ -2494,6 +2808,32 @@ hipError_t launch_pbox_price_se1(const Params& P, const PboxArgs& D, const Pbox1
 hipError_t launch_pbox_step_se1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
                                 hipStream_t s) {
     hipLaunchKernelGGL(k_pbox_step_se1, dim3(1), dim3(1024), 0, s, P, D, X, E);
+    return hipGetLastError();
+}
+
+hipError_t pbox_se_f_prepare(const Params& P, const PboxSeCfg& c) {
+    const size_t vec = (size_t)P.L * 8;
+    if (c.lds_vecs == 3) return set_lds(k_pbox_price_se_f<3>, 3 * vec);
+    if (c.lds_vecs == 1) return set_lds(k_pbox_price_se_f<1>, vec);
+    return hipSuccess;
+}
+
+hipError_t launch_pbox_price_se_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
+                                  const PboxFreeArgs& F, const PboxSeCfg& c, hipStream_t s, hipEvent_t e0,
+                                  hipEvent_t e1) {
+    const size_t vec = (size_t)P.L * 8;
+    const size_t lds = c.lds_vecs == 3 ? 3 * vec : (c.lds_vecs == 1 ? vec : 0);
+    auto kernel =
+        c.lds_vecs == 3 ? k_pbox_price_se_f<3> : (c.lds_vecs == 1 ? k_pbox_price_se_f<1> : k_pbox_price_se_f<0>);
+    if (e0 || e1)
+        hipExtLaunchKernelGGL(kernel, dim3(c.price_grid), dim3(PBOX_BLOCK), (uint32_t)lds, s, e0, e1, 0, P, D, X, E, F);
+    else hipLaunchKernelGGL(kernel, dim3(c.price_grid), dim3(PBOX_BLOCK), lds, s, P, D, X, E, F);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_step_se_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
+                                 const PboxFreeArgs& F, hipStream_t s) {
+    hipLaunchKernelGGL(k_pbox_step_se_f, dim3(1), dim3(1024), 0, s, P, D, X, E, F);
     return hipGetLastError();
 }
 

@@ -113,6 +113,26 @@ the sides stream different numbers of non-basic slack columns.  With --solve,
 whole solves of boxed_general at every --solve-shape from the slack basis,
 Dantzig phase 1 / steepest / Dantzig / steepest, each with the CPU certificate.
 
+--free --primal-pricing steepest --phase1-pricing steepest --free-pricing steepest
+measures steepest edge with free columns instead, in phase 1,
+where the kernel it derives from runs; one child per side, the sides alternating:
+  p1_se         boxed_general(m, n, seed) without free columns under steepest edge
+                through phase 1: k_pbox_price_se1 / k_pbox_update1 / k_pbox_step_se1
+  p1_se_free    the same LP with every fifth structural column free (p1_free's LP)
+                and the three opt-ins: k_pbox_price_se_f / k_pbox_update_f /
+                k_pbox_step_se_f
+  p1_free       that LP under Dantzig: k_pbox_price_f / k_pbox_update_f
+  with --parent-lib also p1_se_parent (p1_se on a build of the parent commit: its
+  second run over its first is the session's parent-against-itself spread), and the
+  loops of contexts that never opt in on both builds: pbox_se, pbox_se_parent,
+  pbox, pbox_parent
+  ..._again     every side once more
+The pricing kernels are compared by time and by algorithmic bandwidth
+(bytes_price / time: the sides stream different numbers of non-basic slack
+columns).  With --solve, whole solves of tests/primal_lu_ref.py general_lu at
+every --solve-shape from the slack basis, Dantzig / steepest / Dantzig /
+steepest, each with the CPU certificate (certificate_lu).
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
     python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
@@ -124,6 +144,9 @@ Dantzig phase 1 / steepest / Dantzig / steepest, each with the CPU certificate.
     python tools/pbox_bench.py --free --parent-lib PATH [--out profiles/pbox_lu_c3.json]
     python tools/pbox_bench.py --phase1 --primal-pricing steepest --phase1-pricing steepest [--parent-lib PATH]
                                [--solve --solve-shape 1024 4096 4] [--out profiles/pbox_p1se_c3.json]
+    python tools/pbox_bench.py --free --primal-pricing steepest --phase1-pricing steepest --free-pricing steepest
+                               [--parent-lib PATH] [--solve --solve-shape 512 2048 4 --solve-shape 1024 4096 4]
+                               [--out profiles/pbox_free_se_c3.json]
     python tools/pbox_bench.py --ranging --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5
                                --kernel-shape 4096 16384 5 [--parent-root DIR] [--out profiles/ranging_c3.json]
 """
@@ -401,7 +424,78 @@ def _parent_bindings():
     """A build of the parent commit (SPX_LIB) lacks the entry point this package binds since."""
     from simplex_method_gpu_amd import _lib
 
-    _lib.SIGNATURES.pop("spx_set_primal_phase_one_pricing")
+    _lib.SIGNATURES.pop("spx_set_primal_free_pricing")
+
+
+def _free_fifth(a):
+    """p1_dense's LP with every fifth structural column free: (A_cols, b, c, l, u, free count)."""
+    import numpy as np
+
+    import primal_phase1_ref
+
+    A, b, c, u = primal_phase1_ref.boxed_general(a.m, a.n, a.seed)
+    ns = a.n - a.m
+    fr = np.arange(ns) % 5 == 2
+    l = np.zeros(a.n)
+    l[:ns][fr] = -np.inf
+    u[:ns][fr] = np.inf
+    return np.ascontiguousarray(A.T), b, c, l, u, int(fr.sum())
+
+
+def run_p1_se_free(a):
+    """p1_free's LP under steepest edge in both phases, free columns included."""
+    import simplex_method_gpu_amd as spx
+
+    A_cols, b, c, l, u, nfree = _free_fifth(a)
+    S = spx.PRIMAL_PRICING_STEEPEST
+    res = measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, lower=l,
+                                                    upper=u, primal_phase1=True, primal_pricing=S,
+                                                    primal_phase1_pricing=S, primal_free_pricing=S, timing=timing),
+                         a.k, a.warm, a.k, False)
+    res["free_columns"] = nfree
+    return res
+
+
+def run_p1_se_parent(a):
+    _parent_bindings()
+    return run_p1_se(a)
+
+
+def run_solve_lu(a):
+    """Whole solves of general_lu (a fifth of the structural columns free) from the
+    slack basis through phase 1, under Dantzig or under steepest edge throughout."""
+    import numpy as np
+
+    import primal_lu_ref
+    import simplex_method_gpu_amd as spx
+
+    out = []
+    steep = a.primal_pricing == "steepest"
+    rule = spx.PRIMAL_PRICING_STEEPEST if steep else spx.PRIMAL_PRICING_DANTZIG
+    for (m, n, seed) in [tuple(s) for s in a.solve_shape]:
+        A, b, c, l, u = primal_lu_ref.general_lu(m, n, seed)
+        with spx.Context(np.ascontiguousarray(A.T), b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, lower=l, upper=u,
+                         refactor_every=a.refactor, primal_phase1=True, primal_pricing=rule,
+                         primal_phase1_pricing=rule, primal_free_pricing=rule) as ctx:
+            ctx.iterate(20)  # (first-launch costs)
+            ctx.reset()
+            t0 = time.perf_counter()
+            r = ctx.solve()
+            dt = time.perf_counter() - t0
+            x, up = ctx.primal()
+            fl = ctx.primal_flips()
+            ph = ctx.primal_phase1()
+        rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "primal_pricing": a.primal_pricing,
+               "free_columns": int(np.isneginf(l).sum()), "free_basic": int(np.isneginf(l)[r.b_ixs].sum()),
+               "status": int(r.status), "pivots": r.pivots, "z": r.z, "seconds": round(dt, 4),
+               "it_per_s": round(r.pivots / dt, 1), "flip_passes": fl[0], "to_upper": fl[1],
+               "phase1_passes": ph[0], "phase1_pivots": ph[1], "phase1_rows": ph[2]}
+        if int(r.status) == 1:
+            viol, dviol, zc = primal_lu_ref.certificate_lu(A, b, c, l, u, r.b_ixs, up)
+            rec.update({"cert_bound_violation": viol, "cert_dual_violation": dviol,
+                        "cert_z_rel": abs(zc - r.z) / abs(zc), "cert_ok": bool(viol <= 1e-9 and dviol <= 1e-7)})
+        out.append(rec)
+    return out
 
 
 def run_pbox_se_parent(a):
@@ -452,31 +546,18 @@ def run_solve_p1(a):
 
 def run_p1_free(a):
     """p1_dense's LP with every fifth structural column free."""
-    import numpy as np
-
-    import primal_phase1_ref
     import simplex_method_gpu_amd as spx
 
-    A, b, c, u = primal_phase1_ref.boxed_general(a.m, a.n, a.seed)
-    ns = a.n - a.m
-    fr = np.arange(ns) % 5 == 2
-    l = np.zeros(a.n)
-    l[:ns][fr] = -np.inf
-    u[:ns][fr] = np.inf
-    A_cols = np.ascontiguousarray(A.T)
-    del A
+    A_cols, b, c, l, u, nfree = _free_fifth(a)
     res = measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, lower=l,
                                                     upper=u, primal_phase1=True, timing=timing), a.k, a.warm, a.k, False)
-    res["free_columns"] = int(fr.sum())
+    res["free_columns"] = nfree
     return res
 
 
 def run_p1_parent(a):
-    """p1_dense on a build of the parent commit (SPX_LIB), which lacks the entry points this package binds since."""
-    from simplex_method_gpu_amd import _lib
-
-    for name in ("spx_set_bounds_lu", "spx_get_bounds_lu"):
-        _lib.SIGNATURES.pop(name)
+    """p1_dense on a build of the parent commit (SPX_LIB)."""
+    _parent_bindings()
     return run_p1_dense(a)
 
 
@@ -753,7 +834,9 @@ def main():
     ap.add_argument("--role", default=None,
                     choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se",
                              "warm_resolve", "wexact_kernel", "p1_free", "p1_parent", "ranging_kernel", "p1_se",
-                             "pbox_se_parent", "pbox_parent", "solve_p1"])
+                             "pbox_se_parent", "pbox_parent", "solve_p1", "p1_se_free", "p1_se_parent", "solve_lu"])
+    ap.add_argument("--free-pricing", default="dantzig", choices=["dantzig", "steepest"],
+                    help="with --free --primal-pricing steepest: steepest edge with free columns (DESIGN.md 7m)")
     ap.add_argument("--parent-root", default=None,
                     help="with --ranging: a built checkout of the parent commit (its package and its libsimplex.so)")
     ap.add_argument("--ranging", action="store_true",
@@ -765,7 +848,8 @@ def main():
                "pbox_se": run_pbox_se, "warm_resolve": run_warm_resolve, "wexact_kernel": run_wexact_kernel,
                "p1_free": run_p1_free, "p1_parent": run_p1_parent, "ranging_kernel": run_ranging_kernel,
                "p1_se": run_p1_se, "pbox_se_parent": run_pbox_se_parent, "pbox_parent": run_pbox_parent,
-               "solve_p1": run_solve_p1}[a.role]
+               "solve_p1": run_solve_p1, "p1_se_free": run_p1_se_free, "p1_se_parent": run_p1_se_parent,
+               "solve_lu": run_solve_lu}[a.role]
         print(json.dumps(run(a)), flush=True)
         return
     if a.ranging:
@@ -814,6 +898,53 @@ def main():
     if a.k < 252:
         ap.error("--k: at least 252 timed pivots")
     res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "seed": a.seed}
+    if a.free and a.primal_pricing == "steepest":
+        if a.phase1_pricing != "steepest" or a.free_pricing != "steepest":
+            ap.error("--free --primal-pricing steepest needs --phase1-pricing steepest and --free-pricing steepest (the "
+                     "library refuses it otherwise)")
+        if a.parent_lib and not os.path.exists(a.parent_lib):
+            ap.error("--parent-lib: no such file")
+        sides = [("p1_se", "p1_se"), ("p1_se_free", "p1_se_free"), ("p1_free", "p1_free")]
+        if a.parent_lib:
+            sides += [("p1_se_parent", "p1_se_parent"), ("pbox_se", "pbox_se"), ("pbox_se_parent", "pbox_se_parent"),
+                      ("pbox", "pbox"), ("pbox_parent", "pbox_parent")]
+        for again in ("", "_again"):
+            for key, role in sides:
+                res[key + again] = child(a, role, "steepest" if "se" in role else "dantzig",
+                                         lib=a.parent_lib if role.endswith("_parent") else None)
+                sys.stderr.write(f"{key + again}: {json.dumps(res[key + again])}\n")
+                sys.stderr.flush()
+        keys = ("price_us", "price_TBps", "update_us", "vtb_us", "passes_per_s")
+        for ag in ("", "_again"):
+            q = res["p1_se_free" + ag]
+            res["p1_se_free_over_p1_se" + ag] = {k: round(q[k] / res["p1_se" + ag][k], 4) for k in keys}
+            res["p1_se_free_over_p1_free" + ag] = {k: round(q[k] / res["p1_free" + ag][k], 4) for k in keys}
+        res["again_over_first"] = {k: {f: round(res[k + "_again"][f] / res[k][f], 4) for f in keys}
+                                   for k in ("p1_se", "p1_se_free", "p1_free")}
+        if a.parent_lib:
+            res["p1_se_parent_again_over_p1_se_parent"] = {k: round(res["p1_se_parent_again"][k] / res["p1_se_parent"][k], 4)
+                                                           for k in keys}
+            res["p1_se_over_p1_se_parent"] = {ag or "first": {k: round(res["p1_se" + ag][k] / res["p1_se_parent" + ag][k], 4)
+                                                              for k in keys} for ag in ("", "_again")}
+            res["this_over_parent_it_per_s"] = {f"{k}{ag}": round(res[k + ag]["it_per_s"] / res[k + "_parent" + ag]["it_per_s"], 4)
+                                                for k in ("pbox_se", "pbox") for ag in ("", "_again")}
+            res["parent_again_over_parent_it_per_s"] = {k: round(res[k + "_parent_again"]["it_per_s"]
+                                                                 / res[k + "_parent"]["it_per_s"], 4) for k in ("pbox_se", "pbox")}
+        if a.solve and a.solve_shape:
+            runs = [child(a, "solve_lu", rule) for rule in ("dantzig", "steepest", "dantzig", "steepest")]
+            res["solve"] = []
+            for i in range(len(a.solve_shape)):
+                dz, se = runs[0][i], runs[1][i]
+                res["solve"].append({"dantzig": dz, "steepest": se, "dantzig_again": runs[2][i],
+                                     "steepest_again": runs[3][i],
+                                     "pivot_ratio": round(dz["pivots"] / se["pivots"], 2),
+                                     "time_ratio": round(dz["seconds"] / se["seconds"], 2),
+                                     "certificates_ok": bool(all(r[i].get("cert_ok") for r in runs))})
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
     if a.phase1 and a.primal_pricing == "steepest":
         if a.phase1_pricing != "steepest":
             ap.error("--phase1 --primal-pricing steepest needs --phase1-pricing steepest (the library refuses it otherwise)")
