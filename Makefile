@@ -16,7 +16,7 @@ LDFLAGS   := -L$(ROCM)/lib -Wl,-rpath,$(ROCM)/lib -lrccl
 LIB       := $(PKG)/libsimplex.so
 # the primal loop's kernel units (make xlib rebuilds these)
 KUNITS    := spx_kernels spx_price spx_update spx_foldk
-UNITS     := $(KUNITS) spx_reinv spx_tableau spx_loop spx_dual spx_pbox spx_pbox_wexact spx_ranging spx_api spx_api_dual spx_api_pbox spx_api_ranging
+UNITS     := $(KUNITS) spx_reinv spx_tableau spx_loop spx_dual spx_pbox spx_pbox_wexact spx_ranging spx_bndrange spx_api spx_api_dual spx_api_pbox spx_api_ranging
 OBJS      := $(UNITS:%=$(BUILD)/%.o)
 CLI       := solver
 GLPKDRV   := solver_glpk

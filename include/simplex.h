@@ -659,9 +659,10 @@ int spx_set_primal_weight_init(spx_ctx* ctx, int32_t mode);
  * SPX_PRIMAL_PRICING_DANTZIG or outside SPX_ALGO_PRIMAL_BOX. */
 int spx_refresh_primal_weights(spx_ctx* ctx);
 
-/* Sensitivity ranging at the optimum: how far one cost
- * coefficient or one right-hand side may move, everything else fixed, before
- * the optimal basis changes, and what blocks it.  Conventions are the bounded
+/* Sensitivity ranging at the optimum (bounds and the objective at
+ * the range ends: spx_ranging_bound and spx_ranging_objective below, §7n): how
+ * far one cost coefficient or one right-hand side may move, everything else
+ * fixed, before the optimal basis changes, and what blocks it.  Conventions are the bounded
  * loops': maximise c.x, d = y.A - c, sigma_k = +1 for a non-basic column at its
  * lower bound and -1 at its upper bound, optimal means sigma_k d_k >= 0; tol =
  * opts.piv_tol, s_k = max(sigma_k d_k, 0).  Every result is a non-negative delta
@@ -695,6 +696,45 @@ int spx_refresh_primal_weights(spx_ctx* ctx);
  * by the first call; a context that never asks allocates and launches nothing. */
 int spx_ranging_cost(spx_ctx* ctx, double* down, double* up, int64_t* block_down, int64_t* block_up);
 int spx_ranging_rhs(spx_ctx* ctx, double* down, double* up, int64_t* leave_down, int64_t* leave_up);
+
+/* Bound ranging, n entries each: how far one bound of column j
+ * may move, everything else fixed, before the optimal basis changes.  The
+ * conventions, the refusals and the promises are those of the two calls above;
+ * leave_* = 2 row + side of the row that leaves (side 1: to its upper bound),
+ * the smallest on equal ratios, -1 where nothing blocks, SPX_RANGING_OWN_BOUND
+ * where the moving bound meets the column's own other bound first.
+ *
+ * Non-basic and not free (at lower or at upper alike): the bound the column sits
+ * at moves by t and the column with it, x_B(t) = x_B - t alpha, alpha = B^-1 A_j.
+ * up (t > 0): alpha_i > tol blocks at x_i / alpha_i (side 0), alpha_i < -tol with
+ * ub_B[i] finite at (ub_B[i] - x_i) / -alpha_i (side 1).  down (t < 0): alpha_i <
+ * -tol blocks at x_i / -alpha_i (side 0), alpha_i > tol with ub_B[i] finite at
+ * (ub_B[i] - x_i) / alpha_i (side 1).  A row whose basic column is free never
+ * blocks.  At lower, up is also capped by the column's range ub_j = u_j - l_j, at
+ * upper down is: SPX_RANGING_OWN_BOUND, only where strictly smaller than every
+ * row's ratio (a fixed column, ub_j = 0, by the same rule).  Non-basic and free:
+ * no bound to move, both +inf with -1.  Basic in row i: up = x_i, how far its
+ * lower bound may rise (2 i; a free column: +inf, -1); down = ub_B[i] - x_i, how
+ * far its upper bound may fall (2 i + 1; no upper bound: +inf, -1).  For a
+ * non-basic slack of row r at lower, up is spx_ranging_rhs's down[r] and down
+ * its up[r], values and indices bit for bit. */
+#define SPX_RANGING_OWN_BOUND (-2)
+int spx_ranging_bound(spx_ctx* ctx, double* down, double* up, int64_t* leave_down, int64_t* leave_up);
+
+/* The objective at the two ends of every range: down / up are the arrays the
+ * matching call returned (what = SPX_RANGING_COST: n entries, _RHS: m, _BOUND: n).
+ * Host arithmetic in fp64 from the context's own readbacks; z is spx_objective's,
+ * in the caller's variables.  Cost: obj_up = z + up x_j, obj_down = z - down x_j,
+ * x as spx_get_primal gives it.  Right-hand side: z +- delta y_r.  Bound, a
+ * non-basic column that is not free: obj_up = z - up d_j, obj_down = z + down d_j
+ * with d = y.A - c; basic or free: z both ways.  A multiplier that is exactly 0
+ * gives z even where the delta is +inf; otherwise +inf propagates with its sign.
+ * The refusals of the ranging calls apply; SPX_ERR_ARG for an unknown `what`. */
+#define SPX_RANGING_COST  0
+#define SPX_RANGING_RHS   1
+#define SPX_RANGING_BOUND 2
+int spx_ranging_objective(spx_ctx* ctx, int32_t what, const double* down, const double* up, double* obj_down,
+                          double* obj_up);
 
 /* Phase-1 counters of the bounded primal loop, kept on the device by the kernel
  * that commits the pass: out[0] phase-1 passes since spx_create or spx_reset
@@ -830,6 +870,11 @@ int spx_pbox_wexact_times(spx_ctx* ctx, double* ms, int64_t* launches);
  * gather, the product and the merge) and [1] the right-hand-side rangings (B^-1
  * brought current, the stream and the merge). */
 int spx_ranging_times(spx_ctx* ctx, double ms[2], int64_t launches[2]);
+
+/* With SPX_FLAG_TIMING: total device milliseconds and count of the bound
+ * rangings (B^-1 brought current, the gather, the product, the merge and the
+ * basic columns) since the last call (resets). */
+int spx_ranging_bound_times(spx_ctx* ctx, double* ms, int64_t* launches);
 
 /* With SPX_FLAG_TIMING: device milliseconds summed since the last call (resets)
  * of out[0] the pricing kernel, out[1] pricing + the cross-rank MINLOC

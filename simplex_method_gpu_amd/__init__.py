@@ -31,7 +31,7 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX",
            "FLAG_PRIMAL_PHASE1", "PRIMAL_PRICING_DANTZIG", "PRIMAL_PRICING_STEEPEST", "FLAG_PRIMAL_STEEPEST",
            "PRIMAL_WEIGHTS_REFERENCE", "PRIMAL_WEIGHTS_EXACT", "FLAG_PRIMAL_EXACT_WEIGHTS", "FLAG_PRIMAL_PHASE1_STEEPEST",
-           "CostRanging", "RhsRanging"]
+           "CostRanging", "RhsRanging", "BoundRanging", "RangeEnds", "RANGING_OWN_BOUND"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -110,6 +110,24 @@ class RhsRanging(NamedTuple):
     up: np.ndarray
     leave_down: np.ndarray
     leave_up: np.ndarray
+
+
+RANGING_OWN_BOUND = -2  # BoundRanging.leave_*: the column's own other bound (SPX_RANGING_OWN_BOUND)
+
+
+class BoundRanging(NamedTuple):
+    """Context.bound_ranging(): non-negative deltas and 2 row + side of the leaving rows
+    (-1: nothing blocks; RANGING_OWN_BOUND: the column's own other bound)."""
+    down: np.ndarray
+    up: np.ndarray
+    leave_down: np.ndarray
+    leave_up: np.ndarray
+
+
+class RangeEnds(NamedTuple):
+    """Context.ranging_objective(): the objective at the down / up end of every range."""
+    down: np.ndarray
+    up: np.ndarray
 
 
 def _ptr(a: np.ndarray | None):
@@ -644,6 +662,39 @@ class Context:
         ms, k = (ctypes.c_double * 2)(), (ctypes.c_int64 * 2)()
         check(self._L.spx_ranging_times(self._h, ms, k))
         return (ms[0], ms[1]), (k[0], k[1])
+
+    def bound_ranging(self) -> "BoundRanging":
+        """At an optimum of ALGO_DUAL / ALGO_PRIMAL_BOX: how far one bound of each
+        column may go down and up before the basis changes, and 2 row + side of
+        the row that then leaves (-1: nothing blocks; RANGING_OWN_BOUND: the
+        moving bound meets the column's other bound first); n entries each
+        (spx_ranging_bound)."""
+        n = self.n
+        r = BoundRanging(np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64))
+        check(self._L.spx_ranging_bound(self._h, _ptr(r.down), _ptr(r.up), _ptr(r.leave_down), _ptr(r.leave_up)))
+        return r
+
+    def ranging_objective(self, r) -> "RangeEnds":
+        """The objective at the two ends of every range of r, a CostRanging,
+        RhsRanging or BoundRanging of this context (spx_ranging_objective)."""
+        what = {CostRanging: 0, RhsRanging: 1, BoundRanging: 2}.get(type(r))
+        if what is None:
+            raise TypeError("ranging_objective takes a CostRanging, RhsRanging or BoundRanging")
+        down = np.ascontiguousarray(r.down, dtype=np.float64)
+        up = np.ascontiguousarray(r.up, dtype=np.float64)
+        k = self.m if what == 1 else self.n
+        if down.shape != (k,) or up.shape != (k,):
+            raise ValueError(f"expected {k} entries")
+        e = RangeEnds(np.zeros(k), np.zeros(k))
+        check(self._L.spx_ranging_objective(self._h, what, _ptr(down), _ptr(up), _ptr(e.down), _ptr(e.up)))
+        return e
+
+    def bound_ranging_times(self):
+        """(milliseconds, calls) of the bound rangings since the last call
+        (timing=True; spx_ranging_bound_times)."""
+        ms, k = ctypes.c_double(), ctypes.c_int64()
+        check(self._L.spx_ranging_bound_times(self._h, ctypes.byref(ms), ctypes.byref(k)))
+        return ms.value, k.value
 
     def wg_times(self):
         """Per-pass clocks of the last two compact window passes (stamps=True,

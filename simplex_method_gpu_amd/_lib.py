@@ -81,6 +81,9 @@ SIGNATURES = {
     "spx_ranging_cost": (ctypes.c_int, [_p, _p, _p, _p, _p]),
     "spx_ranging_rhs": (ctypes.c_int, [_p, _p, _p, _p, _p]),
     "spx_ranging_times": (ctypes.c_int, [_p, _p, _p]),
+    "spx_ranging_bound": (ctypes.c_int, [_p, _p, _p, _p, _p]),
+    "spx_ranging_objective": (ctypes.c_int, [_p, _i32, _p, _p, _p, _p]),
+    "spx_ranging_bound_times": (ctypes.c_int, [_p, _p, _p]),
     "spx_group_iterate": (ctypes.c_int, [_p, _i32, _i64, _p, _p]),
     "spx_group_sync": (ctypes.c_int, [_p, _i32]),
     "spx_solve": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _p]),

@@ -83,6 +83,12 @@
 //                  up leave_down leave_up), "%.17g %.17g %lld %lld"; any other
 //                  status prints the library's refusal (exit 1); without --dual or
 //                  --primal-box it is refused by name (exit 1)
+//   --bound-ranging PREFIX  after a --dual or --primal-box solve that ends at the
+//                  optimum: bound ranging and the objective at the range ends
+//                  (spx_ranging_bound / _objective) written to
+//                  PREFIX.bound.txt (one line per column: down up leave_down
+//                  leave_up obj_down obj_up), "%.17g %.17g %lld %lld %.17g %.17g";
+//                  refusals as --ranging's
 //   --tableau      window tableau (SPX_FLAG_TABLEAU): T_w = B_w A
 //                  kept in HBM, no per-pivot A / B^-1 stream
 //   --mps          the input is an MPS file (mps_io.h): converted to the
@@ -128,7 +134,7 @@ static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
                  " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--phase1-pricing dantzig|steepest] [--free-pricing dantzig|steepest] [--primal-weights reference|exact]]"
-                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F] [--ranging PREFIX]"
+                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F] [--ranging PREFIX] [--bound-ranging PREFIX]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -140,7 +146,7 @@ int main(int argc, char* argv[]) {
     int device = -1;
     bool iter_lines = true, json = false, gen = false, solve = true;
     int threads = 0;
-    std::string write_bin, write_text, bounds_path, lower_path, ranging_prefix;
+    std::string write_bin, write_text, bounds_path, lower_path, ranging_prefix, bound_ranging_prefix;
     int64_t gm = 0, gn = 0;
     uint64_t gseed = 0;
     const char* path = nullptr;
@@ -189,6 +195,7 @@ int main(int argc, char* argv[]) {
         else if (s == "--primal-box") primal_box = true;
         else if (s == "--phase1") phase1 = true;
         else if (s == "--ranging") { need(1); ranging_prefix = argv[++a]; }
+        else if (s == "--bound-ranging") { need(1); bound_ranging_prefix = argv[++a]; }
         else if (s == "--bounds") { need(1); bounds_path = argv[++a]; }
         else if (s == "--lower") { need(1); lower_path = argv[++a]; }
         else if (s == "--dual-pricing") {
@@ -274,6 +281,10 @@ int main(int argc, char* argv[]) {
     }
     if (!ranging_prefix.empty() && !primal_box && !dual) {
         std::cerr << "--ranging needs --dual or --primal-box: ranging describes an optimum of the bounded loops\n";
+        return 1;
+    }
+    if (!bound_ranging_prefix.empty() && !primal_box && !dual) {
+        std::cerr << "--bound-ranging needs --dual or --primal-box: ranging describes an optimum of the bounded loops\n";
         return 1;
     }
     if (primal_pricing_given && !primal_box) {
@@ -443,6 +454,28 @@ int main(int argc, char* argv[]) {
         }
         if (!ok) {
             if (rc != SPX_OK) std::cerr << "--ranging failed (" << rc << "): " << spx_last_error() << "\n";
+            spx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+    }
+    if (!bound_ranging_prefix.empty()) {  // PREFIX.bound.txt (n lines): down up index index obj_down obj_up
+        std::vector<double> dn((size_t)n), up((size_t)n), zd((size_t)n), zu((size_t)n);
+        std::vector<int64_t> kd((size_t)n), ku((size_t)n);
+        rc = spx_ranging_bound(ctx, dn.data(), up.data(), kd.data(), ku.data());
+        if (rc == SPX_OK) rc = spx_ranging_objective(ctx, SPX_RANGING_BOUND, dn.data(), up.data(), zd.data(), zu.data());
+        if (rc != SPX_OK) {
+            std::cerr << "--bound-ranging failed (" << rc << "): " << spx_last_error() << "\n";
+            spx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+        const std::string file = bound_ranging_prefix + ".bound.txt";
+        std::FILE* f = std::fopen(file.c_str(), "w");
+        if (f)
+            for (int64_t k = 0; k < n; ++k)
+                std::fprintf(f, "%.17g %.17g %lld %lld %.17g %.17g\n", dn[(size_t)k], up[(size_t)k],
+                             (long long)kd[(size_t)k], (long long)ku[(size_t)k], zd[(size_t)k], zu[(size_t)k]);
+        if (!f || std::fclose(f) != 0) {
+            std::cerr << "--bound-ranging: cannot write " << file << "\n";
             spx_destroy(ctx);
             return EXIT_FAILURE;
         }

@@ -1392,6 +1392,7 @@ void spx_destroy(spx_ctx* x) {
     for (hipEvent_t e : x->pbox.ev_wx) (void)hipEventDestroy(e);
     for (const std::vector<hipEvent_t>& v : x->rng.ev)
         for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    for (hipEvent_t e : x->brng.ev) (void)hipEventDestroy(e);
     if (x->comm) (void)ncclCommDestroy(x->comm);
     for (void* p : x->mbox_opened) (void)hipIpcCloseMemHandle(p);
     for (void* p : x->allocs) (void)hipFree(p);

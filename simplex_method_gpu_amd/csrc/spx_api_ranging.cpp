@@ -1,10 +1,11 @@
-// spx_api_ranging.cpp — sensitivity ranging's host side (kernels: spx_ranging.h;
-// DESIGN.md §7k): its state (RangingState, spx_ctx.h), the refusals, and the
-// three entry points.  A call reads the context and writes only its own
+// spx_api_ranging.cpp — sensitivity ranging's host side (kernels: spx_ranging.h,
+// spx_bndrange.h): its state (RangingState and
+// BoundRangingState, spx_ctx.h), the refusals, and the entry points.  A call reads the context and writes only its own
 // buffers: the basis, the placements, x_b, y, S, the pending pivot record, the
 // steepest-edge record and weights, the pivot count and the status stay as they
 // are (flush is the readbacks': a y left stale by phase 1 is refreshed first).
 #include <cmath>
+#include <vector>
 
 #include "spx_ctx.h"
 
@@ -95,6 +96,52 @@ int ranging_events(spx_ctx* x, int which, hipEvent_t* e0, hipEvent_t* e1) {
     return SPX_OK;
 }
 
+// bound ranging's buffers and geometry, on first use
+int bound_setup(spx_ctx* x) {
+    BoundRangingState& g = x->brng;
+    if (g.args.parts) return SPX_OK;
+    const size_t n = (size_t)x->n;
+    g.cfg = bnd_geometry(x->m, x->n);
+    HIP_TRY(bnd_prepare());
+    SPX_TRY(pbox_binv_copy(x));
+    SPX_TRY(x->alloc(&g.free_flags, n));
+    SPX_TRY(x->alloc(&g.args.col, (size_t)g.cfg.cap));
+    SPX_TRY(x->alloc(&g.args.kind, (size_t)g.cfg.cap));
+    SPX_TRY(x->alloc(&g.args.ubj, (size_t)g.cfg.cap));
+    SPX_TRY(x->alloc(&g.args.down, n));
+    SPX_TRY(x->alloc(&g.args.up, n));
+    SPX_TRY(x->alloc(&g.args.kdown, n));
+    SPX_TRY(x->alloc(&g.args.kup, n));
+    SPX_TRY(x->alloc(&g.args.parts, g.cfg.parts));
+    g.args.cap = g.cfg.cap;
+    g.args.row_blocks = g.cfg.row_blocks;
+    return SPX_OK;
+}
+
+// what a call reads of the context as it is now (as ranging_bind)
+int bound_bind(spx_ctx* x) {
+    BoundRangingState& g = x->brng;
+    g.args.S = x->pbox.wx_S;
+    g.args.ub = x->dual.args.ub;
+    g.args.at_upper = x->dual.args.at_upper;
+    g.args.ub_B = x->dual.args.ub_B;
+    g.args.tol = x->opts.piv_tol;
+    g.args.is_free = nullptr;
+    if (x->dual.nfree > 0) {
+        std::vector<int8_t> fr((size_t)x->n);
+        for (size_t j = 0; j < fr.size(); ++j) fr[j] = x->dual.lb[j] == -INFINITY ? 1 : 0;
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        HIP_TRY(hipMemcpy(g.free_flags, fr.data(), fr.size(), hipMemcpyHostToDevice));
+        g.args.is_free = g.free_flags;
+    }
+    return SPX_OK;
+}
+
+// z + sign * delta * mult; a multiplier that is exactly 0 gives z even where delta is +inf
+double range_end(double z, double sign, double delta, double mult) {
+    return mult == 0.0 ? z : z + sign * delta * mult;
+}
+
 }  // namespace
 
 }  // namespace spx_host
@@ -145,6 +192,91 @@ int spx_ranging_rhs(spx_ctx* x, double* down, double* up, int64_t* leave_down, i
     HIP_TRY(hipMemcpy(up, g.args.r_up, m * sizeof(double), hipMemcpyDeviceToHost));
     if (leave_down) HIP_TRY(hipMemcpy(leave_down, g.args.r_kdown, m * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (leave_up) HIP_TRY(hipMemcpy(leave_up, g.args.r_kup, m * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_ranging_bound(spx_ctx* x, double* down, double* up, int64_t* leave_down, int64_t* leave_up) {
+    if (!x || !down || !up) return fail(SPX_ERR_ARG, "NULL argument");
+    SPX_TRY(ranging_refusal(x, "spx_ranging_bound"));
+    SPX_TRY(bound_setup(x));
+    SPX_TRY(flush(x));
+    SPX_TRY(bound_bind(x));
+    BoundRangingState& g = x->brng;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (x->timing) {
+        while (g.ev.size() < 2 * (g.n_ev + 1)) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            g.ev.push_back(e);
+        }
+        e0 = g.ev[2 * g.n_ev];
+        e1 = g.ev[2 * g.n_ev + 1];
+        ++g.n_ev;
+    }
+    if (e0) HIP_TRY(hipEventRecord(e0, x->stream));
+    HIP_TRY(launch_materialize(x->P, x->pbox.wx_S, x->stream));
+    HIP_TRY(launch_rng_bound(x->P, g.args, g.cfg, x->stream));
+    if (e1) HIP_TRY(hipEventRecord(e1, x->stream));
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    const size_t n = (size_t)x->n;
+    HIP_TRY(hipMemcpy(down, g.args.down, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(up, g.args.up, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (leave_down) HIP_TRY(hipMemcpy(leave_down, g.args.kdown, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (leave_up) HIP_TRY(hipMemcpy(leave_up, g.args.kup, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_ranging_bound_times(spx_ctx* x, double* ms, int64_t* launches) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (!x->timing) return fail(SPX_ERR_STATE, "context created without SPX_FLAG_TIMING");
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    BoundRangingState& g = x->brng;
+    double t = 0.0;
+    for (size_t i = 0; i < g.n_ev; ++i) {
+        float e = 0.f;
+        HIP_TRY(hipEventElapsedTime(&e, g.ev[2 * i], g.ev[2 * i + 1]));
+        t += e;
+    }
+    if (ms) *ms = t;
+    if (launches) *launches = (int64_t)g.n_ev;
+    g.n_ev = 0;
+    return SPX_OK;
+}
+
+int spx_ranging_objective(spx_ctx* x, int32_t what, const double* down, const double* up, double* obj_down,
+                          double* obj_up) {
+    if (!x || !down || !up || !obj_down || !obj_up) return fail(SPX_ERR_ARG, "NULL argument");
+    if (what != SPX_RANGING_COST && what != SPX_RANGING_RHS && what != SPX_RANGING_BOUND)
+        return fail(SPX_ERR_ARG, "unknown kind of ranging %d (SPX_RANGING_COST, _RHS or _BOUND)", (int)what);
+    SPX_TRY(ranging_refusal(x, "spx_ranging_objective"));
+    const size_t n = (size_t)x->n, m = (size_t)x->m;
+    double z = 0.0;
+    SPX_TRY(spx_objective(x, &z));
+    if (what == SPX_RANGING_COST) {  // z +- delta x_j, x in the caller's variables
+        std::vector<double> xv(n);
+        SPX_TRY(spx_get_primal(x, xv.data(), nullptr));
+        for (size_t j = 0; j < n; ++j) {
+            obj_down[j] = range_end(z, -1.0, down[j], xv[j]);
+            obj_up[j] = range_end(z, 1.0, up[j], xv[j]);
+        }
+    } else if (what == SPX_RANGING_RHS) {  // z +- delta y_r
+        std::vector<double> y(m);
+        SPX_TRY(spx_get_state(x, nullptr, nullptr, y.data(), nullptr, nullptr, nullptr, nullptr));
+        for (size_t r = 0; r < m; ++r) {
+            obj_down[r] = range_end(z, -1.0, down[r], y[r]);
+            obj_up[r] = range_end(z, 1.0, up[r], y[r]);
+        }
+    } else {  // a non-basic column that is not free moves with its bound: z -+ delta d_j; basic or free: z
+        std::vector<double> d(n);
+        std::vector<int32_t> pos(n);
+        SPX_TRY(spx_reduced_costs(x, d.data()));
+        HIP_TRY(hipMemcpy(pos.data(), x->P.nb_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < n; ++j) {
+            const bool moves = pos[j] >= 0 && !(x->dual.nfree > 0 && x->dual.lb[j] == -INFINITY);
+            obj_down[j] = moves ? range_end(z, 1.0, down[j], d[j]) : z;
+            obj_up[j] = moves ? range_end(z, -1.0, up[j], d[j]) : z;
+        }
+    }
     return SPX_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "spx_loop.h"
 #include "spx_pbox.h"
 #include "spx_ranging.h"
+#include "spx_bndrange.h"
 #include "spx_reinv.h"
 
 namespace spx_host {
@@ -196,6 +197,20 @@ struct RangingState {
     size_t n_ev[2] = {0, 0};
 };
 
+// Bound ranging (spx_bndrange.h; everything that reads or writes it is in
+// spx_api_ranging.cpp).  args.parts != nullptr  <=>  bound_setup
+// ran: every buffer of BndArgs but S (PboxState::wx_S, shared as above) and cfg
+// are set, by the first spx_ranging_bound; a context that never asks allocates
+// and launches none of it.  As RangingState, nothing outlives a call but the
+// buffers.
+struct BoundRangingState {
+    spx::BndArgs args{};
+    spx::BndCfg cfg{};
+    int8_t* free_flags = nullptr;  // n (args.is_free while the context holds a free column)
+    std::vector<hipEvent_t> ev;    // timing: pairs around a bound ranging (spx_ranging_bound_times)
+    size_t n_ev = 0;
+};
+
 struct spx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -320,6 +335,7 @@ struct spx_ctx {
     DualState dual;                  // the dual one's state (spx_api_dual.cpp)
     PboxState pbox;                  // the bounded primal one's (spx_api_pbox.cpp)
     RangingState rng;                // sensitivity ranging (spx_api_ranging.cpp)
+    BoundRangingState brng;          // bound ranging (spx_api_ranging.cpp)
 
     template <typename T>
     int alloc(T** p, size_t count, unsigned ext_flags = ~0u) {

@@ -96,6 +96,16 @@ the bounded primal loop of a context that never ranges follows (role pbox, twice
 alternating with --parent-root (a built checkout of the parent commit: its package
 and its libsimplex.so) when one is given.
 
+--bound-ranging measures bound ranging against cost ranging, one
+child process per --kernel-shape: the same LP, context and session as --ranging,
+then, after one untimed round, five rounds of spx_ranging_cost and
+spx_ranging_bound, alternating, with their device times (spx_ranging_times,
+spx_ranging_bound_times) and the ratio of the fastest bound ranging to the
+fastest cost ranging.  With --k >= 252 the loops of contexts that never range
+follow (role pbox: the bounded primal loop; role dual_box: the boxed dual loop on
+tests/dual_box_ref.py boxed), each twice, alternating with --parent-root when one
+is given.
+
 --phase1 --primal-pricing steepest --phase1-pricing steepest measures steepest
 edge through phase 1 instead, one child per side, the sides
 alternating:
@@ -149,6 +159,8 @@ steepest, each with the CPU certificate (certificate_lu).
                                [--out profiles/pbox_free_se_c3.json]
     python tools/pbox_bench.py --ranging --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5
                                --kernel-shape 4096 16384 5 [--parent-root DIR] [--out profiles/ranging_c3.json]
+    python tools/pbox_bench.py --bound-ranging --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5
+                               --kernel-shape 4096 16384 5 [--parent-root DIR] [--out profiles/bound_ranging_c3.json]
 """
 import argparse
 import json
@@ -782,6 +794,61 @@ def run_ranging_kernel(a):
             "finite_rhs_limits": int(np.isfinite(h.down).sum() + np.isfinite(h.up).sum())}
 
 
+def run_bound_ranging_kernel(a):
+    """One shape (the first --kernel-shape): run_ranging_kernel's LP and context, then
+    five rounds of spx_ranging_cost and spx_ranging_bound, alternating, with their
+    device times."""
+    import numpy as np
+
+    import primal_box_ref
+    import simplex_method_gpu_amd as spx
+
+    m, n, seed = a.kernel_shape[0]
+    A, b, c, u = primal_box_ref.boxed_primal(m, n, seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    with spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u, timing=True,
+                     primal_pricing=spx.PRIMAL_PRICING_STEEPEST) as ctx:
+        t0 = time.perf_counter()
+        r = ctx.solve()
+        solve_s = time.perf_counter() - t0
+        if r.status != spx.SolveStatus.OptimumFound:
+            raise SystemExit(f"{m}x{n}: the solve ended with {r.status!r}")
+        ctx.cost_ranging()  # first launches: untimed
+        ctx.bound_ranging()
+        ctx.ranging_times()
+        ctx.bound_ranging_times()
+        cost, bound = [], []
+        for _ in range(5):
+            ctx.cost_ranging()
+            cost.append(round(ctx.ranging_times()[0][0], 4))
+            g = ctx.bound_ranging()
+            bound.append(round(ctx.bound_ranging_times()[0], 4))
+        nb = ~np.isin(np.arange(n), r.b_ixs)
+    flops = 2.0 * m * m * (n - m)
+    return {"m": m, "n": n, "seed": seed, "pivots": r.pivots, "solve_s": round(solve_s, 3),
+            "cost_ms": cost, "bound_ms": bound, "cost_ms_best": min(cost), "bound_ms_best": min(bound),
+            "bound_over_cost": round(min(bound) / min(cost), 3),
+            "bound_fp64_TFLOPs": round(flops / (min(bound) * 1e-3) / 1e12, 2),
+            "finite_bound_limits": int(np.isfinite(g.down[nb]).sum() + np.isfinite(g.up[nb]).sum()),
+            "side1_blockers": sum(int(np.sum((k[nb] >= 0) & (k[nb] % 2 == 1))) for k in (g.leave_down, g.leave_up)),
+            "own_bound_winners": sum(int(np.sum(k[nb] == -2)) for k in (g.leave_down, g.leave_up))}
+
+
+def run_dual_box(a):
+    """The boxed dual loop (tests/dual_box_ref.py boxed) of a context that never ranges."""
+    import numpy as np
+
+    import dual_box_ref
+    import simplex_method_gpu_amd as spx
+
+    A, b, c, u = dual_box_ref.boxed(a.m, a.n, a.seed)
+    A_cols = np.ascontiguousarray(A.T)
+    del A
+    return measure(lambda timing: spx.Context(A_cols, b, c, device=0, window=-1, algorithm=spx.ALGO_DUAL, upper=u,
+                                              timing=timing), a.k, a.warm)
+
+
 def child(a, role, pricing="dantzig", se_lds=None, lib=None, root=None):
     env = dict(os.environ)
     if root is not None:
@@ -834,13 +901,16 @@ def main():
     ap.add_argument("--role", default=None,
                     choices=[None, "primal", "dual", "pbox", "solve", "pbox_flag", "p1_dense", "p1_sparse", "pbox_se",
                              "warm_resolve", "wexact_kernel", "p1_free", "p1_parent", "ranging_kernel", "p1_se",
-                             "pbox_se_parent", "pbox_parent", "solve_p1", "p1_se_free", "p1_se_parent", "solve_lu"])
+                             "pbox_se_parent", "pbox_parent", "solve_p1", "p1_se_free", "p1_se_parent", "solve_lu",
+                             "bound_ranging_kernel", "dual_box"])
     ap.add_argument("--free-pricing", default="dantzig", choices=["dantzig", "steepest"],
                     help="with --free --primal-pricing steepest: steepest edge with free columns (DESIGN.md 7m)")
     ap.add_argument("--parent-root", default=None,
                     help="with --ranging: a built checkout of the parent commit (its package and its libsimplex.so)")
     ap.add_argument("--ranging", action="store_true",
                     help="sensitivity ranging against the exact weight start instead (DESIGN.md 7k)")
+    ap.add_argument("--bound-ranging", action="store_true",
+                    help="bound ranging against cost ranging instead (DESIGN.md 7n); --parent-root as with --ranging")
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
         run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
@@ -849,8 +919,38 @@ def main():
                "p1_free": run_p1_free, "p1_parent": run_p1_parent, "ranging_kernel": run_ranging_kernel,
                "p1_se": run_p1_se, "pbox_se_parent": run_pbox_se_parent, "pbox_parent": run_pbox_parent,
                "solve_p1": run_solve_p1, "p1_se_free": run_p1_se_free, "p1_se_parent": run_p1_se_parent,
-               "solve_lu": run_solve_lu}[a.role]
+               "solve_lu": run_solve_lu, "bound_ranging_kernel": run_bound_ranging_kernel,
+               "dual_box": run_dual_box}[a.role]
         print(json.dumps(run(a)), flush=True)
+        return
+    if a.bound_ranging:
+        import copy
+
+        res = {"k": a.k, "warm": a.warm, "kernel": []}
+        for shape in a.kernel_shape:
+            one = copy.copy(a)
+            one.solve_shape, one.kernel_shape = [], [shape]
+            res["kernel"].append(child(one, "bound_ranging_kernel", "steepest"))
+            sys.stderr.write(f"bound ranging {shape}: {json.dumps(res['kernel'][-1])}\n")
+            sys.stderr.flush()
+        if a.k >= 252:  # the loops of contexts that never range, against the parent build when one is given
+            roots = (("parent", a.parent_root), ("this", None)) if a.parent_root else (("this", None),)
+            for role in ("pbox", "dual_box"):
+                for again in ("", "_again"):
+                    for name, root in roots:
+                        key = f"{role}_{name}{again}"
+                        res[key] = child(a, role, root=root)
+                        sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+                        sys.stderr.flush()
+                if a.parent_root:
+                    base = res[f"{role}_parent"]["it_per_s"]
+                    res[f"{role}_it_per_s_over_parent"] = {
+                        k: round(res[k]["it_per_s"] / base, 4)
+                        for k in (f"{role}_this", f"{role}_parent_again", f"{role}_this_again")}
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
         return
     if a.ranging:
         import copy
