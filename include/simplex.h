@@ -209,8 +209,11 @@ typedef struct spx_opts {
  *         exactly the passes it launches without.  Phase 1 prices with
  *         Dantzig's rule, or with the steepest-edge weights where the loop's
  *         rule is steepest edge and spx_set_primal_phase_one_pricing says so
- *         (below).  Still out: a long-step phase 1, phase 1 under
- *         SPX_ALGO_PRIMAL, a rule that differs between the phases. */
+ *         (below).  The phase-1 ratio test stops at the first row that reaches
+ *         a bound, or walks past such rows while the sum of violations still
+ *         falls (SPX_PRIMAL_RATIO_LONG_STEP, spx_set_primal_phase_one_ratio,
+ *         below).  Still out: phase 1 under SPX_ALGO_PRIMAL, a rule that
+ *         differs between the phases. */
 #define SPX_ALGO_PRIMAL 0
 #define SPX_ALGO_DUAL   1
 #define SPX_ALGO_PRIMAL_BOX 2
@@ -293,6 +296,36 @@ typedef struct spx_opts {
  *            same passes. */
 #define SPX_PRIMAL_WEIGHTS_REFERENCE 0
 #define SPX_PRIMAL_WEIGHTS_EXACT     1
+
+/* Ratio tests of the bounded primal loop's phase-1 passes
+ * (spx_set_primal_phase_one_ratio).  Phase-2 passes are the same
+ * under both.  Notation as above: ahat = sigma_p alpha, only rows with |ahat_i| >
+ * piv_tol take part, entries are ordered by (t, 2 row + side), side 1 = the row
+ * leaves to its upper bound.
+ * TEXTBOOK:  the first row that reaches a bound leaves (above; the default).
+ * LONG_STEP: the sum of violations is piecewise linear along the entering
+ *            direction: its slope is sigma_p d_p < 0 at t = 0 (-|d_p| for a free
+ *            entering column) and gains |ahat_i| where an infeasible row i
+ *            reaches the bound it violates.  Such a point is a soft breakpoint:
+ *            a below row with ahat_i < 0 at x_b[i] / ahat_i (side 0), an above
+ *            row with ahat_i > 0 at (x_b[i] - u_k) / ahat_i (side 1): TEXTBOOK's
+ *            entries.  Hard breakpoints must not be passed: every entry of a
+ *            feasible row (TEXTBOOK's, the free rule included), and the far
+ *            bound of a row that has a soft breakpoint (a below row with a
+ *            finite u_k at (x_b[i] - u_k) / ahat_i, side 1; an above row at
+ *            x_b[i] / ahat_i, side 0).  With h the smallest hard breakpoint,
+ *            the soft breakpoints before h are walked in order, slope +=
+ *            |ahat_i| at each: the first at which slope >= -opts.eps leaves, at
+ *            its t and side; one with a smaller slope is passed (its row comes
+ *            out feasible).  If the walk ends without a leaving row, h leaves,
+ *            or with no hard breakpoint the last soft one; with no breakpoint
+ *            at all the pass is TEXTBOOK's (a flip, or
+ *            SPX_STATUS_THETA_OVERFLOW).  The flip test u_p <= t_q, the commit,
+ *            the classification and the counters are TEXTBOOK's with this t_q.
+ *            No feasible row leaves its box, so ninf still never grows; a walk
+ *            that passes nothing selects TEXTBOOK's row. */
+#define SPX_PRIMAL_RATIO_TEXTBOOK  0
+#define SPX_PRIMAL_RATIO_LONG_STEP 1
 
 /* Ratio tests of the dual loop's boxed passes (SPX_FLAG_DUAL_LONG_STEP at
  * spx_create, spx_set_dual_ratio later).
@@ -639,6 +672,23 @@ int spx_set_primal_phase_one_pricing(spx_ctx* ctx, int32_t rule);
  * rule is STEEPEST (the call would re-create the refused state: set
  * SPX_PRIMAL_PRICING_DANTZIG with spx_set_primal_pricing first). */
 int spx_set_primal_free_pricing(spx_ctx* ctx, int32_t rule);
+
+/* Ratio test of the bounded primal loop's phase-1 passes from the next pass on:
+ * SPX_PRIMAL_RATIO_TEXTBOOK (the default) or SPX_PRIMAL_RATIO_LONG_STEP (above;
+ * DESIGN.md §7o).  Between any two calls and under any algorithm; inert outside
+ * phase 1 (phase 1 off, a feasible basis, phase-2 passes, the other loops).  It
+ * restarts and invalidates nothing: the basis, x_b, y, the weights, the counters
+ * and the status stay.  Under any entering rule and with free columns.  A context
+ * that never sets LONG_STEP allocates and launches nothing for it.  SPX_ERR_ARG
+ * for NULL or an unknown rule.  (The name spells the digit out: the bindings'
+ * header scan reads [a-z_] names.) */
+int spx_set_primal_phase_one_ratio(spx_ctx* ctx, int32_t rule);
+
+/* Counters of the long-step walk, kept on the device by the kernel that walks
+ * (whether the pass then flips or pivots): out[0] rows passed since spx_create or
+ * spx_reset, out[1] passes that passed at least one, out[2] the most in one
+ * pass, out[3] the current rule (SPX_PRIMAL_RATIO_*). */
+int spx_get_primal_long_steps(spx_ctx* ctx, int64_t out[4]);
 
 /* Steepest-edge weights w[0..n) of the current basis, by column: the non-basic
  * entries are live (1 + ||B^-1 A_j||^2 as the recurrence keeps it, a pending

@@ -31,7 +31,8 @@ __all__ = ["SolveStatus", "SolveResult", "Context", "solve", "read_lp", "comm_un
            "DUAL_RATIO_TEXTBOOK", "DUAL_RATIO_LONG_STEP", "FLAG_DUAL_LONG_STEP", "ALGO_PRIMAL_BOX",
            "FLAG_PRIMAL_PHASE1", "PRIMAL_PRICING_DANTZIG", "PRIMAL_PRICING_STEEPEST", "FLAG_PRIMAL_STEEPEST",
            "PRIMAL_WEIGHTS_REFERENCE", "PRIMAL_WEIGHTS_EXACT", "FLAG_PRIMAL_EXACT_WEIGHTS", "FLAG_PRIMAL_PHASE1_STEEPEST",
-           "CostRanging", "RhsRanging", "BoundRanging", "RangeEnds", "RANGING_OWN_BOUND"]
+           "CostRanging", "RhsRanging", "BoundRanging", "RangeEnds", "RANGING_OWN_BOUND",
+           "PRIMAL_RATIO_TEXTBOOK", "PRIMAL_RATIO_LONG_STEP"]
 
 FLAG_TIMING = 1
 FLAG_STAMPS = 2
@@ -76,6 +77,9 @@ FLAG_PRIMAL_PHASE1_STEEPEST = 65536
 # refused).  Context(primal_free_pricing=...) is the interface; the bit itself (SPX_FLAG_PRIMAL_FREE_STEEPEST) stays
 # module-private, the public FLAG_* names end at FLAG_PRIMAL_PHASE1_STEEPEST.
 _FLAG_PRIMAL_FREE_STEEPEST = 131072
+# ratio tests of the bounded primal loop's phase-1 passes (include/simplex.h SPX_PRIMAL_RATIO_*); no flag and no
+# Context keyword: Context.set_primal_phase1_ratio is the interface
+PRIMAL_RATIO_TEXTBOOK, PRIMAL_RATIO_LONG_STEP = 0, 1
 
 
 class SolveStatus(IntEnum):
@@ -261,6 +265,7 @@ class Context:
         if primal_free_pricing not in (PRIMAL_PRICING_DANTZIG, PRIMAL_PRICING_STEEPEST):
             raise ValueError("primal_free_pricing must be PRIMAL_PRICING_DANTZIG or PRIMAL_PRICING_STEEPEST")
         self._primal_free_pricing = primal_free_pricing
+        self._primal_phase1_ratio = PRIMAL_RATIO_TEXTBOOK
         o.flags = ((FLAG_TIMING if timing else 0) | (FLAG_STAMPS if stamps else 0)
                    | (FLAG_GLOBAL_Y if global_y else 0) | (FLAG_ROW_SHARD if row_shard else 0)
                    | (FLAG_SPLIT_TAIL if split_tail else 0)
@@ -463,6 +468,24 @@ class Context:
         holds a free column and the rule is steepest edge."""
         check(self._L.spx_set_primal_free_pricing(self._h, rule))
         self._primal_free_pricing = rule
+
+    def set_primal_phase1_ratio(self, rule: int):
+        """Ratio test of the bounded primal loop's phase-1 passes from the next
+        pass on (spx_set_primal_phase_one_ratio): PRIMAL_RATIO_TEXTBOOK (the
+        default: the first row that reaches a bound leaves) or
+        PRIMAL_RATIO_LONG_STEP (the walk goes past rows that reach the bound
+        they violate while the sum of violations still falls).  Inert outside
+        phase 1; restarts nothing."""
+        check(self._L.spx_set_primal_phase_one_ratio(self._h, rule))
+        self._primal_phase1_ratio = rule
+
+    def primal_long_steps(self):
+        """(rows the long-step walk passed, passes that passed at least one, the
+        most in one pass, the current rule) of the bounded primal loop's phase 1
+        since create / reset (spx_get_primal_long_steps)."""
+        out = (ctypes.c_int64 * 4)()
+        check(self._L.spx_get_primal_long_steps(self._h, out))
+        return tuple(int(v) for v in out)
 
     def primal_weights(self):
         """Steepest-edge weights of the bounded primal loop by column, n entries
@@ -814,6 +837,7 @@ class Context:
         cfg["primal_weights"] = self._primal_weights
         cfg["primal_phase1_pricing"] = self._primal_phase1_pricing
         cfg["primal_free_pricing"] = self._primal_free_pricing
+        cfg["primal_phase1_ratio"] = self._primal_phase1_ratio
         return cfg
 
     def loop_layout(self):

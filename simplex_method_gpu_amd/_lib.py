@@ -70,6 +70,8 @@ SIGNATURES = {
     "spx_set_primal_pricing": (ctypes.c_int, [_p, _i32]),
     "spx_set_primal_phase_one_pricing": (ctypes.c_int, [_p, _i32]),
     "spx_set_primal_free_pricing": (ctypes.c_int, [_p, _i32]),
+    "spx_set_primal_phase_one_ratio": (ctypes.c_int, [_p, _i32]),
+    "spx_get_primal_long_steps": (ctypes.c_int, [_p, _p]),
     "spx_get_primal_weights": (ctypes.c_int, [_p, _p]),
     "spx_get_dual_flips": (ctypes.c_int, [_p, _p]),
     "spx_set_cost": (ctypes.c_int, [_p, _p]),

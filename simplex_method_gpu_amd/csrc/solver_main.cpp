@@ -54,6 +54,14 @@
 //                  candidates with the steepest-edge weights);
 //                  inert without --phase1 or under --primal-pricing dantzig;
 //                  without --primal-box it is refused by name (exit 1)
+//   --phase1-ratio R  ratio test of --phase1's passes: textbook (default) | long
+//                  (SPX_PRIMAL_RATIO_LONG_STEP, spx_set_primal_phase_one_ratio: the
+//                  walk goes past rows that reach the bound they violate while
+//                  the sum of violations still falls); with the
+//                  option one more line "Long steps: rows passed R, passes P,
+//                  most in one pass M" follows the result; inert without
+//                  --phase1; an unknown word is refused by name (exit 1), and so
+//                  is the option without --primal-box
 //   --free-pricing R  entering rule of --primal-box where --lower holds a free
 //                  column under --primal-pricing steepest: dantzig (default: the
 //                  library's refusal is printed, exit 1) | steepest
@@ -134,7 +142,7 @@ static void usage() {
     std::cerr << "usage: solver [--max-iter K] [--eps E] [--compat] [--device D] [--no-iter-lines] [--json]"
                  " [--threads T] [--write-bin F] [--write-text F] [--no-solve] [--ratio reference|guarded|harris]"
                  " [--piv-tol T] [--feas-tol T] [--refactor K] [--window W] [--pricing dantzig|devex|steepest] [--tableau] [--dual] [--primal-box [--phase1] [--primal-pricing dantzig|steepest] [--phase1-pricing dantzig|steepest] [--free-pricing dantzig|steepest] [--primal-weights reference|exact]]"
-                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F] [--ranging PREFIX] [--bound-ranging PREFIX]"
+                 " [--dual-pricing dantzig|steepest] [--dual-ratio textbook|long] [--bounds F] [--lower F] [--ranging PREFIX] [--bound-ranging PREFIX] [--phase1-ratio textbook|long]"
                  " [--mps [--big-m M]]"
                  " (<file> | --gen m n seed)\n";
 }
@@ -157,6 +165,7 @@ int main(int argc, char* argv[]) {
     bool primal_pricing_given = false, primal_steepest = false;
     bool primal_weights_given = false, primal_exact = false;
     bool phase1_pricing_given = false, phase1_steepest = false;
+    bool phase1_ratio_given = false, phase1_long = false;
     bool free_pricing_given = false, free_steepest = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
@@ -220,6 +229,16 @@ int main(int argc, char* argv[]) {
             }
             phase1_pricing_given = true;
             phase1_steepest = r == "steepest";
+        }
+        else if (s == "--phase1-ratio") {
+            need(1);
+            const std::string r = argv[++a];
+            if (r != "textbook" && r != "long") {
+                std::cerr << "--phase1-ratio " << r << ": textbook or long\n";
+                return 1;
+            }
+            phase1_ratio_given = true;
+            phase1_long = r == "long";
         }
         else if (s == "--free-pricing") {
             need(1);
@@ -294,6 +313,10 @@ int main(int argc, char* argv[]) {
     }
     if (phase1_pricing_given && !primal_box) {
         std::cerr << "--phase1-pricing needs --primal-box: it is the rule of the bounded primal loop's phase 1\n";
+        return 1;
+    }
+    if (phase1_ratio_given && !primal_box) {
+        std::cerr << "--phase1-ratio needs --primal-box: it is the ratio test of the bounded primal loop's phase 1\n";
         return 1;
     }
     if (free_pricing_given && !primal_box) {
@@ -415,6 +438,14 @@ int main(int argc, char* argv[]) {
             return EXIT_FAILURE;
         }
     }
+    if (phase1_long) {
+        rc = spx_set_primal_phase_one_ratio(ctx, SPX_PRIMAL_RATIO_LONG_STEP);
+        if (rc != SPX_OK) {
+            std::cerr << "spx_set_primal_phase_one_ratio failed (" << rc << "): " << spx_last_error() << "\n";
+            spx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+    }
     const TimePoint t_init_end = Clock::now();
     double z = 0.0;
     int32_t status = 0;
@@ -432,6 +463,8 @@ int main(int argc, char* argv[]) {
     if (primal_box) spx_get_primal_flips(ctx, pflips);
     int64_t ph1[4] = {0, 0, 0, 0};
     if (phase1) spx_get_primal_phase1(ctx, ph1);
+    int64_t lsteps[4] = {0, 0, 0, 0};
+    if (phase1_ratio_given) spx_get_primal_long_steps(ctx, lsteps);
     if (!ranging_prefix.empty()) {  // PREFIX.cost.txt (n lines) and PREFIX.rhs.txt (m lines): down up index index
         std::vector<double> dn((size_t)n), up((size_t)n);
         std::vector<int64_t> kd((size_t)n), ku((size_t)n);
@@ -531,6 +564,9 @@ int main(int argc, char* argv[]) {
         case SPX_STATUS_INFEASIBLE: std::cout << "Problem infeasible.\n"; break;
         default: std::cout << "MAX_ITER exceeded.\n"; break;
     }
+    if (phase1_ratio_given)
+        std::cout << "Long steps: rows passed " << lsteps[0] << ", passes " << lsteps[1] << ", most in one pass "
+                  << lsteps[2] << '\n';
     std::cout << '\n';
     const TimePoint t_host_free = Clock::now();
     lp = lpio::LP();

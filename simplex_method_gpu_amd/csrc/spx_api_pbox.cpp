@@ -200,6 +200,17 @@ int pbox_se_restart(spx_ctx* x) {
     return SPX_OK;
 }
 
+// the long-step ratio test's counters and list capacity, on first use (after pbox_setup)
+int pbox_long_setup(spx_ctx* x) {
+    PboxState& s = x->pbox;
+    if (s.lg.lrec) return SPX_OK;
+    // SPX_PBOX_LONG_CAP (tests): fewer soft breakpoints in LDS than PBOX_LONG_CAP, so small shapes walk by rounds
+    const size_t cap = env_bytes("SPX_PBOX_LONG_CAP");
+    s.lg.cap = cap > 0 && cap < (size_t)PBOX_LONG_CAP ? (int32_t)cap : PBOX_LONG_CAP;
+    SPX_TRY(x->alloc(&s.lg.lrec, 1));
+    return SPX_OK;
+}
+
 // timing: the next event pair around the vtb / tau step
 int vtb_events(spx_ctx* x, hipEvent_t* v0, hipEvent_t* v1) {
     PboxState& s = x->pbox;
@@ -232,6 +243,9 @@ int vtb_events(spx_ctx* x, hipEvent_t* v0, hipEvent_t* v1) {
 // the same readback brings §7h's four-step pass back, with the weights it finds.
 // Steepest edge with free columns (opt-in): every pass is [vtb ->]
 // price_se_f -> update_f -> step_se_f -> tau, vtb under the same host condition.
+// Phase 1's long-step ratio test (opt-in): a pass that k_pbox_vtb
+// opens gets k_pbox_long1 between its update and its step kernel, in all four
+// phase-1 capable shapes; it rewrites the ratio partials and nothing else.
 int iterate_pbox(spx_ctx* x, int64_t k) {
     SPX_TRY(pbox_setup(x));
     if (!x->pbox.checked) SPX_TRY(pbox_check_entry(x));
@@ -258,11 +272,16 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
     } else {
         s.se_stale = true;  // a Dantzig pass keeps no weights
     }
+    // phase 1's long-step ratio test: k_pbox_long1 between the update and the step kernel of every
+    // pass that k_pbox_vtb opens
+    const bool lng = s.phase1 && s.p1ratio == SPX_PRIMAL_RATIO_LONG_STEP;
+    if (lng) SPX_TRY(pbox_long_setup(x));
     const int64_t target = x->pivots + k;
     SPX_TRY(set_limit(x, target));
     while (x->status == SPX_STATUS_MAX_ITER && x->pivots < target) {
         const int64_t round = target - x->pivots;
         for (int64_t i = 0; i < round; ++i) {
+            const bool p1pass = s.phase1 && (s.ninf > 0 || s.y_stale);
             hipEvent_t p0 = nullptr, p1 = nullptr, u0 = nullptr, u1 = nullptr;
             if (x->timing) SPX_TRY(pass_events(x, &p0, &p1, &u0, &u1));
             if (steep && fr) {
@@ -277,6 +296,7 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
                 HIP_TRY(launch_pbox_price_se_f(x->P, se_args, s.p1, s.se, s.fr, s.secfg, x->stream, p0, p1));
                 if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
                 HIP_TRY(launch_pbox_update_f(x->P, se_args, s.p1, s.fr, s.cfg, x->stream, u0, u1));
+                if (lng && p1pass) HIP_TRY(launch_pbox_long1(x->P, se_args, s.p1, &s.fr, s.lg, x->stream));
                 HIP_TRY(launch_pbox_step_se_f(x->P, se_args, s.p1, s.se, s.fr, x->stream));
                 HIP_TRY(launch_pbox_tau(x->P, s.se, s.cfg, x->stream, t0, t1));
                 ++x->n_eager;
@@ -294,6 +314,7 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
                 HIP_TRY(launch_pbox_price_se1(x->P, se_args, s.p1, s.se, s.secfg, x->stream, p0, p1));
                 if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
                 HIP_TRY(launch_pbox_update1(x->P, se_args, s.p1, s.cfg, x->stream, u0, u1));
+                if (lng) HIP_TRY(launch_pbox_long1(x->P, se_args, s.p1, nullptr, s.lg, x->stream));
                 HIP_TRY(launch_pbox_step_se1(x->P, se_args, s.p1, s.se, x->stream));
                 HIP_TRY(launch_pbox_tau(x->P, s.se, s.cfg, x->stream, t0, t1));
                 ++x->n_eager;
@@ -320,6 +341,7 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
                 HIP_TRY(launch_pbox_price_f(x->P, s.args, s.p1, s.fr, s.cfg, x->stream, p0, p1));
                 if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
                 HIP_TRY(launch_pbox_update_f(x->P, s.args, s.p1, s.fr, s.cfg, x->stream, u0, u1));
+                if (lng && p1pass) HIP_TRY(launch_pbox_long1(x->P, s.args, s.p1, &s.fr, s.lg, x->stream));
                 HIP_TRY(launch_pbox_step_f(x->P, s.args, s.p1, s.fr, x->stream));
                 ++x->n_eager;
                 continue;
@@ -341,6 +363,7 @@ int iterate_pbox(spx_ctx* x, int64_t k) {
                 HIP_TRY(launch_pbox_price1(x->P, s.args, s.p1, s.cfg, x->stream, p0, p1));
                 if (p0) HIP_TRY(hipEventRecord(x->ev_xend[x->n_price - 1], x->stream));
                 HIP_TRY(launch_pbox_update1(x->P, s.args, s.p1, s.cfg, x->stream, u0, u1));
+                if (lng) HIP_TRY(launch_pbox_long1(x->P, s.args, s.p1, nullptr, s.lg, x->stream));
                 HIP_TRY(launch_pbox_step1(x->P, s.args, s.p1, x->stream));
                 ++x->n_eager;
                 continue;
@@ -362,6 +385,7 @@ int pbox_on_reset(spx_ctx* x) {
         HIP_TRY(hipMemsetAsync(x->pbox.args.rec, 0, sizeof(PboxRec), x->stream));
         HIP_TRY(hipMemsetAsync(x->pbox.p1.ph, 0, sizeof(PboxPhase), x->stream));  // (launch_reset rebuilds y)
     }
+    if (x->pbox.lg.lrec) HIP_TRY(hipMemsetAsync(x->pbox.lg.lrec, 0, sizeof(PboxLongRec), x->stream));
     x->pbox.checked = false;
     x->pbox.y_dirty = false;
     x->pbox.ninf = x->pbox.y_stale = 0;
@@ -478,6 +502,28 @@ int spx_set_primal_phase_one_pricing(spx_ctx* x, int32_t rule) {
                     "with steepest-edge pricing (spx_set_primal_pricing) while phase 1 is on (spx_set_primal_phase1); "
                     "switch phase 1 off or set SPX_PRIMAL_PRICING_DANTZIG first");
     x->pbox.p1rule = rule;  // (the weights do not depend on the phase: nothing restarts)
+    return SPX_OK;
+}
+
+int spx_set_primal_phase_one_ratio(spx_ctx* x, int32_t rule) {
+    if (!x) return fail(SPX_ERR_ARG, "ctx is NULL");
+    if (rule != SPX_PRIMAL_RATIO_TEXTBOOK && rule != SPX_PRIMAL_RATIO_LONG_STEP)
+        return fail(SPX_ERR_ARG, "bad primal phase-1 ratio rule %d", rule);
+    x->pbox.p1ratio = rule;  // (read per pass: nothing restarts, nothing is invalidated)
+    return SPX_OK;
+}
+
+int spx_get_primal_long_steps(spx_ctx* x, int64_t out[4]) {
+    if (!x || !out) return fail(SPX_ERR_ARG, "NULL argument");
+    out[0] = out[1] = out[2] = 0;
+    out[3] = x->pbox.p1ratio;
+    if (!x->pbox.lg.lrec) return SPX_OK;  // no long-step pass yet
+    PboxLongRec r;
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(&r, x->pbox.lg.lrec, sizeof r, hipMemcpyDeviceToHost));
+    out[0] = r.passed;
+    out[1] = r.passes;
+    out[2] = r.max_pass;
     return SPX_OK;
 }
 

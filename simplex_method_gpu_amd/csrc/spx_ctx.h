@@ -179,6 +179,11 @@ struct PboxState {
     // edge with frrule == STEEPEST), and with phase1 off the device's ninf is 0.
     spx::PboxFreeArgs fr{};
     int8_t* fr_flags = nullptr;  // n (fr.is_free)
+    // phase 1's ratio test (spx_set_primal_phase_one_ratio): consulted per pass, under the host
+    // condition that launches k_pbox_vtb.  lg.lrec != nullptr  <=>  a pass ran under SPX_PRIMAL_RATIO_LONG_STEP (the
+    // counters, allocated by the first such pass; a context that never sets the rule allocates and launches nothing)
+    int32_t p1ratio = SPX_PRIMAL_RATIO_TEXTBOOK;
+    spx::PboxLongArgs lg{};
 };
 
 // Sensitivity ranging (spx_ranging.h; everything that reads or writes it is in

@@ -324,6 +324,48 @@ hipError_t launch_pbox_price_se_f(const Params& P, const PboxArgs& D, const Pbox
 hipError_t launch_pbox_step_se_f(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxSeArgs& E,
                                  const PboxFreeArgs& F, hipStream_t s);
 
+// Phase 1's long-step ratio test (opt-in,
+// spx_set_primal_phase_one_ratio).  A pass enqueued while the host last saw
+// ninf > 0 or y stale gets one more launch between the update and the step
+// kernel, under any of the four phase-1 capable pass shapes:
+//   k_pbox_long1<FREE>  one workgroup.  Returns at once under the step kernels'
+//                  return conditions and when ninf == 0.  Reads this pass's
+//                  alpha, x_b, ub_B (FREE: lb_B), w, the pass record and
+//                  at_upper[p]; forms every row's soft breakpoint (an infeasible
+//                  row reaches the bound it violates: the update kernels' entry)
+//                  and hard breakpoint (a feasible row's entry, or the far bound
+//                  of a row with a soft one), h = the hard minimum, and walks the
+//                  soft breakpoints before h in (t, 2 row + side) order from
+//                  slope = sigma_p d_p, adding |ahat_i|: the first with slope >=
+//                  -eps leaves, else h, else the last soft one.  The soft
+//                  breakpoints are compacted into LDS (PBOX_LONG_CAP entries of
+//                  (t, idx, |ahat|), 48 KiB), sorted by rank and summed by thread
+//                  0 in sorted order; a longer list (or a lower
+//                  PboxLongArgs::cap: SPX_PBOX_LONG_CAP) is walked by rounds of
+//                  argmin over global memory, with the same entries, order and
+//                  sums.  The leaving entry goes to rparts[0], "none" to the
+//                  other update_grid slots: the step kernels run unchanged.
+//                  Thread 0 keeps the counters.
+constexpr int PBOX_LONG_BLOCK = 1024;
+constexpr int PBOX_LONG_CAP = 2048;  // soft breakpoints kept in LDS
+
+struct alignas(16) PboxLongRec {  // counted by the walk, whether the pass then flips or pivots
+    int64_t passed;    // rows the walk passed since create / spx_reset
+    int64_t passes;    // passes that passed at least one
+    int64_t max_pass;  // the most in one pass
+    int64_t pad;
+};
+
+struct PboxLongArgs {
+    PboxLongRec* lrec;
+    int32_t cap;  // list capacity, 1 .. PBOX_LONG_CAP
+    int32_t pad;
+};
+
+// F: the free-column arrays of a context that runs the *_f kernels, else nullptr
+hipError_t launch_pbox_long1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs* F,
+                             const PboxLongArgs& G, hipStream_t s);
+
 // Exact weights of a warm basis (spx_pbox_wexact.hip): gamma_j =
 // 1 + ||B^-1 A_j||^2 for every column on nb_list, from W.S = the true B^-1 of the
 // current basis (m x L row-major, nothing pending: the host materialises it

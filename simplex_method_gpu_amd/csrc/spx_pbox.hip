@@ -2532,6 +2532,250 @@ __global__ __launch_bounds__(1024) void k_pbox_step_se_f(Params P, PboxArgs D, P
 }
 
 // ---------------------------------------------------------------------------
+// Phase 1's long-step ratio test: the walk past breakpoints
+// ---------------------------------------------------------------------------
+namespace {
+
+// row i's entries: the soft breakpoint (an infeasible row reaches the bound it
+// violates: k_pbox_update1's / _update_f's own entry, same operands, same
+// operations) and the hard one (a feasible row's entry of those kernels, or the
+// far bound of a row that has a soft breakpoint); idx INT64_MAX = none
+template <bool FREE>
+__device__ __forceinline__ void long_entries(int64_t i, double ah, double xi, double ubi, double lbi, double wi,
+                                             double ptol, double& st, int64_t& si, double& ht, int64_t& hi) {
+    st = ht = INFINITY;
+    si = hi = INT64_MAX;
+    if (wi == 0.0) {
+        if (ah > ptol && (!FREE || lbi > -INFINITY)) {
+            ht = (xi > 0.0 ? xi : 0.0) / ah;
+            hi = 2 * i;
+        } else if (ah < -ptol && ubi < INFINITY) {
+            const double gap = ubi - xi;
+            ht = (gap > 0.0 ? gap : 0.0) / (-ah);
+            hi = 2 * i + 1;
+        }
+    } else if (wi > 0.0) {  // below: rises to 0 (soft), then to its upper bound (hard)
+        if (ah < -ptol) {
+            st = xi / ah;
+            si = 2 * i;
+            if (ubi < INFINITY) {
+                ht = (xi - ubi) / ah;
+                hi = 2 * i + 1;
+            }
+        }
+    } else {  // above: falls to its upper bound (soft), then to 0 (hard)
+        if (ah > ptol) {
+            st = (xi - ubi) / ah;
+            si = 2 * i + 1;
+            ht = xi / ah;
+            hi = 2 * i;
+        }
+    }
+}
+
+}  // namespace
+
+// One workgroup, between k_pbox_update1 / k_pbox_update_f and the step kernel,
+// phase-1 passes only (it returns at once under the step kernels' own return
+// conditions and when ninf == 0).  The sum of violations is piecewise linear
+// along the entering direction with slope sigma_p d_p < 0 at t = 0; it gains
+// |ahat_i| where row i reaches the bound it violates.  h = the hard minimum in
+// (t, 2 row + side) order; the soft breakpoints before h are compacted into LDS,
+// sorted by rank (the keys are distinct: one per row), and thread 0 adds their
+// |ahat| in that order: the first with slope >= -eps leaves; none: h leaves, or
+// with no hard entry the last soft one.  The leaving entry goes to rparts[0] and
+// "none" to every other slot, so the step kernels, which take their winner from
+// rparts only, run unchanged.  More than G.cap soft breakpoints: rounds of
+// argmin over the rows strictly beyond the last one taken, read from global
+// memory; thread 0 sees the same entries in the same order with the same
+// |ahat|, so both paths select the same row.  Every loop bound is m or the list
+// count; nothing here waits on another workgroup.
+template <bool FREE>
+__global__ __launch_bounds__(PBOX_LONG_BLOCK) void k_pbox_long1(Params P, PboxArgs D, Pbox1Args X, PboxFreeArgs F,
+                                                                PboxLongArgs G) {
+    constexpr int BLOCK = PBOX_LONG_BLOCK, WAVES = BLOCK / 64, PER = PBOX_LONG_CAP / BLOCK;
+    __shared__ double s_t[PBOX_LONG_CAP];
+    __shared__ double s_a[PBOX_LONG_CAP];
+    __shared__ int64_t s_i[PBOX_LONG_CAP];
+    __shared__ ArgMinEntry s_red[WAVES];
+    __shared__ ArgMinEntry s_win;
+    __shared__ PboxSnap S;
+    __shared__ int32_t s_ninf, s_cnt, s_done;
+    const DevState* st = P.st;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t m = P.m;
+    if (tid == 0) {
+        S.it = st->iter;
+        S.limit = st->limit;
+        S.status = st->status;
+        S.fresh = D.rec->fresh;
+        S.p = D.rec->p;
+        S.d_p = D.rec->d_p;
+        s_ninf = X.ph->ninf;
+        s_cnt = 0;
+        s_done = 0;
+    }
+    __syncthreads();
+    const int64_t it = S.it;
+    if (S.status != ST_RUNNING || it >= S.limit || !S.fresh || s_ninf <= 0) return;
+    const int64_t p = S.p;
+    bool fr_p = false;
+    if constexpr (FREE) fr_p = F.is_free[p] != 0;
+    const double sg = fr_p ? (S.d_p < 0.0 ? 1.0 : -1.0) : (D.at_upper[p] ? -1.0 : 1.0);
+    const double* al = ((it + 1) & 1) ? P.alpha1 : P.alpha0;  // this pass's alpha (the step kernels' `al`)
+    const double ptol = D.piv_tol;
+    const int cap = G.cap < PBOX_LONG_CAP ? G.cap : PBOX_LONG_CAP;
+
+    auto entries = [&](int64_t i, double& t1, int64_t& i1, double& t2, int64_t& i2, double& aa) {
+        const double ah = sg * al[i];
+        double lbi = 0.0;
+        if constexpr (FREE) lbi = F.lb_B[i];
+        long_entries<FREE>(i, ah, P.x_b[i], D.ub_B[i], lbi, X.w[i], ptol, t1, i1, t2, i2);
+        aa = fabs(ah);
+    };
+    // the workgroup's (value, index) argmin; every thread returns with it in s_win
+    auto block_argmin = [&](double v, int64_t j) {
+        wave_argmin(v, j);
+        if (lane == 0) s_red[wave] = ArgMinEntry{v, j};
+        __syncthreads();
+        if (tid == 0) {
+            ArgMinEntry t = s_red[0];
+            for (int w = 1; w < WAVES; ++w)
+                if (argmin_better(s_red[w].val, s_red[w].idx, t.val, t.idx)) t = s_red[w];
+            s_win = t;
+        }
+        __syncthreads();
+    };
+
+    // h: the hard minimum
+    double hv = INFINITY;
+    int64_t hj = INT64_MAX;
+    for (int64_t i = tid; i < m; i += BLOCK) {
+        double t1, t2, aa;
+        int64_t i1, i2;
+        entries(i, t1, i1, t2, i2, aa);
+        if (argmin_better(t2, i2, hv, hj)) {
+            hv = t2;
+            hj = i2;
+        }
+    }
+    block_argmin(hv, hj);
+    hv = s_win.val;
+    hj = s_win.idx;
+    // the soft breakpoints before h, in any order (slots 0 .. cap - 1 are stored, all are counted)
+    for (int64_t i = tid; i < m; i += BLOCK) {
+        double t1, t2, aa;
+        int64_t i1, i2;
+        entries(i, t1, i1, t2, i2, aa);
+        if (i1 != INT64_MAX && argmin_better(t1, i1, hv, hj)) {
+            const int k = atomicAdd(&s_cnt, 1);  // (an integer count: order-free; the sort below fixes the order)
+            if (k < cap) {
+                s_t[k] = t1;
+                s_i[k] = i1;
+                s_a[k] = aa;
+            }
+        }
+    }
+    __syncthreads();
+    const int cnt = s_cnt;  // <= m
+
+    double slope = sg * S.d_p;  // thread 0's
+    int64_t npass = 0;
+    ArgMinEntry win{hv, hj};  // thread 0's: h, or none, unless the walk finds a row
+    if (cnt <= cap) {
+        double kt[PER], ka[PER];
+        int64_t ki[PER];
+        int rk[PER];
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int e = tid + u * BLOCK;
+            rk[u] = -1;
+            if (e < cnt) {
+                kt[u] = s_t[e];
+                ki[u] = s_i[e];
+                ka[u] = s_a[e];
+                int r = 0;
+                for (int f = 0; f < cnt; ++f) r += argmin_better(s_t[f], s_i[f], kt[u], ki[u]) ? 1 : 0;
+                rk[u] = r;  // 0 <= r < cnt: the entries strictly before this one
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            if (rk[u] >= 0) {
+                s_t[rk[u]] = kt[u];
+                s_i[rk[u]] = ki[u];
+                s_a[rk[u]] = ka[u];
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            bool found = false;
+            for (int k = 0; k < cnt; ++k) {
+                slope += s_a[k];
+                if (slope >= -P.eps) {
+                    win = ArgMinEntry{s_t[k], s_i[k]};
+                    found = true;
+                    break;
+                }
+                ++npass;
+            }
+            if (!found && hj == INT64_MAX && cnt > 0) {  // no hard entry: the last soft breakpoint leaves
+                win = ArgMinEntry{s_t[cnt - 1], s_i[cnt - 1]};
+                --npass;
+            }
+        }
+    } else {
+        double lastv = -INFINITY;  // (every t is >= 0)
+        int64_t lastj = -1;
+        for (int round = 0; round < cnt; ++round) {
+            double bv = INFINITY;
+            int64_t bj = INT64_MAX;
+            for (int64_t i = tid; i < m; i += BLOCK) {
+                double t1, t2, aa;
+                int64_t i1, i2;
+                entries(i, t1, i1, t2, i2, aa);
+                if (i1 != INT64_MAX && argmin_better(t1, i1, hv, hj) && argmin_better(lastv, lastj, t1, i1) &&
+                    argmin_better(t1, i1, bv, bj)) {
+                    bv = t1;
+                    bj = i1;
+                }
+            }
+            block_argmin(bv, bj);  // (round < cnt: an entry is left, 0 <= idx < 2 m)
+            if (tid == 0) {
+                if (s_win.idx == INT64_MAX) {  // (not reached: cnt entries were counted)
+                    s_done = 1;
+                } else if ((slope += fabs(al[s_win.idx >> 1])) >= -P.eps) {
+                    win = s_win;
+                    s_done = 1;
+                } else if (round == cnt - 1 && hj == INT64_MAX) {
+                    win = s_win;
+                } else {
+                    ++npass;
+                }
+            }
+            lastv = s_win.val;
+            lastj = s_win.idx;
+            __syncthreads();  // (s_done; also fences the next round's stores to s_red and s_win)
+            if (s_done) break;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        s_win = win;
+        PboxLongRec* r = G.lrec;
+        if (npass > 0) {
+            r->passed += npass;
+            r->passes += 1;
+            if (npass > r->max_pass) r->max_pass = npass;
+        }
+    }
+    __syncthreads();
+    const ArgMinEntry out = s_win;
+    for (int g = tid; g < D.update_grid; g += BLOCK) D.rparts[g] = g == 0 ? out : ArgMinEntry{INFINITY, INT64_MAX};
+}
+
+// ---------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------
 namespace {
@@ -2839,6 +3083,13 @@ hipError_t launch_pbox_step_se_f(const Params& P, const PboxArgs& D, const Pbox1
 
 hipError_t launch_pbox_stage(const Params& P, hipStream_t s) {
     hipLaunchKernelGGL(k_pbox_stage, dim3(1), dim3(1024), 0, s, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbox_long1(const Params& P, const PboxArgs& D, const Pbox1Args& X, const PboxFreeArgs* F,
+                             const PboxLongArgs& G, hipStream_t s) {
+    if (F) hipLaunchKernelGGL(k_pbox_long1<true>, dim3(1), dim3(PBOX_LONG_BLOCK), 0, s, P, D, X, *F, G);
+    else hipLaunchKernelGGL(k_pbox_long1<false>, dim3(1), dim3(PBOX_LONG_BLOCK), 0, s, P, D, X, PboxFreeArgs{}, G);
     return hipGetLastError();
 }
 

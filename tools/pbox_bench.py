@@ -143,6 +143,21 @@ columns).  With --solve, whole solves of tests/primal_lu_ref.py general_lu at
 every --solve-shape from the slack basis, Dantzig / steepest / Dantzig /
 steepest, each with the CPU certificate (certificate_lu).
 
+--phase1-ratio long measures phase 1's long-step ratio test
+instead, one child per side, the sides alternating, each twice:
+  p1_dense_textbook / p1_dense_long   boxed_general(m, n, seed) from the slack basis
+                under Dantzig, in timed chunks of --phase1-chunk pivots that end
+                inside phase 1: the textbook pass, and the pass with k_pbox_long1
+                between k_pbox_update1 and k_pbox_step1 (rows passed, passes that
+                passed one, the most in one pass)
+  p1_se_textbook / p1_se_long         the same under steepest edge through phase 1
+  p1_never_parent / p1_never_this     with --parent-root: the textbook pass of a
+                context that never opts in, on a build of the parent commit and on
+                this build
+With --solve, whole solves of boxed_general and general_lu at every --solve-shape
+under both entering rules, textbook / long / textbook / long, with pivots,
+phase-1 passes, rows passed, seconds and the CPU certificate.
+
     python tools/pbox_bench.py [--k 1000 --warm 200] [--solve --solve-shape 1024 4096 4 --rows]
                                [--out profiles/pbox_c3.json]
     python tools/pbox_bench.py --phase1 [--out profiles/pbox_phase1_c3.json]
@@ -161,6 +176,9 @@ steepest, each with the CPU certificate (certificate_lu).
                                --kernel-shape 4096 16384 5 [--parent-root DIR] [--out profiles/ranging_c3.json]
     python tools/pbox_bench.py --bound-ranging --kernel-shape 1024 4096 4 --kernel-shape 2048 8192 5
                                --kernel-shape 4096 16384 5 [--parent-root DIR] [--out profiles/bound_ranging_c3.json]
+    python tools/pbox_bench.py --phase1-ratio long --warm 20 --k 400 --phase1-chunk 50 [--parent-root DIR]
+                               [--solve --solve-shape 512 2048 4 --solve-shape 1024 4096 4]
+                               [--out profiles/pbox_p1long_c3.json]
 """
 import argparse
 import json
@@ -295,6 +313,24 @@ def run_pbox_flag(a):
     return res
 
 
+def with_ratio(ctx, a):
+    """--phase1-ratio long: the context under SPX_PRIMAL_RATIO_LONG_STEP.  Under textbook the
+    setter is not called: the context never opts in (and a parent build has no such setter)."""
+    if a.phase1_ratio == "long":
+        import simplex_method_gpu_amd as spx
+
+        ctx.set_primal_phase1_ratio(spx.PRIMAL_RATIO_LONG_STEP)
+    return ctx
+
+
+def long_record(ctx, a):
+    rec = {"phase1_ratio": a.phase1_ratio}
+    if hasattr(ctx, "primal_long_steps"):
+        ls = ctx.primal_long_steps()
+        rec.update({"rows_passed": ls[0], "long_passes": ls[1], "most_in_one_pass": ls[2]})
+    return rec
+
+
 def measure_phase1(make_ctx, k, warm, chunk, want_phase2, warm2=0):
     """Phase-1 passes in chunks of `chunk` pivots, at most k pivots: only chunks
     that end with rows still out of bounds count (all their passes are phase-1
@@ -322,6 +358,9 @@ def measure_phase1(make_ctx, k, warm, chunk, want_phase2, warm2=0):
             ph = nph
         res.update({"ninf_after": ph[3], "pivots": piv, "passes": passes, "status": int(st),
                     "it_per_s": round(piv / dt, 1) if dt else None, "passes_per_s": round(passes / dt, 1) if dt else None})
+        if hasattr(ctx, "primal_long_steps"):
+            ls = ctx.primal_long_steps()
+            res.update({"rows_passed": ls[0], "long_passes": ls[1], "most_in_one_pass": ls[2], "phase1_ratio_rule": ls[3]})
         if want_phase2:
             guard = 0
             while ctx.primal_phase1()[3] > 0 and guard < 400:
@@ -412,8 +451,9 @@ def run_p1_dense(a):
     A, b, c, u = primal_phase1_ref.boxed_general(a.m, a.n, a.seed)
     A_cols = np.ascontiguousarray(A.T)
     del A
-    return measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
-                                                     primal_phase1=True, timing=timing), a.k, a.warm, a.k, False)
+    return measure_phase1(lambda timing: with_ratio(spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                                                                primal_phase1=True, timing=timing), a),
+                          a.k, a.warm, a.phase1_chunk or a.k, False)
 
 
 def run_p1_se(a):
@@ -427,9 +467,10 @@ def run_p1_se(a):
     A_cols = np.ascontiguousarray(A.T)
     del A
     S = spx.PRIMAL_PRICING_STEEPEST
-    return measure_phase1(lambda timing: spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
-                                                     primal_phase1=True, primal_pricing=S, primal_phase1_pricing=S,
-                                                     timing=timing), a.k, a.warm, a.k, False)
+    return measure_phase1(lambda timing: with_ratio(spx.Context(A_cols, b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
+                                                                primal_phase1=True, primal_pricing=S, primal_phase1_pricing=S,
+                                                                timing=timing), a),
+                          a.k, a.warm, a.phase1_chunk or a.k, False)
 
 
 def _parent_bindings():
@@ -489,6 +530,7 @@ def run_solve_lu(a):
         with spx.Context(np.ascontiguousarray(A.T), b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, lower=l, upper=u,
                          refactor_every=a.refactor, primal_phase1=True, primal_pricing=rule,
                          primal_phase1_pricing=rule, primal_free_pricing=rule) as ctx:
+            with_ratio(ctx, a)
             ctx.iterate(20)  # (first-launch costs)
             ctx.reset()
             t0 = time.perf_counter()
@@ -497,8 +539,9 @@ def run_solve_lu(a):
             x, up = ctx.primal()
             fl = ctx.primal_flips()
             ph = ctx.primal_phase1()
+            lrec = long_record(ctx, a)
         rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "primal_pricing": a.primal_pricing,
-               "free_columns": int(np.isneginf(l).sum()), "free_basic": int(np.isneginf(l)[r.b_ixs].sum()),
+               "free_columns": int(np.isneginf(l).sum()), "free_basic": int(np.isneginf(l)[r.b_ixs].sum()), **lrec,
                "status": int(r.status), "pivots": r.pivots, "z": r.z, "seconds": round(dt, 4),
                "it_per_s": round(r.pivots / dt, 1), "flip_passes": fl[0], "to_upper": fl[1],
                "phase1_passes": ph[0], "phase1_pivots": ph[1], "phase1_rows": ph[2]}
@@ -536,6 +579,7 @@ def run_solve_p1(a):
         with spx.Context(np.ascontiguousarray(A.T), b, c, device=0, algorithm=spx.ALGO_PRIMAL_BOX, upper=u,
                          refactor_every=a.refactor, primal_phase1=True, primal_pricing=rule,
                          primal_phase1_pricing=rule) as ctx:
+            with_ratio(ctx, a)
             ctx.iterate(20)  # (first-launch costs)
             ctx.reset()
             t0 = time.perf_counter()
@@ -544,7 +588,8 @@ def run_solve_p1(a):
             x, up = ctx.primal()
             fl = ctx.primal_flips()
             ph = ctx.primal_phase1()
-        rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "primal_pricing": a.primal_pricing,
+            lrec = long_record(ctx, a)
+        rec = {"m": m, "n": n, "seed": seed, "refactor_every": a.refactor, "primal_pricing": a.primal_pricing, **lrec,
                "phase1_pricing": a.primal_pricing, "status": int(r.status), "pivots": r.pivots, "z": r.z,
                "seconds": round(dt, 4), "it_per_s": round(r.pivots / dt, 1), "flip_passes": fl[0], "to_upper": fl[1],
                "phase1_passes": ph[0], "phase1_pivots": ph[1], "phase1_rows": ph[2]}
@@ -849,7 +894,7 @@ def run_dual_box(a):
                                               timing=timing), a.k, a.warm)
 
 
-def child(a, role, pricing="dantzig", se_lds=None, lib=None, root=None):
+def child(a, role, pricing="dantzig", se_lds=None, lib=None, root=None, ratio="textbook"):
     env = dict(os.environ)
     if root is not None:
         env["SPX_BENCH_ROOT"] = os.path.abspath(root)
@@ -859,7 +904,8 @@ def child(a, role, pricing="dantzig", se_lds=None, lib=None, root=None):
         env["SPX_LIB"] = os.path.abspath(lib)
     cmd = [sys.executable, os.path.abspath(__file__), "--role", role, "--primal-pricing", pricing, "--m", str(a.m), "--n", str(a.n),
            "--seed", str(a.seed), "--k", str(a.k), "--warm", str(a.warm), "--refactor", str(a.refactor),
-           "--sparse-every", str(a.sparse_every), "--sparse-chunk", str(a.sparse_chunk)]
+           "--sparse-every", str(a.sparse_every), "--sparse-chunk", str(a.sparse_chunk),
+           "--phase1-ratio", ratio, "--phase1-chunk", str(a.phase1_chunk)]
     if a.rows:
         cmd.append("--rows")
     for shape in a.solve_shape:
@@ -911,6 +957,11 @@ def main():
                     help="sensitivity ranging against the exact weight start instead (DESIGN.md 7k)")
     ap.add_argument("--bound-ranging", action="store_true",
                     help="bound ranging against cost ranging instead (DESIGN.md 7n); --parent-root as with --ranging")
+    ap.add_argument("--phase1-ratio", default="textbook", choices=["textbook", "long"],
+                    help="long: phase 1's long-step ratio test against the textbook one instead (DESIGN.md 7o); "
+                         "--parent-root as with --ranging")
+    ap.add_argument("--phase1-chunk", type=int, default=0,
+                    help="p1_dense / p1_se: pivots per timed chunk (0: --k, one chunk)")
     a = ap.parse_args()
     if a.role:  # a child: one side, one JSON line
         run = {"primal": run_primal, "dual": run_dual, "pbox": run_pbox, "solve": run_solve,
@@ -922,6 +973,52 @@ def main():
                "solve_lu": run_solve_lu, "bound_ranging_kernel": run_bound_ranging_kernel,
                "dual_box": run_dual_box}[a.role]
         print(json.dumps(run(a)), flush=True)
+        return
+    if a.phase1_ratio == "long":
+        res = {"m": a.m, "n": a.n, "k": a.k, "warm": a.warm, "seed": a.seed, "phase1_chunk": a.phase1_chunk}
+
+        def side(key, role, pricing, **kw):
+            res[key] = child(a, role, pricing, **kw)
+            sys.stderr.write(f"{key}: {json.dumps(res[key])}\n")
+            sys.stderr.flush()
+
+        # the phase-1 pass under both ratio tests and both entering rules, alternating
+        for again in ("", "_again"):
+            for role, pricing in (("p1_dense", "dantzig"), ("p1_se", "steepest")):
+                for ratio in ("textbook", "long"):
+                    side(f"{role}_{ratio}{again}", role, pricing, ratio=ratio)
+        res["long_over_textbook_passes_per_s"] = {
+            f"{role}{ag}": round(res[f"{role}_long{ag}"]["passes_per_s"] / res[f"{role}_textbook{ag}"]["passes_per_s"], 4)
+            for role in ("p1_dense", "p1_se") for ag in ("", "_again")
+            if res[f"{role}_long{ag}"]["passes_per_s"] and res[f"{role}_textbook{ag}"]["passes_per_s"]}
+        if a.parent_root:  # a context that never opts in, against a build of the parent commit
+            for again in ("", "_again"):
+                for name, root in (("parent", a.parent_root), ("this", None)):
+                    side(f"p1_never_{name}{again}", "p1_dense", "dantzig", root=root)
+            base = res["p1_never_parent"]["passes_per_s"]
+            res["never_passes_per_s_over_parent"] = {k: round(res[k]["passes_per_s"] / base, 4)
+                                                     for k in ("p1_never_this", "p1_never_parent_again", "p1_never_this_again")}
+        if a.solve and a.solve_shape:
+            res["solve"] = []
+            for family, role in (("boxed_general", "solve_p1"), ("general_lu", "solve_lu")):
+                for pricing in ("dantzig", "steepest"):
+                    runs = [child(a, role, pricing, ratio=r) for r in ("textbook", "long", "textbook", "long")]
+                    for i in range(len(a.solve_shape)):
+                        tb, lg = runs[0][i], runs[1][i]
+                        rec = {"family": family, "primal_pricing": pricing, "textbook": tb, "long": lg,
+                               "textbook_again": runs[2][i], "long_again": runs[3][i],
+                               "pivot_ratio": round(tb["pivots"] / lg["pivots"], 2),
+                               "phase1_pass_ratio": round(tb["phase1_passes"] / max(lg["phase1_passes"], 1), 2),
+                               "time_ratio": round(tb["seconds"] / lg["seconds"], 2),
+                               "time_ratio_again": round(runs[2][i]["seconds"] / runs[3][i]["seconds"], 2),
+                               "certificates_ok": bool(all(r[i].get("cert_ok") for r in runs))}
+                        res["solve"].append(rec)
+                        sys.stderr.write(f"solve: {json.dumps(rec)}\n")
+                        sys.stderr.flush()
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
         return
     if a.bound_ranging:
         import copy
